@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X Annex-B indexer / RBSP extractor.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: as typed -- this process then starts one child per GPU and relays rank 0's line -- or under
             python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, higher_is_better, dtype,
+ms_per_step (milliseconds of one timed step), the config and the roofline of the timed kernel (HIP events of the timed
+steps themselves).  --full adds everything else, outside the timed region: the full-size parity checks of the last step's
+outputs against the generator's (and, N > 1, of the gathered rows), and at N = 1 the extra objects below.
+--dump-outputs DIR writes what the last timed step computed (rank 0's index, RBSP arena and summary; seeded samples and
+block sums of the large arrays, float64 / float32 .npy, ~30 MB) to DIR: see dump_outputs().
 
 Metric (BASELINE.json): Annex-B GB/s scanned (+ NAL units/s) on a 16 GiB synthetic
 stream per GPU.  One "step" = one pass of the hot path -- start-code scan + NAL
@@ -19,6 +26,9 @@ Extra objects on that line:
                 per launch (stream read + RBSP written + 32 B/NAL index) divided by
                 its mean duration, measured here with HIP events recorded around
                 that kernel on the stream it runs on (hbs_ctx_enable_timing).
+                With --full it also carries the placed / plain arena comparison and
+                the scalars of other_kernels (record_scalars).
+  --full only:
   cpu_baseline  the reference's loop (find_nal_unit + nal_to_rbsp per NAL) timed on ONE host
                 core over a bounded prefix of rank 0's stream: the real reference library when
                 its prebuilt copy is there (oracle/_ref, "reference"), else the oracle's
@@ -951,6 +961,64 @@ def launch_ranks(n, argv, script=None):
     return 0
 
 
+DUMP_SEED = 0x5EED                  # --dump-outputs: where the samples are taken; fixed, so the same arguments give the same files
+
+
+def dump_outputs(torch, out_dir, index, rbsp, s, n, rb, max_rows=1 << 17, max_bytes=1 << 21, block=1 << 20):
+    """--dump-outputs DIR: what hbs_index_extract handed its caller in the last timed step, as .npy files (~30 MB in all).
+      summary.npy           float64 [nal_count, nal_found, rbsp_bytes, stream_bytes, stop_reason, error]
+      index_rows.npy        float64, a seeded sample of max_rows NAL numbers, ascending (every NAL when n <= max_rows)
+      index_sample.npy      float64 [rows, 5]: start, end, rbsp_off, rbsp_len, status of those NALs
+      index_block_sums.npy  float64 [ceil(n / 1024), 5]: the same five fields summed over every 1024 NALs (every entry counts)
+      rbsp_offsets.npy      float64, a seeded sample of max_bytes offsets into the RBSP arena, ascending
+      rbsp_sample.npy       float32, the arena's bytes at those offsets
+      rbsp_block_sums.npy   float64 [ceil(rb / 1 MiB), 2]: per MiB of the arena the sum of its bytes and the sum of
+                            byte x (offset in the MiB + 1), so that a byte moved within a MiB shows too
+    Every sum is of integers and below 2**53: exact in float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    dev = rbsp.device
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    save("summary", np.array([float(s[f]) for f in ("nal_count", "nal_found", "rbsp_bytes", "stream_bytes", "stop_reason", "error")]))
+    # the index: (start, end, rbsp_off, rbsp_len | status << 32) as int64 words; rbsp_len is u32, status the i32 above it
+    ent = index[: n * 32].view(torch.int64).view(n, 4)
+    fields = torch.stack([ent[:, 0], ent[:, 1], ent[:, 2], ent[:, 3] & 0xFFFFFFFF, ent[:, 3] >> 32], dim=1)
+    if n <= max_rows:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.RandomState(DUMP_SEED).choice(n, max_rows, replace=False)).astype(np.int64)
+    save("index_rows", rows.astype(np.float64))
+    save("index_sample", fields[torch.from_numpy(rows).to(dev)].cpu().numpy().astype(np.float64))
+    nb = (n + 1023) // 1024
+    padded = torch.zeros((nb * 1024, 5), dtype=torch.int64, device=dev)
+    padded[:n] = fields
+    save("index_block_sums", padded.view(nb, 1024, 5).sum(dim=1).cpu().numpy().astype(np.float64))
+    del fields, padded
+    # the arena
+    if rb <= max_bytes:
+        offs = np.arange(rb, dtype=np.int64)
+    else:
+        offs = np.sort(np.random.RandomState(DUMP_SEED + 1).randint(0, rb, size=max_bytes)).astype(np.int64)
+    save("rbsp_offsets", offs.astype(np.float64))
+    save("rbsp_sample", rbsp[torch.from_numpy(offs).to(dev)].cpu().numpy().astype(np.float32))
+    full = rb // block
+    sums = torch.zeros((full + (1 if rb % block else 0), 2), dtype=torch.int64, device=dev)
+    w = torch.arange(1, block + 1, dtype=torch.int64, device=dev)
+    for lo in range(0, full, 64):                                       # 64 MiB at a time: 1 GiB of int64 temporaries
+        hi = min(full, lo + 64)
+        x = rbsp[lo * block: hi * block].view(hi - lo, block).to(torch.int64)
+        sums[lo:hi, 0] = x.sum(dim=1)
+        sums[lo:hi, 1] = (x * w).sum(dim=1)
+    if rb % block:
+        x = rbsp[full * block: rb].to(torch.int64)
+        sums[full, 0] = x.sum()
+        sums[full, 1] = (x * w[: rb - full * block]).sum()
+    save("rbsp_block_sums", sums.cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -958,16 +1026,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--nals", type=int, default=N_NALS_16GIB, help="NALs per GPU (default: 16 GiB of stream)")
     ap.add_argument("--mode", type=int, default=0, help="0 uniform payload (headline), 1 zero-heavy")
-    ap.add_argument("--cpu-sample-nals", type=int, default=1_000_000, help="0 disables the CPU baseline leg")
-    ap.add_argument("--other-kernels", type=int, default=1, help="0 skips the emit / parse / write measurements (N = 1 only)")
-    ap.add_argument("--sweep", type=int, default=1, help="0 skips other_kernels' NAL-size sweep (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything besides the headline: full-size parity checks, and at N = 1 the CPU baseline, "
+                         "the placed / plain arena comparison and other_kernels (each as the three options below allow)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64 / float32, seeded samples and block sums; see dump_outputs)")
+    ap.add_argument("--cpu-sample-nals", type=int, default=1_000_000, help="with --full: 0 disables the CPU baseline leg")
+    ap.add_argument("--other-kernels", type=int, default=1, help="with --full: 0 skips the emit / parse / write measurements (N = 1 only)")
+    ap.add_argument("--sweep", type=int, default=1, help="with --full: 0 skips other_kernels' NAL-size sweep (profiling passes)")
     ap.add_argument("--placed-arena", type=int, default=0,
                     help="1: the RBSP arena (and the other lines' outputs) from hbs_pair_alloc, placed against their inputs by measurement, instead of torch's "
                          "allocator.  Off by default since round 6: over six processes the median gain was 1.3 %% of the kernel's time (profiles/r06/pair_time.txt); "
-                         "the default run still reports both arenas (roofline.kernel_ms_placed_arena / kernel_ms_plain_arena)")
+                         "a --full run still reports both arenas (roofline.kernel_ms_placed_arena / kernel_ms_plain_arena)")
     ap.add_argument("--exercise-gather", action="store_true",
                     help="dev aid: run the N > 1 code path (RCCL group, pipelined index gather) with a one-rank group on one GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python3 bench.py --gpus N` as typed: this process becomes the launcher.  It has not imported torch and never
@@ -1083,16 +1158,19 @@ def main():
     kms = [ctx.kernel_ms_back(b) for b in range(min(args.steps, 64))]
     gms = gatherer.gather_ms(args.steps) if gatherer is not None else []
     s = ctx.read_summary(summary)
-
-    # parity properties at full size (outside the timed region)
     assert int(s["error"]) == 0 and int(s["nal_count"]) == n and int(s["stop_reason"]) == -1, s
     assert int(s["rbsp_bytes"]) == rb
-    assert torch.equal(rbsp[:rb], gen_rbsp[:rb]), "extracted RBSP != generated RBSP"
-    a = index[: n * 32].view(torch.int64).view(n, 4)
-    b = gen_index[: n * 32].view(torch.int64).view(n, 4)
-    assert torch.equal(a[:, :3], b[:, :3]), "NAL index != generator's index"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, indexes[(counter[0] - 1) % len(indexes)], rbsp, s, n, rb)
 
-    if multi:
+    if args.full:
+        # parity properties at full size (outside the timed region)
+        assert torch.equal(rbsp[:rb], gen_rbsp[:rb]), "extracted RBSP != generated RBSP"
+        a = index[: n * 32].view(torch.int64).view(n, 4)
+        b = gen_index[: n * 32].view(torch.int64).view(n, 4)
+        assert torch.equal(a[:, :3], b[:, :3]), "NAL index != generator's index"
+
+    if multi and args.full:
         # what the exchange delivered in the last step: every rank's rows back to back in rank order; MY rows must be my index
         # (the others are checked by their owners, and all ranks hold the same bytes)
         last_k = (counter[0] - 1) % len(indexes)
@@ -1182,7 +1260,7 @@ def main():
         if tr is not None:
             out["roofline"]["traffic"] = tr["traffic_bytes_per_launch"]
             out["roofline"]["traffic_source"] = tr["source"]
-        if world == 1 and args.other_kernels:
+        if world == 1 and args.full and args.other_kernels:
             # what placement buys, in THIS process: the same steps into the other kind of arena (outside the timed region) -- torch's
             # allocator when the timed steps' arena was placed, hbs_pair_alloc against the stream otherwise
             t_b = time.perf_counter()
@@ -1207,9 +1285,9 @@ def main():
                                             "placed_allocation": other_report if not PLACED else placement,
                                             "note": "same process, same stream: an arena from torch's allocator against one from hbs_pair_alloc (placed against the "
                                                     "stream by measurement); median of five calls each"}
-        if world == 1 and args.cpu_sample_nals > 0:            # rank 0 at N = 1 only
+        if world == 1 and args.full and args.cpu_sample_nals > 0:            # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(stream, index, rbsp, n, min(args.cpu_sample_nals, n))
-        if world == 1 and args.other_kernels:
+        if world == 1 and args.full and args.other_kernels:
             g["uniform_kernel_ms"] = k_ms
             del rbsp, index
             ok = other_kernels(torch, hbs, ctx, g, n, sweep=bool(args.sweep), cpu_parse=args.cpu_sample_nals > 0)

@@ -6,8 +6,8 @@ O=gpurun_out/r02; mkdir -p $O
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch0 -- python3 bench.py --steps 2 --warmup 1 --cpu-sample-nals 0 --other-kernels 0 > $O/pmc_fetch0_line.json 2> $O/pmc_fetch0.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write0 -- python3 bench.py --steps 2 --warmup 1 --cpu-sample-nals 0 --other-kernels 0 > $O/pmc_write0_line.json 2> $O/pmc_write0.err
 # the other kernels: bench.py's other_kernels leg (index-only kernel x4 and K3 x5 on the 16 GiB stream / arena; its config-3 leg runs K3 once on 2 GiB: dropped by near_max)
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 bench.py --steps 2 --warmup 1 --cpu-sample-nals 0 > $O/pmc_fetch_line.json 2> $O/pmc_fetch.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 bench.py --steps 2 --warmup 1 --cpu-sample-nals 0 > $O/pmc_write_line.json 2> $O/pmc_write.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 bench.py --full --steps 2 --warmup 1 --cpu-sample-nals 0 > $O/pmc_fetch_line.json 2> $O/pmc_fetch.err
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 bench.py --full --steps 2 --warmup 1 --cpu-sample-nals 0 > $O/pmc_write_line.json 2> $O/pmc_write.err
 python3 scripts/pmc_traffic.py $O/pmc_fetch0 $O/pmc_write0 k_scan_extract4 34403064115 $O/traffic_k_scan_extract4.json | tail -12
 python3 scripts/pmc_traffic.py $O/pmc_fetch $O/pmc_write k_scan_index5 17231091218 $O/traffic_k_scan_index5.json | tail -12
 python3 scripts/pmc_traffic.py $O/pmc_fetch $O/pmc_write k3_tiles 34403064115 $O/traffic_k3_tiles.json near_max | tail -12

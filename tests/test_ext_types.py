@@ -3,7 +3,8 @@
     reference's never-dispatched readers produced (tests/golden/ext_vectors.json, made by make_golden_ext.py);
   - the product's byte-level reader (hbs_parse_ext.h, single-stepped on the CPU) against the oracle on the same NALs
     and on random ones;
-  - `-m ref`: the oracle against the reference driver itself on random NALs (dev container only);
+  - the oracle against the reference driver itself on random NALs (live in the dev container, elsewhere through the
+    driver's answers recorded on the same NALs, tests/golden/fuzz_answers.json.gz);
   - `-m gpu`: hbs_parse_extended through the C ABI, a stream of mixed NALs, against the oracle per NAL."""
 import ctypes as C
 import json
@@ -88,21 +89,46 @@ def test_product_reader_single_stepped_against_the_oracle(orc):
             assert as_tuple(got_rc, got) == as_tuple(rc, rec), nal.hex()
 
 
-@pytest.mark.ref
-def test_oracle_against_the_reference_driver_fuzz(orc):
+def ext_fuzz_inputs():
+    return random_nals(11, 6000)
+
+
+def reference_ext_driver():
+    """oracle/_ref/libref_ext_driver.so (the reference's never-dispatched readers), or None where it is not built"""
     drv = os.path.join(ROOT, "oracle", "_ref", "libref_ext_driver.so")
     if not os.path.exists(drv):
-        pytest.skip("reference build not present")
+        return None
     lib = C.CDLL(drv)
     lib.ref_read_extended_nal.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-    for nal in random_nals(11, 6000):
-        out = np.zeros(1, dtype=EXT)
-        t = C.c_int(0)
-        rc = lib.ref_read_extended_nal(bytes(nal), len(nal), out.ctypes.data, C.byref(t))
-        orc_rc, orc_t, rec = oracle_ext(orc, nal)
-        assert (rc, t.value) == (orc_rc, orc_t), nal.hex()
-        if t.value >= 0 and rc != -2:
-            assert as_tuple(rc, out[0]) == as_tuple(orc_rc, rec), nal.hex()
+    return lib
+
+
+def reference_ext_answer(lib, nal):
+    out = np.zeros(1, dtype=EXT)
+    t = C.c_int(0)
+    rc = lib.ref_read_extended_nal(bytes(nal), len(nal), out.ctypes.data, C.byref(t))
+    return rc, t.value, (as_tuple(rc, out[0]) if t.value >= 0 and rc != -2 else None)
+
+
+def oracle_ext_answer(orc, nal):
+    rc, t, rec = oracle_ext(orc, nal)
+    return rc, t, (as_tuple(rc, rec) if t >= 0 and rc != -2 else None)
+
+
+def test_oracle_against_the_reference_driver_fuzz(orc):
+    """the oracle against the reference driver on random NALs: live where oracle/_ref is built, else against the driver's
+    answers recorded on the same NALs (golden/fuzz_answers.json.gz, make_golden_fuzz.py)"""
+    from tests.golden.make_golden_fuzz import digest, load
+    lib = reference_ext_driver()
+    nals = ext_fuzz_inputs()
+    want = load("ext_fuzz") if lib is None else None
+    assert len(nals) == 6000 and (want is None or len(want) == 6000)
+    for k, nal in enumerate(nals):
+        got = oracle_ext_answer(orc, nal)
+        if lib is not None:
+            assert got == reference_ext_answer(lib, nal), nal.hex()
+        else:
+            assert digest(got) == want[k], nal.hex()
 
 
 @pytest.mark.gpu

@@ -177,7 +177,8 @@ def test_bench_with_two_ranks_on_one_gpu(tmp_path, how, world):
     try:
         hooks = dict(HBS_RCCL_LIB=fake, HBS_FAKE_RCCL_SHM="/" + shm.name.lstrip("/"), HBS_FAKE_RCCL_SLOT=str(slot),
                      HBS_BENCH_ONE_DEVICE="0", HBS_BENCH_DIST_BACKEND="gloo")
-        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1", "--nals", str(nals)]
+        # --full: the parity checks of every rank's outputs and of the gathered rows run too
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1", "--nals", str(nals), "--full"]
         if how == "launcher":
             # the driver's command as typed: no RANK / WORLD_SIZE in the environment, bench.py starts its ranks itself
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}

@@ -1,11 +1,15 @@
 """Pin the oracle's byte layer: against golden vectors generated from the real
-reference (tests/golden/l2_vectors.json, made by make_golden_l2.py) and, when
-oracle/_ref is present (dev container), against the reference itself on fuzz."""
+reference (tests/golden/l2_vectors.json, made by make_golden_l2.py) and against
+the reference itself on fuzz -- live when oracle/_ref is present (dev container),
+else through its answers recorded on the same inputs (make_golden_fuzz.py)."""
 import json
 import os
 
 import numpy as np
 import pytest
+
+from tests import _orc
+from tests.golden.make_golden_fuzz import digest as answer_digest, load as load_answers
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "l2_vectors.json")))
@@ -44,37 +48,69 @@ def test_ten_nal_index_golden(orc):
 ALPHA = np.array([0, 0, 0, 0, 1, 1, 2, 3, 3, 4, 0x40, 0x80, 0xFF], dtype=np.uint8)
 
 
-@pytest.mark.ref
-def test_fuzz_vs_reference(orc, ref):
+def l2_fuzz_inputs():
     rng = np.random.RandomState(7)
     for _ in range(4000):
-        b = bytes(ALPHA[rng.randint(0, len(ALPHA), size=rng.randint(3, 64))])
-        assert orc.find_nal_unit(b) == ref.find_nal_unit(b), b.hex()
-        a, r = orc.nal_to_rbsp(b), ref.nal_to_rbsp(b)
-        assert a == r, b.hex()
-        assert orc.rbsp_to_nal(b) == ref.rbsp_to_nal(b), b.hex()
+        yield bytes(ALPHA[rng.randint(0, len(ALPHA), size=rng.randint(3, 64))])
 
 
-@pytest.mark.ref
-def test_stream_loop_vs_reference(orc, ref):
-    """orc_index_stream == the hevc_analyze.c:135-205 loop driven on the reference."""
+def l2_answer(lib, b):
+    return lib.find_nal_unit(b), lib.nal_to_rbsp(b), lib.rbsp_to_nal(b)
+
+
+def test_fuzz_vs_reference(orc):
+    """the oracle's three byte functions against the reference's: live where oracle/_ref is built, else against the
+    reference's answers recorded on the same inputs (golden/fuzz_answers.json.gz, make_golden_fuzz.py)"""
+    ref = _orc.reference()
+    want = load_answers("l2_fuzz") if ref is None else None
+    k = -1
+    for k, b in enumerate(l2_fuzz_inputs()):
+        got = l2_answer(orc, b)
+        if ref is not None:
+            assert got == l2_answer(ref, b), b.hex()
+        else:
+            assert answer_digest(got) == want[k], b.hex()
+    assert k + 1 == 4000 and (want is None or len(want) == 4000)
+
+
+def stream_loop_inputs():
     rng = np.random.RandomState(11)
     for _ in range(300):
         n = rng.randint(4, 400)
         s = ALPHA[rng.randint(0, len(ALPHA), size=n)].copy()
         s[rng.rand(n) < 0.5] = 0x55          # thin out so NALs have some length
-        data = bytes(s)
-        want, p = [], 0
-        while True:
-            r, st, en = ref.find_nal_unit(data[p:])
-            if r <= 0:
-                if r == -1:
-                    want.append((p + st, p + en))
-                break
-            want.append((p + st, p + en))
-            p += en
+        yield s
+
+
+def reference_stream_loop(ref, s):
+    """the hevc_analyze.c:135-205 loop driven on the reference: [(start, end)] of every NAL"""
+    data = bytes(s)
+    want, p = [], 0
+    while True:
+        r, st, en = ref.find_nal_unit(data[p:])
+        if r <= 0:
+            if r == -1:
+                want.append((p + st, p + en))
+            break
+        want.append((p + st, p + en))
+        p += en
+    return want
+
+
+def test_stream_loop_vs_reference(orc):
+    """orc_index_stream == the hevc_analyze.c:135-205 loop driven on the reference (live where oracle/_ref is built, else
+    the loop's answers recorded on the same streams)."""
+    ref = _orc.reference()
+    want = load_answers("stream_loop") if ref is None else None
+    k = -1
+    for k, s in enumerate(stream_loop_inputs()):
         idx, why = orc.index_stream(s)
-        assert [(int(a), int(b)) for a, b in zip(idx["start"], idx["end"])] == want, data.hex()
+        got = [(int(a), int(b)) for a, b in zip(idx["start"], idx["end"])]
+        if ref is not None:
+            assert got == reference_stream_loop(ref, s), bytes(s).hex()
+        else:
+            assert answer_digest(got) == want[k], bytes(s).hex()
+    assert k + 1 == 300 and (want is None or len(want) == 300)
 
 
 @pytest.mark.ref
