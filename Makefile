@@ -61,8 +61,8 @@ diag: $(DIAG_OBJS) $(LEGACY_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(EXPORTS) -o build/diag/libhbs_diag.so $(DIAG_OBJS) $(LEGACY_OBJ)
 
 # development variant of the library with extra -D flags, for A/B timing (HBS_LIB=build/variants/<NAME>/libhbs.so)
-#   make variant NAME=ntload DEFS="-DHBS_NT_LOAD=1"
-#   make variant NAME=d4 DEFS="-DHBS4_COPY_DEPTH=4" ONLY="hbs_scan4"      (recompile only the named files; the rest from build/obj)
+#   make variant NAME=pt DEFS="-DHBS_PHASE_TIMING"
+#   make variant NAME=dz DEFS="-DHBS_DZ_TIMING" ONLY="hbs_emit"      (recompile only the named files; the rest from build/obj)
 ONLY ?= $(patsubst $(CSRC)/%.hip,%,$(HIP_SRCS))
 VAR_OBJS := $(patsubst %,build/variants/$(NAME)/%.o,$(ONLY))
 VAR_REST := $(filter-out $(patsubst %,build/obj/%.o,$(ONLY)),$(HIP_OBJS))

@@ -213,12 +213,14 @@ class Context:
         self._check(self.lib.hbs_ctx_set_emit_path(self.h, path), "hbs_ctx_set_emit_path")
 
     def set_kernel(self, variant):
-        """0 = automatic (density probe picks 4 or 2 on the device; the default), 2 = LDS-image
-        scan/extract kernel, 4 = event-sparse one, 5 = index-only streaming one"""
+        """0 = automatic (a density probe picks 4, 6, 2 or 5 on the device; the default), 2 = LDS-image
+        scan/extract kernel, 4 = event-sparse one, 5 = index-only streaming one (with an arena it means 4),
+        6 = event-sparse one with 24 rows a wavefront"""
         self._check(self.lib.hbs_ctx_set_kernel(self.h, variant), "hbs_ctx_set_kernel")
 
     def set_count_ahead(self, mode=1):
-        """kernel 4's dense tiles counted ahead of it: 0 never, 1 on streams of 3 GiB and more (default), 2 always"""
+        """dense tiles counted ahead of kernel 4 and of emit_annexb's arena-tile kernel: 0 never, 1 on streams / arenas
+        of 3 GiB and more (default), 2 always"""
         self.lib.hbs_ctx_set_count_ahead.argtypes = [C.c_void_p, C.c_int]     # (bound here: development libraries of earlier rounds load too)
         self._check(self.lib.hbs_ctx_set_count_ahead(self.h, mode), "hbs_ctx_set_count_ahead")
 

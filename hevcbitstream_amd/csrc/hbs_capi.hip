@@ -17,15 +17,11 @@
 #include "hbs_parse.h"
 #include "hbs_parse_compact.h"
 
-#ifndef HBS_DEFAULT_KERNEL
-#define HBS_DEFAULT_KERNEL 0
-#define HBS_DEFAULT_SCHED 1
-#endif
-
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
 struct hbs_ctx {
     int device;
+    int cus;                            /* compute units of `device` */
     hipStream_t own_stream;
     hipStream_t stream;
     int grid_blocks;
@@ -51,7 +47,6 @@ struct hbs_ctx {
                                          workspace, which the next call of any kind overwrites or reallocates); null: no verdict (small path) */
     uint32_t* emit_verdict;           /* 16 bytes of device memory owned by the context */
     uint32_t emit_calls;              /* hbs_emit_annexb calls so far: stamps the dense tiles counted ahead (never 0) */
-    int sched;
     unsigned long long* desc;
     uint64_t desc_tiles;
     hbs::RunHeader* hdr;
@@ -127,6 +122,7 @@ int hbs_ctx_create(hbs_ctx** out, int device)
     if (!c) return HBS_E_HIP;
     memset(c, 0, sizeof(*c));
     c->device = device;
+    c->cus = prop.multiProcessorCount;
     hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; return HBS_E_HIP; }
     c->stream = c->own_stream;
@@ -149,9 +145,7 @@ int hbs_ctx_create(hbs_ctx** out, int device)
     const char* ca = getenv("HBS_COUNT_AHEAD");
     c->count_ahead = (ca && ca[0] >= '0' && ca[0] <= '2') ? ca[0] - '0' : 1;
     const char* kv = getenv("HBS_KERNEL");              /* 0 automatic, 2 LDS-image, 4 event-sparse, 5 index-only streaming, 6 event-sparse with 24 rows */
-    const char* sv = getenv("HBS_SCHED");
-    c->sched = (sv && atoi(sv) >= 0 && atoi(sv) <= 2) ? atoi(sv) : HBS_DEFAULT_SCHED;
-    c->variant = (kv && (atoi(kv) == 0 || atoi(kv) == 2 || atoi(kv) == 4 || atoi(kv) == 5 || atoi(kv) == 6)) ? atoi(kv) : HBS_DEFAULT_KERNEL;
+    c->variant = (kv && (atoi(kv) == 0 || atoi(kv) == 2 || atoi(kv) == 4 || atoi(kv) == 5 || atoi(kv) == 6)) ? atoi(kv) : 0;
     c->last_variant = c->variant ? c->variant : 4;
     *out = c;
     return 0;
@@ -429,7 +423,7 @@ int hbs_index_extract(hbs_ctx* c, const uint8_t* d_stream, uint64_t n,
     }
     c->last_index_only = (hbs::scan_uses_index_only(n, c->variant, d_rbsp) && !hbs::scan_takes_small_path(n, index_cap, c->variant)) ? 1 : 0;
     a.variant = c->variant;
-    a.sched = c->sched;
+    a.cus = c->cus;
     a.grid_blocks = c->grid_blocks; a.grid_blocks4 = c->grid_blocks4; a.grid_blocks4r24 = c->grid_blocks6; a.spare_wgs = c->spare_wgs; a.first_static = c->exclusive;
     c->probe_pending = (c->variant == 0 && n) ? 1 : 0;
     if (hbs::scan_takes_small_path(n, index_cap, c->variant)) { c->probe_pending = 0; c->last_variant = 2; }
@@ -463,12 +457,8 @@ int hbs_emit_annexb(hbs_ctx* c, const uint8_t* d_rbsp, uint64_t rbsp_bytes,
     if (c->emit_blocks <= 0) {
         c->emit_blocks = hbs::emit_grid_blocks(c->device);
         if (c->emit_blocks <= 0) return fail(c, hipErrorUnknown, "occupancy query of the emit kernel");
-        const char* eb = getenv("HBS_EMIT_BLOCKS");         /* debugging aid */
-        if (eb && atoi(eb) > 0 && atoi(eb) < c->emit_blocks) c->emit_blocks = atoi(eb);
         const char* tp = getenv("HBS_EMIT_TWO_PASS");        /* 1 / 0 pin a way; default: picked on the device */
         if (!c->emit_path_set) { c->emit_two_pass = !tp ? -1 : (atoi(tp) == 1 ? 1 : 0); c->emit_tiles = !tp ? 1 : 0; }
-        const char* et = getenv("HBS_EMIT_TILES");          /* 0 / 1 / 2: never / when eligible / pinned */
-        if (!c->emit_path_set && et && atoi(et) >= 0 && atoi(et) <= 2) c->emit_tiles = atoi(et);
         c->emit_tile_blocks = hbs::emit_tile_grid_blocks(c->device);
         if (c->emit_tile_blocks <= 0) return fail(c, hipErrorUnknown, "occupancy query of the arena-tile emit kernel");
     }
@@ -502,7 +492,7 @@ int hbs_emit_annexb(hbs_ctx* c, const uint8_t* d_rbsp, uint64_t rbsp_bytes,
     a.first_static = c->exclusive;
     a.tiles = c->emit_tiles; a.tile_blocks = c->emit_tile_blocks;
     a.clear_bytes = b_desc + 1024;                          /* look-back words and the counters behind them */
-    a.grid_blocks = c->emit_blocks; a.two_pass = c->emit_two_pass;
+    a.grid_blocks = c->emit_blocks; a.two_pass = c->emit_two_pass; a.cus = c->cus;
     if (!c->emit_verdict) {
         const hipError_t ea = hipMalloc(reinterpret_cast<void**>(&c->emit_verdict), 16);
         if (ea != hipSuccess) return fail(c, ea, "hipMalloc(emit verdict)");

@@ -101,10 +101,7 @@ HBS_HD unsigned long long ahead_stamp_of(unsigned long long call) { return (call
  * kernel handles flagged chunks 64 at a time on one wavefront, so once more than one chunk in
  * kDenseOneIn may hold a zero pair the LDS-image kernel, whose cost does not depend on the data,
  * is the faster of the two. */
-#ifndef HBS_DENSE_ONE_IN
-#define HBS_DENSE_ONE_IN 44
-#endif
-constexpr uint32_t kDenseOneIn = HBS_DENSE_ONE_IN;    /* Round 3: the probe counts ELEMENTS (chunks a pattern 00 00 {<=3} ends in, neighbours seen).  Round 6: beyond one
+constexpr uint32_t kDenseOneIn = 44;                  /* Round 3: the probe counts ELEMENTS (chunks a pattern 00 00 {<=3} ends in, neighbours seen).  Round 6: beyond one
                                            element in 44 chunks the event-sparse kernel's 24-row geometry takes over from the 48-row one (2 GiB sweep, profiles/r06:
                                            NALs of 1 KiB -- one in 53 -- 0.58 of peak on 48 rows against 0.55 on 24; 768 bytes -- one in 40 -- 0.535 / 0.530;
                                            512 bytes 0.485 / 0.516; the zero-heavy stress stream -- one in 41 -- 0.524 / 0.561), where until round 5 the 48-row

@@ -24,14 +24,6 @@
 #include "hbs_emit.h"
 #include "hbs_emit_launch.h"
 
-#ifndef HBS_K3F_COPY_DEPTH
-#define HBS_K3F_COPY_DEPTH -1     /* k3_fused: stores / loads of a wavefront in flight (-1: no limit).  Round 3 tried 3 / 8 and 3 / 4,
-                                     the recipe that took k3_tiles from 6.9 to 6.1 ms: nothing here (8.7-8.9 ms either way, scripts/experiments/k3f_ab.sh) */
-#endif
-#ifndef HBS_K3F_LOAD_DEPTH
-#define HBS_K3F_LOAD_DEPTH -1
-#endif
-
 namespace hbs {
 
 /* Which of the two ways?  The single-pass kernel (k3_fused) sends every row that holds a flagged chunk through
@@ -708,39 +700,22 @@ extern "C" int hbs_debug_phase_cycles_emit(unsigned long long* host_out /* [1024
 #define HBS3_T_FLUSH
 #endif
 
-#ifndef HBS_EMIT_SLOTS
-#define HBS_EMIT_SLOTS 3
-#define HBS_EMIT_ROWS 12
-#endif
-#ifndef HBS_EMIT_WGS
-#define HBS_EMIT_WGS 2                            /* workgroups per CU the register budget is set for */
-#endif
-constexpr int kEmitSlots = HBS_EMIT_SLOTS;        /* NALs a wavefront works on at a time */
-constexpr int kEmitRows = HBS_EMIT_ROWS;          /* rows of 1 KiB per slot held in registers */
+constexpr int kEmitWgs = 2;                       /* workgroups per CU the register budget is set for */
+constexpr int kEmitSlots = 3;                     /* NALs a wavefront works on at a time */
+constexpr int kEmitRows = 12;                     /* rows of 1 KiB per slot held in registers */
 constexpr int kEmitGroup = 4 * kEmitSlots;        /* NALs per workgroup and ticket */
 constexpr uint32_t kEmitSpinLimit = 1u << 26;
 
 struct __attribute__((packed, aligned(1))) Chunk16 { u32x4 v; };
 /* streaming accesses of the single pass: the arena is read once and the stream written once (hbs_wave.h has the measurements) */
-#ifndef HBS_K3_NT
-#define HBS_K3_NT 1
-#endif
 typedef const __attribute__((address_space(1))) u32x4_u1* global_u32x4_u1_ptr;
 __device__ __forceinline__ u32x4 k3_load16(const uint8_t* p)
 {
-#if HBS_K3_NT
     return __builtin_nontemporal_load((global_u32x4_u1_ptr)(uintptr_t)p);
-#else
-    return reinterpret_cast<const Chunk16*>(p)->v;
-#endif
 }
 __device__ __forceinline__ void k3_store16(uint8_t* p, u32x4 v)
 {
-#if HBS_K3_NT
     __builtin_nontemporal_store(v, reinterpret_cast<u32x4_u1*>(p));
-#else
-    reinterpret_cast<Chunk16*>(p)->v = v;
-#endif
 }
 
 /* rows [r0, r0 + kEmitRows) of a NAL.  Unpredicated loads: a lane whose chunk starts behind the
@@ -764,9 +739,6 @@ __device__ __forceinline__ void load_rows(u32x4 (&R)[kEmitRows], const uint8_t* 
                  * and phases (they are all the same expression) they would fill the register file */
                 const uint32_t off = 1024u * (r0 + (uint32_t)r) + 16u * (uint32_t)launder_lane(lane);
                 R[r] = k3_load16(base + (off < lim ? off : lim));
-#if HBS_K3F_LOAD_DEPTH >= 0
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(HBS_K3F_LOAD_DEPTH) : "memory");
-#endif
             }
         }
     }
@@ -797,10 +769,7 @@ __device__ __forceinline__ void flag_batch(const u32x4 (&R)[kEmitRows], uint32_t
             myflags |= (mine ? 1u : 0u) << r;
             e_prev = (uint32_t)__builtin_amdgcn_readlane((int)R[r].w, 63);
         }
-#ifndef HBS_K3_FLAG_INTERLEAVE
-#define HBS_K3_FLAG_INTERLEAVE 1
-#endif
-        if ((r % HBS_K3_FLAG_INTERLEAVE) == HBS_K3_FLAG_INTERLEAVE - 1) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -869,11 +838,6 @@ __device__ __forceinline__ void emit_batch(const u32x4 (&R)[kEmitRows], const ui
                 if (off == last_off) store_bytes(dst, R[r], len - last_off);
             }
         }
-#if HBS_K3F_COPY_DEPTH >= 0
-        /* at most that many stores of a wavefront in flight: a short memory queue on the CU keeps the other workgroups'
-         * look-back polls quick (hbs_scan4.hip, round 3) */
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(HBS_K3F_COPY_DEPTH) : "memory");
-#endif
         __builtin_amdgcn_sched_barrier(0);                     /* one row at a time: interleaving rows only costs registers */
     }
 }
@@ -1019,7 +983,7 @@ struct Lds3 {
     uint32_t ticket;
 };
 
-__global__ __launch_bounds__(256, HBS_EMIT_WGS)
+__global__ __launch_bounds__(256, kEmitWgs)
 void k3_fused(const uint8_t* __restrict__ rbsp, uint64_t arena, const hbs_nal_entry* __restrict__ idx, uint64_t n, int gap_mode,
               const unsigned long long* __restrict__ items, const unsigned long long* __restrict__ n_items_ptr, uint64_t items_cap,
               unsigned long long* __restrict__ desc, uint32_t* __restrict__ ticket,
@@ -2014,9 +1978,7 @@ void k3_dense_tile(LdsT& l, TileCtx t, uint64_t tile, bool last_tile, unsigned l
 #endif
 }
 
-#ifndef HBS3T_COPY_DEPTH
-#define HBS3T_COPY_DEPTH 3      /* stores of a wavefront in flight during k3_tiles' copy */
-#endif
+constexpr int kTCopyDepth = 3;           /* stores of a wavefront in flight during k3_tiles' copy */
 template <class F, int... Is>
 __device__ __forceinline__ void t_rows_apply(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
 template <int N, class F>
@@ -2436,8 +2398,8 @@ void k3_tiles(const uint8_t* __restrict__ rbsp, const hbs_nal_entry* __restrict_
                     const uint32_t k = rowpre + lanes_below(f);
                     if (!((f >> lane) & 1ull) && cc < whole) arena_store16(tout + l.seg[k] + 16u * cc, q[r]);
                 }
-                /* at most HBS3T_COPY_DEPTH stores of a wavefront in flight: see the fetch */
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(HBS3T_COPY_DEPTH) : "memory");
+                /* at most kTCopyDepth stores of a wavefront in flight: see the fetch */
+                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kTCopyDepth) : "memory");
             });
         }
         HBS3_T_MARK(6)
@@ -2508,16 +2470,11 @@ hipError_t launch_emit_annexb(const EmitArgs& a, hipStream_t st)
         /* an index that is one stretch of the arena: 64 consecutive NALs a wavefront, cooperatively (hbs_emit_groups.h: sizes,
          * the scan of the wavefronts' sums, the bytes); the lane per NAL behind it is what other indexes get */
         {
-            uint32_t gcap = groups_region_cap(a.rbsp_bytes / a.n), npw = groups_nals_per_wave(a.rbsp_bytes / a.n);
-            if (const char* e = getenv("HBS_K3G_NPW")) {                 /* tuning aid: NALs a wavefront takes (16, 32 or 64) */
-                const int v = atoi(e);
-                if (v == 16 || v == 32 || v == 64) { npw = (uint32_t)v; gcap = groups_region_cap_for(npw, a.rbsp_bytes / a.n); }
-            }
+            const uint32_t gcap = groups_region_cap(a.rbsp_bytes / a.n), npw = groups_nals_per_wave(a.rbsp_bytes / a.n);
             const uint64_t nw = (a.n + npw - 1u) / npw, wgs = (nw + kGWaves - 1) / kGWaves;
-            static const int cus = [] { int d = 0, c = 256; if (hipGetDevice(&d) == hipSuccess) (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d); return c; }();
             const size_t per_cu_lds = (size_t)160 * 1024 / (groups_lds_bytes(gcap) + 64);
-            const uint64_t gmax_emit = (uint64_t)cus * (uint64_t)(per_cu_lds > 16 ? 16 : per_cu_lds < 1 ? 1 : per_cu_lds);
-            const uint64_t gmax_sizes = (uint64_t)cus * 16u;
+            const uint64_t gmax_emit = (uint64_t)a.cus * (uint64_t)(per_cu_lds > 16 ? 16 : per_cu_lds < 1 ? 1 : per_cu_lds);
+            const uint64_t gmax_sizes = (uint64_t)a.cus * 16u;
             k3g_sizes<<<dim3((unsigned)(wgs < gmax_sizes ? wgs : gmax_sizes)), dim3(64 * kGWaves), 0, st>>>(
                 a.rbsp, a.rbsp_bytes, a.index_in, a.n, a.gap_mode, a.nal_total, a.tflag, a.err, gcap, npw, try_tiles ? 0 : 1);
             launch_scan_u64(a.nal_total, a.out_off, nw, a.total_dense, a.scan_tmp, st, nullptr, kWhenGroups, a.tflag);

@@ -336,10 +336,7 @@ __device__ __forceinline__ void parse_lane_sink(int type, const hbs_nal_entry& e
  * pass 0: parameter sets (workgroups [0, parse_blocks)) while the workgroups behind them clear the
  * slice slots; pass 1: slices against them.  kMode: plain parse, or parse + per-field trace (the
  * debug reader's variant of the syntax, see hbs_parse.h). */
-#ifndef HBS_PARSE_LANES
-#define HBS_PARSE_LANES 64
-#endif
-constexpr int kParseLanes = HBS_PARSE_LANES;          /* NALs a wavefront walks at once (lanes 0 .. kParseLanes-1) */
+constexpr int kParseLanes = 64;                       /* NALs a wavefront walks at once (lanes 0 .. kParseLanes-1) */
 constexpr unsigned kZeroBlocks = 1024;                /* spare workgroups of the parameter-set launch that clear slice slots */
 /* kSink (pass 1 of a compact parse): the slices WITHOUT a slot, into sinks; otherwise: the NALs with one, as always -- and, in a
  * compact parse, the record of a slice that has a slot (hbs_parse_materialize) taken from its struct */
@@ -717,9 +714,6 @@ void k4_fix_list(FixCtx c, uint32_t* __restrict__ list, uint32_t* __restrict__ f
         if (fix_is_affected(c, k)) list[atomicAdd(&fix_count[0], 1u)] = (uint32_t)k;
 }
 
-#ifndef HBS_FIX_ENABLED
-#define HBS_FIX_ENABLED 1
-#endif
 constexpr unsigned kFixBlocks = 128;             /* x 64 lanes: slices walked again at the same time */
 template <int kMode>
 __global__ __launch_bounds__(64)
@@ -735,15 +729,11 @@ void k4_fix(FixCtx c, const uint32_t* __restrict__ list, uint32_t* __restrict__ 
     for (uint32_t q = me; q < count; q += gridDim.x * 64u) {
         const uint64_t k = list[q];
         uint32_t tr_n = 0;
-#if HBS_FIX_ENABLED
         const bool ok = fix_slice<kMode>(c, k, my, trace ? trace + k * (uint64_t)trace_cap : nullptr, trace_cap, &tr_n, my_struct);
         if (ok && compact) {                                     /* the record again, from the struct the exact walk filled (its slot, or this lane's own) */
             const uint64_t so = c.parsed[k].struct_off;
             compact[k] = compact_of(*reinterpret_cast<const hevc_slice_header_t*>(so != ~0ull ? c.structs + so : my_struct));
         }
-#else
-        const bool ok = false; (void)my;
-#endif
         if (!ok) atomicOr(&fix_count[1], 1u);                    /* a chain of slices deeper than kFixDepth: the whole batch in order (k4_seq) */
         else if (trace_count) trace_count[k] = tr_n;
     }

@@ -248,7 +248,7 @@ static int alloc_chunked(hbs_ctx* ctx, const void* d_peer, uint64_t peer_bytes, 
     /* layout: whole chunks of 1 GiB, the size rounded up (a remainder mapped as a chunk of its own size made hipMemSetAccess
      * fail with "invalid argument" on this stack, so every mapping is one GiB: up to a GiB more than asked for is held) */
     const uint64_t total = up(bytes, kGran);
-    const bool want_probe = d_peer != nullptr && peer_bytes >= kChunk / 2 && total >= kChunk && !getenv("HBS_PAIR_NO_PROBE");
+    const bool want_probe = d_peer != nullptr && peer_bytes >= kChunk / 2 && total >= kChunk;
     if (!want_probe) return HBS_E_CAPACITY;                           /* nothing to place: the plain way */
     if ((reinterpret_cast<uintptr_t>(d_peer) & 15u) != 0) return HBS_E_ARG;     /* the probe loads 16 bytes a lane */
     const uint64_t nfull = (total + kChunk - 1) / kChunk;
@@ -319,9 +319,9 @@ static int alloc_chunked(hbs_ctx* ctx, const void* d_peer, uint64_t peer_bytes, 
     r.from_pool = (uint32_t)(from_pool0 + from_pool1);
     /* Round 6: a bounded search by default -- 24 candidates past the chunks and 32 GiB of ballast (88 and 128 GiB until then: the
      * first allocation of a process took 3.4-5.7 s on boxes that hand out long runs of one class, for a median gain of 1.3 % of K12's
-     * time over six processes, profiles/r06/pair_time.txt).  HBS_PAIR_EXTRA_CANDS / HBS_PAIR_BALLAST_GIB widen it again. */
-    static const int kExtraCands = [] { const char* e = getenv("HBS_PAIR_EXTRA_CANDS"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 512 ? v : 24; }();
-    static const uint64_t kBallastMax = [] { const char* e = getenv("HBS_PAIR_BALLAST_GIB"); const int v = e ? atoi(e) : -1; return (uint64_t)(v >= 0 && v <= 256 ? v : 32) << 30; }();
+     * time over six processes, profiles/r06/pair_time.txt). */
+    constexpr int kExtraCands = 24;
+    constexpr uint64_t kBallastMax = 32ull << 30;
     constexpr uint64_t kKeepFree = 24ull << 30;
     auto room_for = [&](uint64_t more) -> bool {
         size_t fr = 0, tot = 0;
@@ -446,7 +446,7 @@ static int alloc_plain(hbs_ctx* ctx, const void* d_peer, uint64_t peer_bytes, ui
     constexpr int kTries = 6;
     const uint64_t half = (kChunk / 2) / kTile * kTile;
     const uint64_t nfull = bytes / kChunk;
-    const bool want_probe = d_peer != nullptr && peer_bytes >= half && nfull >= 1 && !getenv("HBS_PAIR_NO_PROBE");
+    const bool want_probe = d_peer != nullptr && peer_bytes >= half && nfull >= 1;
     const bool dbg = getenv("HBS_PAIR_DEBUG") != nullptr;
     Prober* pr = want_probe ? new (std::nothrow) Prober(st, device) : nullptr;
     if (pr && !pr->ok) { delete pr; pr = nullptr; }
@@ -528,7 +528,7 @@ extern "C" {
 int hbs_pair_alloc(hbs_ctx* ctx, const void* d_peer, uint64_t peer_bytes, uint64_t bytes, void** out, hbs_pair_report* rep)
 {
     if (!ctx || !out) return HBS_E_ARG;
-    const bool probe = d_peer != nullptr && peer_bytes >= kChunk / 2 && bytes >= kChunk && !getenv("HBS_PAIR_NO_PROBE");
+    const bool probe = d_peer != nullptr && peer_bytes >= kChunk / 2 && bytes >= kChunk;
     if (probe && !getenv("HBS_PAIR_PLAIN")) {
         const int rc = alloc_chunked(ctx, d_peer, peer_bytes, bytes, out, rep);
         (void)hipGetLastError();                       /* a HIP call that failed on the way (memory ran out under the candidates) is not the caller's error */

@@ -24,14 +24,13 @@ struct ScanArgs {
     uint32_t* ahead_list;         /* workspace: the tiles so marked, a word per tile of the stream at most                                */
     AheadCtl* ahead_ctl;          /* workspace: the call's number (-> its stamp) and the entries of the list (hbs_common.h)               */
     void* ahead_tab;              /* workspace: scan4_ahead_entry_bytes() per tile: the aggregates of the tiles counted ahead           */
-              /* this call's number on its context (never 0): stamps the entries                                  */
     int grid_blocks;              /* persistent workgroups (<= resident capacity) of the LDS-image kernel */
     int grid_blocks4;                 /* ... of the event-sparse kernel                                        */
     int grid_blocks4r24;              /* ... of its 24-row geometry (hbs_scan4_r24.hip)                        */
     int first_static;                 /* hbs_ctx_set_device_exclusive: persistent kernels take their first tile by workgroup number (else by ticket) */
     int spare_wgs;                    /* hbs_ctx_reserve_workgroups: slots (of 256 threads) every scan kernel leaves free     */
     hipEvent_t ev_begin, ev_end;  /* when non-null: recorded around the main kernel only */
-    int sched;                    /* tile schedule of the LDS-image kernel: 0 striped, 1 ticket at loop top, 2 ticket after prefix */
+    int cus;                      /* compute units of the context's device (the index-only kernel's grid) */
     int variant;                  /* 0: automatic (density probe, then event-sparse or LDS-image kernel, decided on the device),
                                      2: LDS-image kernel (hbs_scan.hip), 4: event-sparse kernel (hbs_scan4.hip),
                                      5: index only (rbsp == nullptr), streaming kernel (hbs_scan5.hip); with an arena it means 4 */

@@ -27,10 +27,6 @@
 #include "hbs_tile.h"
 #include "hbs_scan.h"
 
-#ifndef HBS2_COPY_DEPTH
-#define HBS2_COPY_DEPTH -1
-#endif
-
 namespace hbs {
 
 /* Diagnostic build only (-DHBS_PHASE_TIMING, tests/tools/phase_timing.py): per-phase
@@ -396,8 +392,6 @@ __device__ __forceinline__ void store_holes(const TileView& v, uint8_t* out, uin
     if (cnt & 1u) { *p = (uint8_t)lo; }
 }
 
-enum : int { kSchedStriped = 0, kSchedTicketTop = 1, kSchedTicketAfterPrefix = 2 };
-
 /* next unclaimed tile, the same value in every thread (contains a barrier) */
 __device__ __forceinline__ uint64_t take_ticket(TileLds& l, RunHeader* hdr, int tid)
 {
@@ -406,12 +400,14 @@ __device__ __forceinline__ uint64_t take_ticket(TileLds& l, RunHeader* hdr, int 
     return (uint64_t)l.ticket;
 }
 
-/* the tile loop of the LDS-image kernel; `first` = the workgroup's first tile under the striped schedule */
+/* the tile loop of the LDS-image kernel.  kTicket (the persistent kernel): tiles are handed out in arrival order, a tile's loads
+ * issued as soon as its ticket is taken; otherwise (the one-tile kernel) tile i belongs to workgroup i mod grid */
+template <bool kTicket>
 __device__ __forceinline__
 void scan_tiles(TileLds& l, const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_tiles,
                 hbs_nal_entry* __restrict__ index, uint64_t index_cap,
                 uint8_t* __restrict__ rbsp, uint64_t rbsp_cap,
-                unsigned long long* __restrict__ desc, RunHeader* __restrict__ hdr, int sched)
+                unsigned long long* __restrict__ desc, RunHeader* __restrict__ hdr)
 {
     const int tid0 = threadIdx.x;
     EmitTarget tgt;
@@ -421,16 +417,12 @@ void scan_tiles(TileLds& l, const uint8_t* __restrict__ stream, uint64_t n, uint
 
     const uint64_t full_tiles = n / (uint64_t)kTileBytes;      /* tiles [0, full_tiles) are complete */
     TileRegs nxt;
-    /* sched 0: tile i belongs to workgroup i mod grid; 1: tiles are handed out in
-     * arrival order at the top of the loop; 2: the next tile is taken (and its
-     * loads issued) once the current one has its prefix */
-    uint64_t tile = (sched == kSchedStriped) ? (uint64_t)blockIdx.x : take_ticket(l, hdr, tid0);
-    if (sched != kSchedTicketTop && tile < full_tiles) fetch_tile(nxt, stream, tile * (uint64_t)kTileBytes, tid0);
+    uint64_t tile = kTicket ? take_ticket(l, hdr, tid0) : (uint64_t)blockIdx.x;
+    if (tile < full_tiles) fetch_tile(nxt, stream, tile * (uint64_t)kTileBytes, tid0);
     HBS_T_DECL
 
     while (tile < num_tiles) {
         const uint64_t tile_base = tile * (uint64_t)kTileBytes;
-        if (sched == kSchedTicketTop && tile < full_tiles) fetch_tile(nxt, stream, tile_base, launder(tid0));
         uint64_t next_tile = tile + gridDim.x;
         do {
         {
@@ -465,11 +457,10 @@ void scan_tiles(TileLds& l, const uint8_t* __restrict__ stream, uint64_t n, uint
             const Prefix incl = fold(excl, agg);
             hdr->final_kept = incl.kept; hdr->final_nals = incl.nals; hdr->final_inside = incl.inside;
         }
-        /* Next tile's HBM reads fly under the emit and the gather.  They are issued
+        /* Striped: the next tile's HBM reads fly under the emit and the gather.  They are issued
          * behind the look-back because loads return in order: a descriptor read
          * queued behind 16 tile loads would wait for all of them. */
-        if (sched == kSchedTicketAfterPrefix) next_tile = take_ticket(l, hdr, launder(tid0));
-        if (sched != kSchedTicketTop && next_tile < full_tiles) fetch_tile(nxt, stream, next_tile * (uint64_t)kTileBytes, launder(tid0));
+        if (!kTicket && next_tile < full_tiles) fetch_tile(nxt, stream, next_tile * (uint64_t)kTileBytes, launder(tid0));
 
         const uint64_t ex_kept = excl.kept;
         const uint32_t tile_kept = agg.known + (excl.inside ? agg.sig : 0u);
@@ -497,9 +488,6 @@ void scan_tiles(TileLds& l, const uint8_t* __restrict__ stream, uint64_t n, uint
                     if (d.sub == 0xFFFFu) {
                         const Quad qd = view.quad((int32_t)(16u * c));
                         store16_unaligned(out + d.rank, qd);
-#if HBS2_COPY_DEPTH >= 0
-                        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(HBS2_COPY_DEPTH) : "memory");     /* a short memory queue on the CU: hbs_scan4.hip, round 3 */
-#endif
                     } else if (d.sub != 0u) {
                         const uint32_t slot = atomicAdd(&l.slow_cnt, 1u);
                         if (slot < (uint32_t)kSlowCap) l.slow[slot] = (uint16_t)c;
@@ -520,7 +508,10 @@ void scan_tiles(TileLds& l, const uint8_t* __restrict__ stream, uint64_t n, uint
         __syncthreads();
         HBS_T_MARK(6)
         } while (0);
-        if (sched == kSchedTicketTop) next_tile = take_ticket(l, hdr, launder(tid0));
+        if (kTicket) {
+            next_tile = take_ticket(l, hdr, launder(tid0));
+            if (next_tile < full_tiles) fetch_tile(nxt, stream, next_tile * (uint64_t)kTileBytes, launder(tid0));
+        }
         tile = next_tile;
     }
     HBS_T_FLUSH
@@ -530,11 +521,11 @@ __global__ __launch_bounds__(kThreads, 4)
 void k_scan_extract(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_tiles,
                     hbs_nal_entry* __restrict__ index, uint64_t index_cap,
                     uint8_t* __restrict__ rbsp, uint64_t rbsp_cap,
-                    unsigned long long* __restrict__ desc, RunHeader* __restrict__ hdr, int sched, int gate)
+                    unsigned long long* __restrict__ desc, RunHeader* __restrict__ hdr, int gate)
 {
     if (gate_closed(gate, hdr)) return;
     __shared__ TileLds l;
-    scan_tiles(l, stream, n, num_tiles, index, index_cap, rbsp, rbsp_cap, desc, hdr, sched);
+    scan_tiles<true>(l, stream, n, num_tiles, index, index_cap, rbsp, rbsp_cap, desc, hdr);
 }
 
 #ifdef HBS_PHASE_TIMING
@@ -622,7 +613,7 @@ void k_scan_small(const uint8_t* __restrict__ stream, uint64_t n,
     }
     __threadfence();
     __syncthreads();
-    if (n) scan_tiles(l, stream, n, 1, index, index_cap, rbsp, rbsp_cap, desc, hdr, kSchedStriped);
+    if (n) scan_tiles<false>(l, stream, n, 1, index, index_cap, rbsp, rbsp_cap, desc, hdr);
     __threadfence();
     __syncthreads();
     if (tid == 0) {
@@ -712,10 +703,10 @@ hipError_t launch_scan_extract(const ScanArgs& a, hipStream_t st)
              * holds to one element in 9 chunks itself: hbs_common.h) */
             if (!index_only) scan4r24_launch_kernel(a, tiles6, kGateIfMid, st);
             k_scan_extract<<<dim3((unsigned)grid), dim3(kThreads), 0, st>>>(
-                a.stream, a.n, tiles2, a.index, a.index_cap, a.rbsp, a.rbsp_cap, a.desc, a.hdr, a.sched, index_only ? kGateIfDenseIdx : kGateIfDense);
+                a.stream, a.n, tiles2, a.index, a.index_cap, a.rbsp, a.rbsp_cap, a.desc, a.hdr, index_only ? kGateIfDenseIdx : kGateIfDense);
         } else {
             k_scan_extract<<<dim3((unsigned)grid), dim3(kThreads), 0, st>>>(
-                a.stream, a.n, tiles2, a.index, a.index_cap, a.rbsp, a.rbsp_cap, a.desc, a.hdr, a.sched, kGateNone);
+                a.stream, a.n, tiles2, a.index, a.index_cap, a.rbsp, a.rbsp_cap, a.desc, a.hdr, kGateNone);
         }
         if (a.ev_end) note(hipEventRecord(a.ev_end, st));
     }

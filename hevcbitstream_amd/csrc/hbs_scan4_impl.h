@@ -94,41 +94,11 @@ static __device__ int g_fake_lb4 = 0;       /* experiments: 1 = do not look back
 #define HBS4_T_FLUSH
 #endif
 
-#ifndef HBS4_WG_PER_CU
-#define HBS4_WG_PER_CU 2      /* workgroups per CU = wavefronts per SIMD the register budget is cut for */
-#endif
-#ifndef HBS4_TICKET_BARRIER
-#define HBS4_TICKET_BARRIER 0  /* 1: a barrier in front of the ordinary tile's ticket too (wavefront 0, which takes it, is nearly always the last to finish) */
-#endif
-#ifndef HBS4_PROGRESSIVE
-#define HBS4_PROGRESSIVE 1     /* the fetch inside the flag pass, four rows at a time */
-#endif
-#ifndef HBS4_EXACT_FLAG
-#define HBS4_EXACT_FLAG 1      /* rows with a zero pair are asked again, exactly: only chunks a pattern 00 00 {<=3} touches become elements */
-#endif
-#ifndef HBS4_ELEM_WAVES
-#if HBS4_ROWS <= 24
-#define HBS4_ELEM_WAVES 4      /* 24 rows: nothing is parked, every wavefront takes element batches */
-#define HBS4_EMIT_WAVES 4
-#endif
-#endif
-#ifndef HBS4_ELEM_WAVES
-#define HBS4_ELEM_WAVES 2      /* wavefronts that share the batches of a tile with more than 64 elements (each parks kParkRows rows in LDS) */
-#endif
-#ifndef HBS4_EMIT_WAVES
-#define HBS4_EMIT_WAVES 2      /* wavefronts that share the second half (emission) of those batches (4: the other two with all their rows in place -- spills 45 registers, some on every tile's path) */
-#endif
-#ifndef HBS4_EXACT_MIN
-#define HBS4_EXACT_MIN kExactFlagMin       /* ... when the row has more flagged chunks than this */
-#endif
-#ifndef HBS4_COPY_DEPTH
-#define HBS4_COPY_DEPTH 3      /* stores of a wavefront in flight during the copy (-1: no limit) */
-#endif
-#ifdef HBS4_NO_PRIO
-#define HBS4_PRIO(p)
-#else
-#define HBS4_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#endif
+constexpr int kWgPerCu = 2;           /* workgroups per CU = wavefronts per SIMD the register budget is cut for */
+/* wavefronts that share the batches of a tile with more than 64 elements, in both halves: with 48 rows, two that park
+ * kParkRows rows each in LDS; with 24 rows nothing is parked and all four take them */
+constexpr int kElemWaves = HBS4_ROWS == 48 ? 2 : 4;
+constexpr int kCopyDepth = 3;          /* stores of a wavefront in flight during the copy */
 static_assert(k4Rows == HBS4_ROWS, "hbs_sparse.h takes the geometry from HBS4_ROWS");
 constexpr int kParkRows = HBS4_PARK_ROWS;          /* rows of an element wavefront that wait in LDS meanwhile (hbs_scan4_rows*.h) */
 
@@ -142,16 +112,6 @@ struct RowRegs {
     uint32_t after;           /* dword behind it (0xFF bytes past the end of the stream)      */
 };
 
-/* All of a wavefront's rows, unguarded: the last tile of a stream is read from a padded copy
- * (k_scan_prologue), so every address below exists.  `src` is the stream or that copy. */
-__device__ __forceinline__ void fetch_row_regs(RowRegs& R, const uint8_t* __restrict__ src, uint64_t seg, int lane)
-{
-    const u32x4* p = reinterpret_cast<const u32x4*>(src + seg) + lane;
-#define HBS_LD(r) R.q##r = stream_load16(p + r * 64);
-    HBS_ROWS(HBS_LD)
-#undef HBS_LD
-}
-
 constexpr int kDepCap = 64;
 constexpr uint32_t kDenseElems = HBS4_ROWS == 48 ? 512 : 1024;      /* a tile with more elements than this is walked by rows (dense tiles, below): 4.2 % of a 192 KiB tile's chunks, 16.7 % of a 96 KiB tile's */
 
@@ -163,7 +123,7 @@ struct Lds4 {
     u32x4 rec[kDenseElems][3];             /* tiles with several batches of elements: what the first walk found out about each
                                               (marks, summary, classes, its bytes), so that the second half does not walk it again */
     Deposit dep[k4Waves][kDepCap];         /* bytes of the first elements of each wavefront, left by the flag pass */
-    u32x4 park[kParkRows ? HBS4_ELEM_WAVES : 1][kParkRows ? kParkRows : 1][kParkRows ? 64 : 1];   /* rows of the wavefronts that handle elements (wavefront 0 always, and it looks back) meanwhile */
+    u32x4 park[kParkRows ? kElemWaves : 1][kParkRows ? kParkRows : 1][kParkRows ? 64 : 1];   /* rows of the wavefronts that handle elements (wavefront 0 always, and it looks back) meanwhile */
     unsigned long long ex_kept, ex_nals;   /* the tile's exclusive prefix, from wavefront 0 */
     uint32_t ex_inside, ex_ok;
     uint32_t ticket;
@@ -280,7 +240,7 @@ __device__ __forceinline__ void rec4_load(const u32x4* r, Elem& el, const uint8_
     el.v.stream = src; el.v.g0 = base + 16ull * a.x; el.v.n = n;
 }
 
-/* second half of the batches first, first + HBS4_EMIT_WAVES, ... of a tile with several: index entries, the elements' own
+/* second half of the batches first, first + kElemWaves, ... of a tile with several: index entries, the elements' own
  * bytes, a segment word each; the tile's exclusive prefix is in LDS by now */
 __device__ __forceinline__ void emit_batches(Lds4& l, uint32_t first, uint32_t npass, uint32_t nflag, int lane,
                                              const uint8_t* src, uint64_t base, uint64_t n, uint8_t* rbsp, const EmitTarget& tgt)
@@ -290,7 +250,7 @@ __device__ __forceinline__ void emit_batches(Lds4& l, uint32_t first, uint32_t n
     const Prefix exu = prefix_uniform4(exl);
     const bool canu = rbsp != nullptr && l.ex_ok == 1u;
 #pragma unroll 1
-    for (uint32_t p = first; p < npass; p += (uint32_t)HBS4_EMIT_WAVES) {
+    for (uint32_t p = first; p < npass; p += (uint32_t)kElemWaves) {
         TileAgg accb = agg_identity();
 #pragma unroll 1
         for (uint32_t q = 0; q < p; ++q) accb = combine(accb, l.bagg[q]);
@@ -397,7 +357,7 @@ bool dense_tile(Lds4& l, const uint8_t* src, uint64_t wseg, uint64_t n, uint32_t
         HBS4_TL(tile, 1, 1)
         const bool ok = look_back4(desc, tile, tagg, hdr, lane, ex, it, stl);
         HBS4_TL(tile, 2, 0)
-        HBS4_PRIO(0);
+        __builtin_amdgcn_s_setprio(0);
         const uint32_t tile_kept = tagg.known + (ex.inside ? tagg.sig : 0u);
         const bool can = rbsp != nullptr && ex.kept + tile_kept <= rbsp_cap;
         if (lane == 0) {
@@ -410,7 +370,7 @@ bool dense_tile(Lds4& l, const uint8_t* src, uint64_t wseg, uint64_t n, uint32_t
             }
         }
     } else {
-        HBS4_PRIO(0);
+        __builtin_amdgcn_s_setprio(0);
     }
     __syncthreads();
     if (l.ex_ok == 0u) return false;
@@ -498,7 +458,7 @@ void launch_scan_ahead4(const ScanArgs& a, uint64_t num_tiles, int gate, hipStre
 
 /* tail: the 0xFF-padded copy of the stream from `tail_base` - k4TailLead on (k_scan_prologue: the last 192 KiB tile of the stream,
  * which holds the last tile of either geometry); the stream's last tile is read from it, unguarded */
-__global__ __launch_bounds__(k4Threads, HBS4_WG_PER_CU)
+__global__ __launch_bounds__(k4Threads, kWgPerCu)
 void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_tiles,
                  hbs_nal_entry* __restrict__ index, uint64_t index_cap,
                  uint8_t* __restrict__ rbsp, uint64_t rbsp_cap,
@@ -544,7 +504,7 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
         const uint8_t* const src = last_tile
             ? reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(tail) + (uintptr_t)k4TailLead - (uintptr_t)tail_base) : stream;
         /* until the tile's aggregate is out, this workgroup is what its successors wait for */
-        HBS4_PRIO(3);
+        __builtin_amdgcn_s_setprio(3);
         RowRegs R;
         /* The dwords around the segment first: the first group of the flag pass needs them, and a load issued behind the rows
          * would make it wait for all of them.  The rows themselves are fetched INSIDE the flag pass, four at a time. */
@@ -553,9 +513,6 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
         R.after = (last_tile || wv != k4Waves - 1) ? stream_load4(src + wseg + k4WaveBytes)
                                                    : load_dword_guarded(stream, (int64_t)(wseg + k4WaveBytes), n);
         const u32x4* const rowp = reinterpret_cast<const u32x4*>(src + wseg) + lane;
-#if !HBS4_PROGRESSIVE
-        fetch_row_regs(R, src, wseg, lane);
-#endif
         HBS4_T_MARK(0)
 
         /* ---- 1. flag masks of my rows --------------------------------------------------- */
@@ -577,7 +534,7 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
                 if (fmask##r != 0) {     /* a zero pair somewhere: now the exact question -- does a pattern 00 00 {<=3} end in bytes [0, 18)? */ \
                     bool g##r = f##r; \
                     uint64_t gmask##r = fmask##r; \
-                    if (HBS4_EXACT_FLAG && __builtin_popcountll(fmask##r) > HBS4_EXACT_MIN) {   /* one or two: a start code, most likely -- nothing to gain */ \
+                    if (__builtin_popcountll(fmask##r) > kExactFlagMin) {   /* one or two: a start code, most likely -- nothing to gain */ \
                         g##r = f##r && chunk_pattern_any_dev(xp##r, R.q##r.x, R.q##r.y, R.q##r.z, R.q##r.w, xn##r); \
                         gmask##r = __ballot(g##r); \
                     } \
@@ -610,14 +567,9 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
              * look-back polls of the OTHER workgroup on this CU waited behind them, 2.7 us a poll; a model of this kernel
              * (scripts/ubench/ceiling3.hip, profiles/r03/ceiling3_*.txt) moves 5.9 TB/s with both throttled and 5.1-5.3 without.
              * The sched_barriers keep the compiler from hoisting the loads back to the top. */
-#if HBS4_PROGRESSIVE
 #define HBS_LD4(a, b, c, d) { R.q##a = stream_load16(rowp + a * 64); R.q##b = stream_load16(rowp + b * 64); \
                 R.q##c = stream_load16(rowp + c * 64); R.q##d = stream_load16(rowp + d * 64); __builtin_amdgcn_sched_barrier(0); }
 #define HBS_FLAG_FENCE __builtin_amdgcn_sched_barrier(0);
-#else
-#define HBS_LD4(a, b, c, d)
-#define HBS_FLAG_FENCE
-#endif
             /* the rows' loads and flag groups in order: hbs_scan4_rows*.h, written by scripts/set_rows4.py */
             HBS_FLAG_PASS
 #undef HBS_FLAG_GROUP
@@ -679,7 +631,7 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
          * all batches alone, ~10 k cycles each, the other three waiting; all FOUR on the elements would need 80 KiB of parked
          * rows, or the rows read again: tried as a function of its own, it lost to this below five batches and gained 4 % above.) */
         const bool multi = npass > 1u;
-        const bool elem_wave = wv == 0 || (multi && wv < HBS4_ELEM_WAVES);
+        const bool elem_wave = wv == 0 || (multi && wv < kElemWaves);
         if (elem_wave) {
             /* this code needs ~100 registers of its own: part of this wavefront's rows wait in LDS */
             Elem el;
@@ -699,7 +651,7 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
                 acc = agg_readlane(ea, 63);
             } else {
 #pragma unroll 1
-                for (uint32_t p = (uint32_t)wv; p < npass; p += (uint32_t)HBS4_ELEM_WAVES) {
+                for (uint32_t p = (uint32_t)wv; p < npass; p += (uint32_t)kElemWaves) {
                     const uint32_t i = p * (uint32_t)k4ElemPass + (uint32_t)lane;
                     TileAgg ea = agg_identity();
                     if (i < nflag) {
@@ -725,7 +677,7 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
             HBS4_DBG(if (g_fake_lb4) { ok = true; it = 0; stl = 0; ex.kept = tile * (uint64_t)(k4TileBytes - 4096); ex.nals = tile * 16; ex.inside = 1; } else)
             ok = look_back4(desc, tile, tagg, hdr, lane, ex, it, stl);
             HBS4_T_COUNT(7, ((unsigned long long)stl << 32) | it)
-            HBS4_PRIO(0);
+            __builtin_amdgcn_s_setprio(0);
             const uint32_t tile_kept = tagg.known + (ex.inside ? tagg.sig : 0u);
             can = rbsp != nullptr && ex.kept + tile_kept <= rbsp_cap;
             if (lane == 0) {
@@ -741,7 +693,7 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
             HBS4_T_MARK(3)
             HBS4_TL(tile, 2, 0)
             } else {
-                HBS4_PRIO(0);
+                __builtin_amdgcn_s_setprio(0);
             }
             if (multi) __syncthreads();
             if (!multi) {
@@ -755,14 +707,9 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
 #undef HBS_UNPARK
         } else {
             /* (a barrier counts wavefronts, wherever they are in the code: these two meet the two above) */
-            HBS4_PRIO(0);
+            __builtin_amdgcn_s_setprio(0);
             if (multi) {
                 __syncthreads(); __syncthreads();
-#if HBS4_EMIT_WAVES > HBS4_ELEM_WAVES
-                /* the second half needs fewer registers than the first (no window rules: what they found is in LDS): these
-                 * wavefronts take their share of it with all their rows in place */
-                if (l.ex_ok != 0u) emit_batches(l, (uint32_t)wv, npass, nflag, lane, src, base, n, rbsp, tgt);
-#endif
             }
         }
         __syncthreads();
@@ -787,13 +734,8 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
              * elements) come from LDS, one broadcast read per row */
             const uint32_t segv = l.seg[lane];
             const uint32_t seg64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)l.seg[k4ElemPass]);
-            /* At most HBS4_COPY_DEPTH stores of a wavefront in flight (see the flag pass: a short memory queue on the CU is what
+            /* At most kCopyDepth stores of a wavefront in flight (see the flag pass: a short memory queue on the CU is what
              * lets the other workgroup's look-back through; depth 3 is the model's optimum, 5 and more lose all of it). */
-#if HBS4_COPY_DEPTH >= 0
-#define HBS_COPY_THROTTLE asm volatile("s_waitcnt vmcnt(%0)" :: "n"(HBS4_COPY_DEPTH) : "memory");
-#else
-#define HBS_COPY_THROTTLE
-#endif
             /* Straight-line over the named rows.  A chunk with k elements in front of it goes where segment word k says. */
 #define HBS_COPY(r) { \
                 const uint32_t cc = cc0 + 64u * r; \
@@ -811,10 +753,9 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
                         if (seg_inside(w)) arena_store16(out + (int64_t)(seg_bias(w) + (int32_t)(16u * cc)), R.q##r); \
                     } \
                 } \
-                HBS_COPY_THROTTLE }
+                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kCopyDepth) : "memory"); }
             HBS_ROWS(HBS_COPY)
 #undef HBS_COPY
-#undef HBS_COPY_THROTTLE
         }
         /* The next tile is claimed only now: tiles are looked back in ticket order, and a ticket
          * taken before the copy (whose duration varies with memory load) makes successors wait for
@@ -822,9 +763,6 @@ void HBS4_KERNEL(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_ti
          * out in stripes instead (tile = workgroup + k x grid, no atomic, no drain of this wavefront's stores
          * in front of it) ran 8.6 ms against 7.06 on the 16 GiB bench stream: workgroups do not progress
          * evenly, and with stripes the fast ones wait in their look-backs for the slow ones. */
-#if HBS4_TICKET_BARRIER
-        __syncthreads();
-#endif
         if (tid == 0) l.ticket = ticket_base + atomicAdd(&hdr->ticket, 1u);
         __syncthreads();
         HBS4_T_MARK(5)
@@ -958,7 +896,7 @@ void k_scan_prologue(const uint8_t* __restrict__ stream, uint64_t n, RunHeader* 
                     const Quad q = *reinterpret_cast<const Quad*>(stream + off);
                     const uint32_t xp = off >= 4 ? *reinterpret_cast<const uint32_t*>(stream + off - 4) : 0xFFFFFFFFu;
                     const uint32_t xn = off + 20 <= n ? *reinterpret_cast<const uint32_t*>(stream + off + 16) : 0xFFFFFFFFu;
-                    f = chunk_flag(xp, q.x, q.y, q.z, q.w, xn) && (!HBS4_EXACT_FLAG || chunk_pattern_any_dev(xp, q.x, q.y, q.z, q.w, xn));
+                    f = chunk_flag(xp, q.x, q.y, q.z, q.w, xn) && chunk_pattern_any_dev(xp, q.x, q.y, q.z, q.w, xn);
                 }
                 chunks += (uint32_t)__builtin_popcountll(__ballot(in));
                 flagged += (uint32_t)__builtin_popcountll(__ballot(f));

@@ -21,20 +21,13 @@
 
 namespace hbs {
 
-#ifndef HBS5_ROWS_KERNEL
-#define HBS5_ROWS_KERNEL 0     /* 1: the emit pass's row walks (tiles of padding or zeros) as a launch of their own */
-#endif
-#ifndef HBS5_SPAN_ROWS
-#define HBS5_SPAN_ROWS 16
-#define HBS5_TILE_ROWS 256
-#endif
-constexpr int k5SpanRows = HBS5_SPAN_ROWS;                    /* rows of 1 KiB a wavefront flags per step */
+constexpr int k5SpanRows = 16;                                /* rows of 1 KiB a wavefront flags per step */
 constexpr uint64_t k5SpanBytes = (uint64_t)k5SpanRows * 1024u;
 /* KiB of stream (= flag words) per tile: a launch parameter since round 5 (`rows`, a whole number of spans, 64 ... 512).  From 4 GiB
  * up it is k5TileRowsLarge, as always; below, the tiles are cut so that every resident wavefront gets the SAME whole number of
  * them (scan5_tile_rows): a 1 GiB stream in 256 KiB tiles is 4096 tiles for 3072 wavefronts -- a third of them took a second
  * tile while the others sat idle, 220 us where the 16 GiB rate says 180. */
-constexpr int k5TileRowsLarge = HBS5_TILE_ROWS;
+constexpr int k5TileRowsLarge = 256;
 constexpr int k5MaxTileRows = 512, k5MinTileRows = 64;
 constexpr int k5MaxWordsPerLane = k5MaxTileRows / 64;         /* lane l owns words [wpl l, wpl l + wpl) of its tile when elements are numbered; wpl = ceil(rows / 64) */
 static_assert(k5TileRowsLarge % k5SpanRows == 0 && k5TileRowsLarge <= k5MaxTileRows && k5MinTileRows % k5SpanRows == 0, "tile = whole spans");
@@ -293,7 +286,6 @@ constexpr uint32_t k5Rewalk = 0xFFFFFFFFu;                                /* nre
  * tile; the tile's own wavefront takes part 0, and all wavefronts of the launch share the other parts of all listed tiles once
  * their own tile is done. */
 constexpr uint32_t k5RewalkParts = 0xFFFFFFFEu;
-constexpr uint32_t k5RewalkWhole = 0xFFFFFFFDu;                           /* ... and one that only the emit pass found dense (not expected): all its rows by its own wavefront */
 constexpr int kPartRows = 32;
 static_assert(kPartRows % k5SpanRows == 0 && k5MaxTileRows / kPartRows <= 16, "a part is whole spans; its aggregates fit the tile's record space many times over");
 constexpr int k5ChunkTiles = 64;
@@ -739,7 +731,6 @@ void k_index5_emit(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_
             const uint32_t nelem = tile_census(l, lane, wpl, by_rows);
             if (by_rows) {                                          /* (the stream pass's census said otherwise: not expected) */
                 own_rows = rows;
-                if (HBS5_ROWS_KERNEL && lane == 0) w5.nrec[tile] = k5RewalkWhole;
             } else {
                 const Prefix excl = tile_prefix5(w5, tile, lane);
                 TileAgg accb = agg_identity();
@@ -759,31 +750,10 @@ void k_index5_emit(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_
             }
         }
     }
-#if !HBS5_ROWS_KERNEL
     if (own_rows == 0 && jobs == 0) return;
     __builtin_amdgcn_wave_barrier();                               /* l is reused */
     emit_row_jobs5(l, stream, n, num_tiles, index, index_cap, rows, ws, hdr, own_rows, jobs);
-#endif
 }
-
-#if HBS5_ROWS_KERNEL
-/* the row jobs as a launch of their own behind k_index5_emit (same grid: a wavefront per tile; all leave at once when no tile
- * was walked by rows) */
-__global__ __launch_bounds__(64)
-void k_index5_emit_rows(const uint8_t* __restrict__ stream, uint64_t n, uint64_t num_tiles,
-                        hbs_nal_entry* __restrict__ index, uint64_t index_cap, int rows, void* __restrict__ ws, RunHeader* __restrict__ hdr, int gate)
-{
-    if (gate_closed(gate, hdr)) return;
-    __shared__ Lds5 l;
-    const Ws5 w5 = ws5_carve(ws, num_tiles, rows);
-    const int nparts = (rows + kPartRows - 1) / kPartRows;
-    const uint64_t jobs = (uint64_t)hdr->rewalk_count * (uint64_t)(nparts - 1);
-    const uint32_t nrec = w5.nrec[blockIdx.x];
-    const int own_rows = nrec == k5RewalkParts ? (rows < kPartRows ? rows : kPartRows) : nrec == k5RewalkWhole ? rows : 0;
-    if (own_rows == 0 && jobs == 0) return;
-    emit_row_jobs5(l, stream, n, num_tiles, index, index_cap, rows, ws, hdr, own_rows, jobs);
-}
-#endif
 
 /* ---- host side ---------------------------------------------------------------------------- */
 
@@ -828,28 +798,18 @@ int scan5_tile_rows(uint64_t n, uint64_t waves) { return scan5_geometry(n, waves
 
 void launch_scan_index5(const ScanArgs& a, int gate, hipStream_t st)
 {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    static const int per_cu = [] {                             /* what is resident: 168 VGPRs per lane (held there by amdgpu_waves_per_eu: 7 per-tile values live in scratch) -> 3 wavefronts per SIMD (8 or 16 per CU measured slower) */
-        const char* e = getenv("HBS5_WAVES_PER_CU");            /* debugging aid */
-        return e && atoi(e) > 0 && atoi(e) <= 32 ? atoi(e) : 12;
-    }();
+    /* what is resident: 168 VGPRs per lane (held there by amdgpu_waves_per_eu: 7 per-tile values live in scratch) -> 3 wavefronts per SIMD (8 or 16 per CU measured slower) */
+    constexpr int per_cu = 12;
     static const int env_rows = [] {                           /* debugging aid: a tile height for every call */
         const char* e = getenv("HBS5_TILE_ROWS");
         const int v = e ? atoi(e) : 0;
         return (v >= k5MinTileRows && v <= k5MaxTileRows && v % k5SpanRows == 0) ? v : 0;
     }();
-    uint64_t waves = (uint64_t)cus * (uint64_t)per_cu;
+    uint64_t waves = (uint64_t)a.cus * (uint64_t)per_cu;
     /* hbs_ctx_reserve_workgroups: a reserved slot is four wavefronts' worth of registers (one 256-thread workgroup of the
      * event-sparse kernel); these one-wavefront workgroups fill every SIMD otherwise */
     if (a.spare_wgs > 0) waves = waves > 4ull * (uint64_t)a.spare_wgs + 64 ? waves - 4ull * (uint64_t)a.spare_wgs : 64;
     Geo5 g = scan5_geometry(a.n, waves);
-    static const int env_ticket = [] { const char* e = getenv("HBS5_FORCE_TICKET"); return e ? atoi(e) : 0; }();   /* debugging aid: 256-row tiles by ticket at any size (round 4's schedule) */
-    if (env_ticket) {
-        g.rows = k5TileRowsLarge; g.strided = 0;
-        g.tiles = (a.n + 1024ull * (uint64_t)g.rows - 1) / (1024ull * (uint64_t)g.rows);
-        g.grid = waves < g.tiles ? waves : g.tiles;
-    }
     if (env_rows) {                                            /* (the debugging aid: that height, by ticket) */
         g.rows = env_rows; g.strided = 0;
         g.tiles = (a.n + 1024ull * (uint64_t)env_rows - 1) / (1024ull * (uint64_t)env_rows);
@@ -868,9 +828,6 @@ void launch_scan_index5(const ScanArgs& a, int gate, hipStream_t st)
     }
     if (rows == k5TileRowsLarge) k_index5_emit<k5TileRowsLarge><<<dim3((unsigned)num_tiles), dim3(64), 0, st>>>(a.stream, a.n, num_tiles, a.index, a.index_cap, rows, a.ws5, a.hdr, gate);
     else k_index5_emit<0><<<dim3((unsigned)num_tiles), dim3(64), 0, st>>>(a.stream, a.n, num_tiles, a.index, a.index_cap, rows, a.ws5, a.hdr, gate);
-#if HBS5_ROWS_KERNEL
-    k_index5_emit_rows<<<dim3((unsigned)num_tiles), dim3(64), 0, st>>>(a.stream, a.n, num_tiles, a.index, a.index_cap, rows, a.ws5, a.hdr, gate);
-#endif
 }
 
 } // namespace hbs

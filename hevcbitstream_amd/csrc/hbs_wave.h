@@ -18,12 +18,6 @@ typedef u32x4 u32x4_u1 __attribute__((aligned(1)));        /* a 16-byte access a
 /* Streaming accesses.  The stream is read once and the arena written once, so neither should displace
  * anything in the caches: `nt` loads read at 6.9 TB/s where default-policy loads of the same pattern read
  * at 6.2 (scripts/ubench/ceiling2.hip, profiles/r02/ceiling2.txt). */
-#ifndef HBS_NT_LOAD
-#define HBS_NT_LOAD 1
-#endif
-#ifndef HBS_NT_STORE
-#define HBS_NT_STORE 1
-#endif
 /* The pointer is cast to the global address space: where hipcc cannot prove that (a pointer picked between two
  * buffers, as the last tile's padded copy is) it emits flat_load, which counts on lgkmcnt too and so is waited
  * for by every `s_waitcnt lgkmcnt(0)` in front of a barrier. */
@@ -32,11 +26,7 @@ typedef const __attribute__((address_space(1))) uint32_t* global_u32_ptr;
 __device__ __forceinline__ u32x4 stream_load16(const u32x4* p)
 {
     const global_u32x4_ptr g = (global_u32x4_ptr)(uintptr_t)p;
-#if HBS_NT_LOAD
     return __builtin_nontemporal_load(g);
-#else
-    return *g;
-#endif
 }
 __device__ __forceinline__ uint32_t stream_load4(const uint8_t* p)
 {
@@ -44,11 +34,7 @@ __device__ __forceinline__ uint32_t stream_load4(const uint8_t* p)
 }
 __device__ __forceinline__ void arena_store16(uint8_t* p, u32x4 v)
 {
-#if HBS_NT_STORE
     __builtin_nontemporal_store(v, reinterpret_cast<u32x4_u1*>(p));
-#else
-    *reinterpret_cast<u32x4_u1*>(p) = v;
-#endif
 }
 
 /* Loads that may straddle either end of the stream (bytes outside read as 0xFF).  Rolled byte

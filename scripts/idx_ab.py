@@ -18,7 +18,7 @@ args = ap.parse_args()
 ctx = hbs.Context(0)
 ctx.enable_timing(True)
 lib = os.path.basename(os.path.dirname(os.environ.get("HBS_LIB", "/default/x")))
-tag = {k: os.environ[k] for k in ("HBS5_FORCE_TICKET", "HBS5_TILE_ROWS") if k in os.environ}
+tag = {k: os.environ[k] for k in ("HBS5_TILE_ROWS",) if k in os.environ}
 
 
 def run(stream, sb, n_cap, reps=args.reps):

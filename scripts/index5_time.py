@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Index-only scan on the bench stream, kernel ms by HIP events (dev aid): python scripts/index5_time.py [reps]
-HBS_LIB picks a development build, HBS5_WAVES_PER_CU the grid."""
+HBS_LIB picks a development build."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +29,7 @@ for i in range(reps + 1):
         ks.append(ctx.kernel_ms())
 s = ctx.read_summary(summary)
 if os.environ.get("HBS5_NOCHECK"):
-    print(json.dumps({"lib": os.path.basename(os.path.dirname(os.environ.get("HBS_LIB", "/default/x"))), "waves_per_cu": os.environ.get("HBS5_WAVES_PER_CU", "20"),
+    print(json.dumps({"lib": os.path.basename(os.path.dirname(os.environ.get("HBS_LIB", "/default/x"))),
                       "ms_min": round(min(ks), 4), "ms_med": round(sorted(ks)[len(ks) // 2], 4), "unchecked": True}))
     sys.exit(0)
 assert int(s["error"]) == 0 and int(s["nal_count"]) == n, s
@@ -37,6 +37,6 @@ a = index[: n * 32].view(torch.int64).view(n, 4)
 b = g["index"][: n * 32].view(torch.int64).view(n, 4)
 assert torch.equal(a[:, :2], b[:, :2]), "index-only NAL index != generator's index"
 ks.sort()
-print(json.dumps({"lib": os.path.basename(os.path.dirname(os.environ.get("HBS_LIB", "/default/x"))), "waves_per_cu": os.environ.get("HBS5_WAVES_PER_CU", "20"),
+print(json.dumps({"lib": os.path.basename(os.path.dirname(os.environ.get("HBS_LIB", "/default/x"))),
                   "kernel": ctx.last_kernel(), "ms_min": round(ks[0], 4), "ms_med": round(ks[len(ks) // 2], 4),
                   "read_TBs_med": round((sb + 32 * n) / ks[len(ks) // 2] / 1e9, 3)}))
