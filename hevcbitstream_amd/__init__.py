@@ -6,7 +6,9 @@ torch tensors.  All work happens in the HIP kernels; there is no CPU fallback --
 loading fails loudly when the library has not been built, and creating a
 context fails when there is no gfx950 GPU."""
 from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TRAILING03,  # noqa: F401
-                  ST_UNTERMINATED, library_path, load_library, source_digest)
+                  ST_UNTERMINATED, library_path, load_library, source_digest,
+                  NAL_FILTER, NALMASK_VCL, NALMASK_IRAP, NALMASK_PARAM_SETS, NALMASK_SEI, NALMASK_ALL)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
-           "ST_UNTERMINATED", "library_path", "load_library", "source_digest"]
+           "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
+           "NAL_FILTER", "NALMASK_VCL", "NALMASK_IRAP", "NALMASK_PARAM_SETS", "NALMASK_SEI", "NALMASK_ALL"]

@@ -13,6 +13,14 @@ SUMMARY = np.dtype([("nal_count", "<u8"), ("nal_found", "<u8"), ("rbsp_bytes", "
                     ("stream_bytes", "<u8"), ("stop_reason", "<i4"), ("error", "<i4"),
                     ("reserved", "<u8", (3,))])
 ST_ERROR, ST_TRAILING03, ST_UNTERMINATED = 1, 2, 4
+# layout of hbs_nal_filter and the masks of its keep_types (hbs_filter_annexb)
+NAL_FILTER = np.dtype([("keep_types", "<u8"), ("max_temporal_id_plus1", "<i4"), ("max_layer_id", "<i4"),
+                       ("keep_short", "<i4"), ("reserved", "<i4")])
+NALMASK_VCL = 0x00000000FFFFFFFF            # types 0..31
+NALMASK_IRAP = 0x0000000000FF0000           # types 16..23
+NALMASK_PARAM_SETS = 0x0000000700000000     # types 32..34
+NALMASK_SEI = 0x0000018000000000            # types 39, 40
+NALMASK_ALL = 0xFFFFFFFFFFFFFFFF
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -38,7 +46,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_host_alloc", "hbs_host_free", "hbs_copy_to_device_async", "hbs_copy_device",
            "hbs_ctx_set_sequential_parse", "hbs_ctx_set_emit_path", "hbs_parse_extended",
            "hbs_comm_unique_id", "hbs_comm_create", "hbs_comm_adopt", "hbs_comm_destroy", "hbs_comm_rank", "hbs_comm_world", "hbs_comm_reserve_hint", "hbs_parse_headers_compact", "hbs_parse_materialize", "hbs_index_parse_compact", "hbs_gather_parts", "hbs_index_parse", "hbs_ctx_reserve_workgroups",
-           "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive"]
+           "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
+           "hbs_filter_annexb"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -160,6 +169,8 @@ def load_library():
     lib.hbs_pair_alloc.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p]
     lib.hbs_pair_free.argtypes = [C.c_void_p, C.c_void_p]
     lib.hbs_ctx_last_emit_by_tiles.argtypes = [C.c_void_p]
+    lib.hbs_filter_annexb.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -580,3 +591,68 @@ class Context:
         if int(s["error"]) != 0:
             raise HbsError("hbs_parse_headers: error %d" % int(s["error"]))
         return parsed[: n_nals * PARSED.itemsize].cpu().numpy().view(PARSED).copy(), structs
+
+    # ---- NAL filter -------------------------------------------------------------------
+
+    @staticmethod
+    def nal_filter(keep_types=NALMASK_ALL, max_temporal_id_plus1=7, max_layer_id=63, keep_short=True):
+        """an hbs_nal_filter record (ndarray[NAL_FILTER] of one)"""
+        r = np.zeros(1, dtype=NAL_FILTER)
+        r["keep_types"] = int(keep_types) & NALMASK_ALL
+        r["max_temporal_id_plus1"] = int(max_temporal_id_plus1)
+        r["max_layer_id"] = int(max_layer_id)
+        r["keep_short"] = 1 if keep_short else 0
+        return r
+
+    def filter_annexb_async(self, stream, stream_bytes, index, n_nals, out, index_out, summary, rule=None, keep=None, out_cap=None):
+        """Enqueue hbs_filter_annexb on the current torch stream.  stream / index / out / index_out / summary / keep are device
+        tensors (out None: plan only; index_out may be None); rule is an ndarray[NAL_FILTER] of one (host memory).  Exactly one of
+        rule and keep is given."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if rule is not None:
+            rule = np.ascontiguousarray(rule, dtype=NAL_FILTER)
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        rc = self.lib.hbs_filter_annexb(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None,
+                                        int(n_nals), rule.ctypes.data_as(C.c_void_p) if rule is not None else None, p(keep),
+                                        p(out), int(out_cap), p(index_out), p(summary))
+        self._check(rc, "hbs_filter_annexb")
+
+    def filter_annexb(self, stream, index_entries, keep_types=NALMASK_ALL, max_temporal_id_plus1=7, max_layer_id=63,
+                      keep_short=True, keep=None, stream_bytes=None):
+        """Convenience: cut `stream` (device uint8 tensor) down to the NAL units a rule keeps -- or, keep given, those whose
+        byte in `keep` (array of n_nals, non-zero = keep; host or device) is set.  index_entries: ndarray[NAL_ENTRY] (host) or a
+        device uint8 tensor of its entries.  Plans first, allocates the exact output, runs.  Returns (out device tensor,
+        entries_out ndarray[NAL_ENTRY], summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        if isinstance(index_entries, np.ndarray):
+            n = len(index_entries)
+            d_idx = t.from_numpy(np.ascontiguousarray(index_entries).view(np.uint8).copy()).to(dev) if n else None
+        else:
+            n = index_entries.numel() // NAL_ENTRY.itemsize
+            d_idx = index_entries
+        nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
+        rule = None
+        d_keep = None
+        if keep is None:
+            rule = self.nal_filter(keep_types, max_temporal_id_plus1, max_layer_id, keep_short)
+        elif isinstance(keep, np.ndarray):
+            d_keep = t.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8).copy()).to(dev) if n else t.zeros(16, dtype=t.uint8, device=dev)
+        else:
+            d_keep = keep
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        self.filter_annexb_async(stream, nbytes, d_idx, n, None, None, summary, rule=rule, keep=d_keep)
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_filter_annexb: error %d" % int(s["error"]))
+        need = int(s["stream_bytes"])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        d_out_idx = t.empty(max(n, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
+        self.filter_annexb_async(stream, nbytes, d_idx, n, out, d_out_idx, summary, rule=rule, keep=d_keep, out_cap=need)
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_filter_annexb: error %d" % int(s["error"]))
+        kept = int(s["nal_count"])
+        return out[:need], d_out_idx[: kept * NAL_ENTRY.itemsize].cpu().numpy().view(NAL_ENTRY).copy(), s

@@ -16,6 +16,7 @@
 #include "hbs_hdrwin.h"
 #include "hbs_parse.h"
 #include "hbs_parse_compact.h"
+#include "hbs_filter.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -56,6 +57,7 @@ struct hbs_ctx {
     void* ahead; uint64_t ahead_tiles;   /* K12's dense tiles counted ahead: a table entry and a byte per 192 KiB tile (streams from 3 GiB up) */
     void* ws2; uint64_t ws2_bytes;   /* hbs_index_parse: header windows and the index that points into them (alive across the parse, which carves ws) */
     uint8_t* zeros;              /* sizeof(hevc_sps_t) zero bytes: the "no parameter set yet" structs */
+    void* fws; uint64_t fws_bytes;   /* hbs_filter_annexb's scratch: allocated on its first call, grow-only */
     /* optional timing of the dominant kernel */
     int timing; hipEvent_t ev0, ev1; int ev_valid;        /* ev0 / ev1: the slot of the ring the last call used */
     hipEvent_t ring0[kTimingRing], ring1[kTimingRing];    /* event pairs of the last kTimingRing timed calls */
@@ -165,6 +167,7 @@ void hbs_ctx_destroy(hbs_ctx* c)
     if (c->zeros) (void)hipFree(c->zeros);
     if (c->emit_verdict) (void)hipFree(c->emit_verdict);
     if (c->ws2) (void)hipFree(c->ws2);
+    if (c->fws) (void)hipFree(c->fws);
     if (c->ring0[0]) for (int i = 0; i < kTimingRing; ++i) { (void)hipEventDestroy(c->ring0[i]); (void)hipEventDestroy(c->ring1[i]); }
     (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -369,7 +372,7 @@ uint64_t hbs_ctx_device_bytes(hbs_ctx* c)
 {
     if (!c) return 0;
     const uint64_t zb = c->zeros ? ((sizeof(hevc_sps_t) + 255) & ~(uint64_t)255) : 0;
-    return c->desc_tiles * 16 + sizeof(hbs::RunHeader) + hbs::scan4_tail_bytes() + c->ws_bytes + c->ws2_bytes + (c->ahead_tiles ? 64 + c->ahead_tiles * hbs::scan4_ahead_entry_bytes() : 0) + zb;
+    return c->desc_tiles * 16 + sizeof(hbs::RunHeader) + hbs::scan4_tail_bytes() + c->ws_bytes + c->ws2_bytes + (c->ahead_tiles ? 64 + c->ahead_tiles * hbs::scan4_ahead_entry_bytes() : 0) + zb + c->fws_bytes;
 }
 
 uint64_t hbs_workspace_bytes(uint64_t stream_bytes)
@@ -503,6 +506,54 @@ int hbs_emit_annexb(hbs_ctx* c, const uint8_t* d_rbsp, uint64_t rbsp_bytes,
     c->last_emit_tflag = hbs::emit_takes_small_path(a.n, a.rbsp_bytes, a.two_pass) ? nullptr : c->emit_verdict;
     hipError_t e = hbs::launch_emit_annexb(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_emit_annexb");
+}
+
+int hbs_filter_annexb(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                      const hbs_nal_entry* d_index, uint64_t n_nals,
+                      const hbs_nal_filter* rule, const uint8_t* d_keep,
+                      uint8_t* d_out, uint64_t out_cap,
+                      hbs_nal_entry* d_index_out, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_nal_filter) == 24, "hbs_nal_filter layout");
+    if (!c || !d_summary || (rule == nullptr) == (d_keep == nullptr)) return HBS_E_ARG;
+    if (n_nals && (!d_index || (stream_bytes && !d_stream))) return HBS_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_stream) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_index) & 7) || (reinterpret_cast<uintptr_t>(d_index_out) & 7)) {
+        snprintf(c->err, sizeof(c->err), "stream/output pointers must be 16-byte aligned, index pointers 8-byte aligned");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    const uint64_t reach = d_out ? (out_cap < stream_bytes ? out_cap : stream_bytes) : 0;    /* the output is at most this long */
+    const uint64_t tiles = (reach + hbs::kFilterTileBytes - 1) / hbs::kFilterTileBytes;
+    const hbs::FilterScratch fs = hbs::filter_scratch(n_nals, tiles);
+    if (fs.total > c->fws_bytes) {
+        if (c->fws) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->fws); c->fws = nullptr; c->fws_bytes = 0; }
+        hipError_t e = hipMalloc(&c->fws, fs.total);
+        if (e != hipSuccess) return fail(c, e, "hipMalloc(filter scratch)");
+        c->fws_bytes = fs.total;
+    }
+    uint8_t* w = static_cast<uint8_t*>(c->fws);
+    hbs::FilterArgs a;
+    memset(&a, 0, sizeof(a));
+    a.stream = d_stream; a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals;
+    if (rule) { a.rule = *rule; a.use_rule = 1; }
+    a.keep = d_keep;
+    a.out = d_out; a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
+    a.part = reinterpret_cast<unsigned long long*>(w + fs.part);
+    a.ctl = reinterpret_cast<unsigned long long*>(w + fs.ctl);
+    a.kept_out = reinterpret_cast<unsigned long long*>(w + fs.kept_out);
+    a.kept_delta = reinterpret_cast<unsigned long long*>(w + fs.kept_delta);
+    a.tile_first = reinterpret_cast<unsigned long long*>(w + fs.tile_first);
+    a.tiles = tiles;
+    if (c->timing) {                                          /* this call's slot of the ring: all of its kernels */
+        const int slot = (int)(c->timed_calls % kTimingRing);
+        c->ev0 = c->ring0[slot]; c->ev1 = c->ring1[slot];
+        c->timed_calls += 1;
+        a.ev_begin = c->ev0; a.ev_end = c->ev1;
+        c->ev_valid = 1;
+    }
+    const hipError_t e = hbs::launch_filter_annexb(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_filter_annexb");
 }
 
 int hbs_synth_rbsp(hbs_ctx* c, uint64_t seed, uint64_t n_nals, int mode,

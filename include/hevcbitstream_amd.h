@@ -254,6 +254,54 @@ uint64_t hbs_annexb_bound(uint64_t rbsp_bytes, uint64_t n_nals);
 uint64_t hbs_annexb_bound_gaps(uint64_t rbsp_bytes, uint64_t n_nals, uint64_t gap_bytes);
 
 /*
+ * Cut an Annex-B stream down to some of its NAL units (keyframes only, temporal sub-layer extraction, stripping AUD / SEI /
+ * filler before muxing), on the device, with the index hbs_index_extract / hbs_index_parse made of it.
+ *
+ *   rule        HOST pointer: which NAL units pass, by the two header bytes stream[start], stream[start + 1] read raw
+ *               (nal_unit_type = (b0 >> 1) & 63, nuh_layer_id = ((b0 & 1) << 5) | (b1 >> 3), nuh_temporal_id_plus1 = b1 & 7:
+ *               the fields hbs_parse_headers reports; the forbidden bit and the status flags play no part).  A NAL passes iff
+ *               bit nal_unit_type of keep_types is set, nuh_temporal_id_plus1 <= max_temporal_id_plus1 and
+ *               nuh_layer_id <= max_layer_id; a NAL with end - start < 2 has no header and passes iff keep_short != 0.
+ *   d_keep      instead of a rule: n_nals bytes on the device, non-zero = keep.  Exactly one of rule and d_keep is non-NULL.
+ *   d_out       the output (16-byte aligned); NULL = plan only: only d_summary is written, stream_bytes = the output's size
+ *   d_index_out optional: room for n_nals entries
+ *
+ * The unit of NAL k is the stream bytes [end_{k-1}, end_k) (end_{-1} = 0): the zeros, the start code and whatever the start
+ * search skipped in front of the NAL, then its payload, all verbatim.  The output is the units of the kept NALs in index order,
+ * back to back (a rule that keeps everything writes stream[0, end_{n-1})).  d_index_out[j] describes the j-th kept NAL: start
+ * and end as offsets in the output, rbsp_len copied, rbsp_off the running sum of the kept rbsp_len, status the input status
+ * with HBS_ST_UNTERMINATED cleared and then set on the last kept entry only.  That is what hbs_index_extract of the output
+ * returns, with one exception: find_nal_unit's `i+4 >= size` rule (h264_nal.c:52) does not find a last kept NAL whose start
+ * code does not begin its unit and whose payload is short -- fewer than 2 bytes behind a 3-byte code (00 00 01), none behind a
+ * 4-byte one (00 00 00 01) -- so the scan of the output ends one NAL earlier.
+ *
+ * d_summary: nal_count = kept NALs, nal_found = n_nals, rbsp_bytes = sum of the kept rbsp_len, stream_bytes = output bytes,
+ * stop_reason = -1 if anything was kept, else 0.  error = HBS_E_ARG when the index is inconsistent (start > end,
+ * end > stream_bytes or start_k < end_{k-1}; each entry is checked before its header bytes are read), HBS_E_CAPACITY when
+ * out_cap is smaller than the output; in both cases nothing is written to d_out or d_index_out.  n_nals = 0 is valid (empty
+ * output).  Nothing outside [d_out, d_out + output bytes) is stored, and no load touches a 16-byte granule that holds no byte
+ * of the stream.  Returns HBS_E_ARG at once on bad arguments (both or neither of rule / d_keep, misaligned pointers).
+ */
+typedef struct hbs_nal_filter {
+    uint64_t keep_types;             /* bit t set: NAL units with nal_unit_type t pass                                   */
+    int32_t  max_temporal_id_plus1;  /* pass iff nuh_temporal_id_plus1 <= this (7: no limit; 0 in the header passes)     */
+    int32_t  max_layer_id;           /* pass iff nuh_layer_id <= this (63: no limit)                                     */
+    int32_t  keep_short;             /* NAL units with end - start < 2 have no header: kept iff non-zero                 */
+    int32_t  reserved;               /* 0                                                                                */
+} hbs_nal_filter;                    /* 24 bytes */
+
+#define HBS_NALMASK_VCL        0x00000000FFFFFFFFull    /* types 0..31                */
+#define HBS_NALMASK_IRAP       0x0000000000FF0000ull    /* types 16..23               */
+#define HBS_NALMASK_PARAM_SETS 0x0000000700000000ull    /* types 32..34: VPS SPS PPS  */
+#define HBS_NALMASK_SEI        0x0000018000000000ull    /* types 39, 40               */
+
+int hbs_filter_annexb(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
+                      const hbs_nal_entry* d_index, uint64_t n_nals,
+                      const hbs_nal_filter* rule, const uint8_t* d_keep,
+                      uint8_t* d_out, uint64_t out_cap,
+                      hbs_nal_entry* d_index_out, hbs_summary* d_summary);
+
+/*
  * K4: header parse, one NAL per lane (64 per wavefront), over the RBSP arena and index that
  * hbs_index_extract produced.  For NAL k it does what read_hevc_nal_unit()
  * does after nal_to_rbsp (hevc_stream.c:175-239): NAL header, then by type the
