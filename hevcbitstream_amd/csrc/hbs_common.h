@@ -81,7 +81,11 @@ struct RunHeader {
     uint32_t pad_a;
     unsigned long long ahead_cand, ahead_tab, ahead_stamp;
     uint32_t rewalk_count;    /* index-only scan (hbs_scan5.hip): tiles walked by rows, listed for the emit pass's helpers; cleared by the prologue */
-    uint32_t pad0[13];
+    uint32_t pad_b;
+    /* rbsp_off of NAL number index_cap, the first one the index has no room for: written by whoever finds that NAL, read only
+     * when the call found more than index_cap NALs (the last delivered entry's rbsp_len ends there) */
+    unsigned long long cap_next_off;
+    uint32_t pad0[10];
     uint32_t ticket;          /* next unclaimed tile (dynamic tile schedules); alone on its 128-byte line */
     uint32_t pad1[31];
     uint32_t probe_slot[64][2];   /* density probe, one pair per probe workgroup: chunks sampled, chunks flagged.  Plain

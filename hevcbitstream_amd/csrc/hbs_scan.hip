@@ -584,8 +584,8 @@ void k_scan_finish(const uint8_t* __restrict__ stream, uint64_t n,
             tail[i] = (q >= 0) ? stream[q] : (uint8_t)0xFF;
         }
         const TailOut t = tail_fixup(hdr, index, index_cap, rbsp, rbsp_cap, tail, n, sum, false);
-        if (lim > 0) fill_rbsp_len_v(index, index_cap, lim - 1, t.found, t.kept);
-        if (t.found > t.found0) fill_rbsp_len_v(index, index_cap, t.found0, t.found, t.kept);
+        if (lim > 0) fill_rbsp_len_v(index, index_cap, lim - 1, t.found, t.kept, hdr->cap_next_off);
+        if (t.found > t.found0) fill_rbsp_len_v(index, index_cap, t.found0, t.found, t.kept, hdr->cap_next_off);
     }
 }
 

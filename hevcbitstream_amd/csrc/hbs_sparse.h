@@ -230,6 +230,7 @@ HBS_D uint32_t emit_chunk_fast(const ElemClasses& cls, uint64_t g0, const ChunkM
                 tgt.index[k].start = g0 + e + 1;                      /* h264_nal.c:61-62 */
                 tgt.index[k].rbsp_off = rbsp_pos + (uint32_t)__builtin_popcount(m.cand & inside_mask);
             } else {
+                if (k == tgt.index_cap) tgt.hdr->cap_next_off = rbsp_pos + (uint32_t)__builtin_popcount(m.cand & inside_mask);
                 flag_error(tgt.hdr, (uint32_t)(-HBS_E_CAPACITY));
             }
             inside = true;

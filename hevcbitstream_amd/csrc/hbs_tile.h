@@ -396,6 +396,7 @@ HBS_D Mask emit_block_t(const View& v, int32_t o, uint64_t g0, const BlockMarksT
                 tgt.index[k].start = g0 + e + 1;              /* h264_nal.c:61-62 */
                 tgt.index[k].rbsp_off = rbsp_pos + mask_popc((Mask)(m.cand & inside_mask));
             } else {
+                if (k == tgt.index_cap) tgt.hdr->cap_next_off = rbsp_pos + mask_popc((Mask)(m.cand & inside_mask));
                 flag_error(tgt.hdr, (uint32_t)(-HBS_E_CAPACITY));
             }
             inside = true;
@@ -545,6 +546,8 @@ HBS_D TailOut tail_fixup(RunHeader* hdr, hbs_nal_entry* index, uint64_t index_ca
                     index[found].start = n - 1;
                     index[found].end = n;
                     index[found].rbsp_off = kept;
+                } else if (found == index_cap) {
+                    hdr->cap_next_off = kept;
                 }
                 if (rbsp != nullptr && kept < rbsp_cap) rbsp[kept] = e[-1];
                 kept += 1;
@@ -562,6 +565,8 @@ HBS_D TailOut tail_fixup(RunHeader* hdr, hbs_nal_entry* index, uint64_t index_ca
                     index[found].start = n;
                     index[found].end = n;
                     index[found].rbsp_off = kept;
+                } else if (found == index_cap) {
+                    hdr->cap_next_off = kept;
                 }
                 found += 1;
                 appended = true;
@@ -600,18 +605,20 @@ HBS_D TailOut tail_fixup(RunHeader* hdr, hbs_nal_entry* index, uint64_t index_ca
     return ret;
 }
 
-/* rbsp_len of NAL k from the packed arena offsets (grid-stride over NALs); found / final_kept: the finished run's */
-HBS_D void fill_rbsp_len_v(hbs_nal_entry* index, uint64_t index_cap, uint64_t k, uint64_t found, uint64_t final_kept)
+/* rbsp_len of NAL k from the packed arena offsets (grid-stride over NALs); found / final_kept: the finished run's; cap_next_off:
+ * RunHeader::cap_next_off, where NAL index_cap begins when the index has no room for it */
+HBS_D void fill_rbsp_len_v(hbs_nal_entry* index, uint64_t index_cap, uint64_t k, uint64_t found, uint64_t final_kept,
+                           uint64_t cap_next_off)
 {
     if (k >= found || k >= index_cap) return;
-    const uint64_t next = (k + 1 < found && k + 1 < index_cap) ? index[k + 1].rbsp_off : final_kept;
+    const uint64_t next = k + 1 >= found ? final_kept : k + 1 < index_cap ? index[k + 1].rbsp_off : cap_next_off;
     index[k].rbsp_len = (uint32_t)(next - index[k].rbsp_off);
     /* a rejected NAL reports no consumed size (h264_nal.c:158,166 return before :197) */
     if (index[k].status & HBS_ST_ERROR) index[k].status &= ~HBS_ST_TRAILING03;
 }
 HBS_D void fill_rbsp_len(const RunHeader* hdr, hbs_nal_entry* index, uint64_t index_cap, uint64_t k)
 {
-    fill_rbsp_len_v(index, index_cap, k, hdr->final_nals, hdr->final_kept);
+    fill_rbsp_len_v(index, index_cap, k, hdr->final_nals, hdr->final_kept, hdr->cap_next_off);
 }
 
 } // namespace hbs
