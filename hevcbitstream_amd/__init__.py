@@ -7,8 +7,12 @@ loading fails loudly when the library has not been built, and creating a
 context fails when there is no gfx950 GPU."""
 from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TRAILING03,  # noqa: F401
                   ST_UNTERMINATED, library_path, load_library, source_digest,
-                  NAL_FILTER, NALMASK_VCL, NALMASK_IRAP, NALMASK_PARAM_SETS, NALMASK_SEI, NALMASK_ALL)
+                  NAL_FILTER, NALMASK_VCL, NALMASK_IRAP, NALMASK_PARAM_SETS, NALMASK_SEI, NALMASK_ALL,
+                  ACCESS_UNIT, AU_CARRY, AU_IRAP, AU_IDR, AU_CVS_START, AU_ANCHOR, AU_NO_PICTURE, AU_DAMAGED,
+                  AU_PARAM_SETS, AU_END_OF_SEQ, AUKEEP_PARAM_SETS)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
            "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
-           "NAL_FILTER", "NALMASK_VCL", "NALMASK_IRAP", "NALMASK_PARAM_SETS", "NALMASK_SEI", "NALMASK_ALL"]
+           "NAL_FILTER", "NALMASK_VCL", "NALMASK_IRAP", "NALMASK_PARAM_SETS", "NALMASK_SEI", "NALMASK_ALL",
+           "ACCESS_UNIT", "AU_CARRY", "AU_IRAP", "AU_IDR", "AU_CVS_START", "AU_ANCHOR", "AU_NO_PICTURE", "AU_DAMAGED",
+           "AU_PARAM_SETS", "AU_END_OF_SEQ", "AUKEEP_PARAM_SETS"]

@@ -21,6 +21,13 @@ NALMASK_IRAP = 0x0000000000FF0000           # types 16..23
 NALMASK_PARAM_SETS = 0x0000000700000000     # types 32..34
 NALMASK_SEI = 0x0000018000000000            # types 39, 40
 NALMASK_ALL = 0xFFFFFFFFFFFFFFFF
+# layout of hbs_access_unit / hbs_au_carry and the flags of hbs_access_units / hbs_au_keep
+ACCESS_UNIT = np.dtype([("first_nal", "<u8"), ("unit_begin", "<u8"), ("unit_end", "<u8"), ("nal_count", "<u4"), ("vcl_count", "<u4"),
+                        ("first_vcl", "<u4"), ("nal_unit_type", "<i4"), ("temporal_id_plus1", "<i4"), ("pic_order_cnt", "<i4"),
+                        ("poc_lsb", "<i4"), ("slice_types", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+AU_CARRY = np.dtype([("flags", "<u4"), ("anchor_poc_lsb", "<i4"), ("anchor_poc_msb", "<i4"), ("reserved", "<u4")])
+AU_IRAP, AU_IDR, AU_CVS_START, AU_ANCHOR, AU_NO_PICTURE, AU_DAMAGED, AU_PARAM_SETS, AU_END_OF_SEQ = 1, 2, 4, 8, 16, 32, 64, 128
+AUKEEP_PARAM_SETS = 1
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -47,7 +54,7 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_ctx_set_sequential_parse", "hbs_ctx_set_emit_path", "hbs_parse_extended",
            "hbs_comm_unique_id", "hbs_comm_create", "hbs_comm_adopt", "hbs_comm_destroy", "hbs_comm_rank", "hbs_comm_world", "hbs_comm_reserve_hint", "hbs_parse_headers_compact", "hbs_parse_materialize", "hbs_index_parse_compact", "hbs_gather_parts", "hbs_index_parse", "hbs_ctx_reserve_workgroups",
            "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
-           "hbs_filter_annexb"]
+           "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -171,6 +178,11 @@ def load_library():
     lib.hbs_ctx_last_emit_by_tiles.argtypes = [C.c_void_p]
     lib.hbs_filter_annexb.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.hbs_access_units.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hbs_au_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+    lib.hbs_au_sps_poc_offset.argtypes = []
+    lib.hbs_au_sps_poc_offset.restype = C.c_uint64
     _lib = lib
     return lib
 
@@ -656,3 +668,56 @@ class Context:
             raise HbsError("hbs_filter_annexb: error %d" % int(s["error"]))
         kept = int(s["nal_count"])
         return out[:need], d_out_idx[: kept * NAL_ENTRY.itemsize].cpu().numpy().view(NAL_ENTRY).copy(), s
+
+    # ---- access units -----------------------------------------------------------------
+
+    def access_units_async(self, index, parsed, compact, structs, n_nals, au, au_cap, nal_au, carry_out, summary, carry=None):
+        """Enqueue hbs_access_units on the current torch stream.  index / parsed / compact / structs / au / nal_au / carry_out /
+        summary are device tensors (structs, nal_au, carry_out may be None; au None: plan only); carry is an ndarray[AU_CARRY]
+        of one (host memory) or None.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if carry is not None:
+            carry = np.ascontiguousarray(carry, dtype=AU_CARRY)
+        return self.lib.hbs_access_units(self.h, p(index), p(parsed), p(compact), p(structs), int(n_nals),
+                                         carry.ctypes.data_as(C.c_void_p) if carry is not None else None,
+                                         p(au), int(au_cap), p(nal_au), p(carry_out), p(summary))
+
+    def access_units(self, index, parsed, compact, structs, n_nals, carry=None):
+        """Plan, allocate, run.  index / parsed / compact: device uint8 tensors of the records (or host ndarrays of them),
+        structs: the struct arena (device tensor) or None.  Returns (au ndarray[ACCESS_UNIT], nal_au ndarray[uint32],
+        summary record, carry_out ndarray[AU_CARRY] of one)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x):
+            if isinstance(x, np.ndarray):
+                return t.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to(dev) if x.size else t.zeros(64, dtype=t.uint8, device=dev)
+            return x
+        index, parsed, compact = dv(index), dv(parsed), dv(compact)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.access_units_async(index, parsed, compact, structs, n_nals, None, 0, None, None, summary, carry), "hbs_access_units")
+        aus = int(self.read_summary(summary)["nal_count"])
+        au = t.empty(max(aus, 1) * ACCESS_UNIT.itemsize, dtype=t.uint8, device=dev)
+        nal_au = t.empty(max(n_nals, 1), dtype=t.int32, device=dev)
+        carry_out = t.zeros(AU_CARRY.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.access_units_async(index, parsed, compact, structs, n_nals, au, aus, nal_au, carry_out, summary, carry), "hbs_access_units")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_access_units: error %d" % int(s["error"]))
+        return (au[: aus * ACCESS_UNIT.itemsize].cpu().numpy().view(ACCESS_UNIT).copy(), nal_au[:n_nals].cpu().numpy().view(np.uint32).copy(),
+                s, carry_out.cpu().numpy().view(AU_CARRY).copy())
+
+    def au_keep_async(self, nal_au, parsed, n_nals, first_au, au_count, keep, param_sets=False):
+        """Enqueue hbs_au_keep: keep (device uint8 tensor of n_nals) becomes the mask hbs_filter_annexb takes as d_keep."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        self._check(self.lib.hbs_au_keep(self.h, p(nal_au), p(parsed), int(n_nals), int(first_au), int(au_count),
+                                         AUKEEP_PARAM_SETS if param_sets else 0, p(keep)), "hbs_au_keep")
+
+    def au_keep(self, nal_au, parsed, n_nals, first_au, au_count, param_sets=False):
+        """-> device uint8 tensor of n_nals: 1 for the NALs of AUs [first_au, first_au + au_count) (and the parameter sets in force)"""
+        t = self.torch
+        keep = t.empty(max(n_nals, 1), dtype=t.uint8, device=t.device("cuda", self.device))
+        self.au_keep_async(nal_au, parsed, n_nals, first_au, au_count, keep, param_sets)
+        return keep[:n_nals]

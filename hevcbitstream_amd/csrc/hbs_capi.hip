@@ -17,6 +17,7 @@
 #include "hbs_parse.h"
 #include "hbs_parse_compact.h"
 #include "hbs_filter.h"
+#include "hbs_au.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -58,6 +59,8 @@ struct hbs_ctx {
     void* ws2; uint64_t ws2_bytes;   /* hbs_index_parse: header windows and the index that points into them (alive across the parse, which carves ws) */
     uint8_t* zeros;              /* sizeof(hevc_sps_t) zero bytes: the "no parameter set yet" structs */
     void* fws; uint64_t fws_bytes;   /* hbs_filter_annexb's scratch: allocated on its first call, grow-only */
+    void* aws; uint64_t aws_bytes;   /* hbs_access_units' scratch, grow-only like fws.  hbs_au_keep uses its first 16 bytes (where hbs_access_units
+                                        keeps its digest): the calls of a context are ordered by its one stream, so neither sees the other's data */
     /* optional timing of the dominant kernel */
     int timing; hipEvent_t ev0, ev1; int ev_valid;        /* ev0 / ev1: the slot of the ring the last call used */
     hipEvent_t ring0[kTimingRing], ring1[kTimingRing];    /* event pairs of the last kTimingRing timed calls */
@@ -168,6 +171,7 @@ void hbs_ctx_destroy(hbs_ctx* c)
     if (c->emit_verdict) (void)hipFree(c->emit_verdict);
     if (c->ws2) (void)hipFree(c->ws2);
     if (c->fws) (void)hipFree(c->fws);
+    if (c->aws) (void)hipFree(c->aws);
     if (c->ring0[0]) for (int i = 0; i < kTimingRing; ++i) { (void)hipEventDestroy(c->ring0[i]); (void)hipEventDestroy(c->ring1[i]); }
     (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -372,7 +376,7 @@ uint64_t hbs_ctx_device_bytes(hbs_ctx* c)
 {
     if (!c) return 0;
     const uint64_t zb = c->zeros ? ((sizeof(hevc_sps_t) + 255) & ~(uint64_t)255) : 0;
-    return c->desc_tiles * 16 + sizeof(hbs::RunHeader) + hbs::scan4_tail_bytes() + c->ws_bytes + c->ws2_bytes + (c->ahead_tiles ? 64 + c->ahead_tiles * hbs::scan4_ahead_entry_bytes() : 0) + zb + c->fws_bytes;
+    return c->desc_tiles * 16 + sizeof(hbs::RunHeader) + hbs::scan4_tail_bytes() + c->ws_bytes + c->ws2_bytes + (c->ahead_tiles ? 64 + c->ahead_tiles * hbs::scan4_ahead_entry_bytes() : 0) + zb + c->fws_bytes + c->aws_bytes;
 }
 
 uint64_t hbs_workspace_bytes(uint64_t stream_bytes)
@@ -554,6 +558,81 @@ int hbs_filter_annexb(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes
     }
     const hipError_t e = hbs::launch_filter_annexb(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_filter_annexb");
+}
+
+namespace {
+int ensure_aws(hbs_ctx* c, uint64_t bytes)
+{
+    if (bytes > c->aws_bytes) {
+        if (c->aws) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->aws); c->aws = nullptr; c->aws_bytes = 0; }
+        hipError_t e = hipMalloc(&c->aws, bytes);
+        if (e != hipSuccess) return fail(c, e, "hipMalloc(access unit scratch)");
+        c->aws_bytes = bytes;
+    }
+    return 0;
+}
+} // namespace
+
+uint64_t hbs_au_sps_poc_offset(void) { return offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4); }
+
+int hbs_access_units(hbs_ctx* c, const hbs_nal_entry* d_index, const hbs_parsed_nal* d_parsed,
+                     const hbs_slice_compact* d_compact, const uint8_t* d_structs, uint64_t n_nals,
+                     const hbs_au_carry* initial, hbs_access_unit* d_au, uint64_t au_cap, uint32_t* d_nal_au,
+                     hbs_au_carry* d_carry_out, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_access_unit) == 64 && sizeof(hbs_au_carry) == 16, "hbs_access_unit / hbs_au_carry layout");
+    static_assert(sizeof(hbs_parsed_nal) == 32 && sizeof(hbs_slice_compact) == 64 && sizeof(hbs_nal_entry) == 32, "record layouts");
+    if (!c || !d_summary || n_nals > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_nals && (!d_index || !d_parsed || !d_compact)) return HBS_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_index) & 15) || (reinterpret_cast<uintptr_t>(d_parsed) & 15) || (reinterpret_cast<uintptr_t>(d_compact) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_au) & 15) || (reinterpret_cast<uintptr_t>(d_nal_au) & 3) || (reinterpret_cast<uintptr_t>(d_carry_out) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_structs) & 3)) {
+        snprintf(c->err, sizeof(c->err), "index / parsed / compact / au pointers must be 16-byte aligned");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    const hbs::AuScratch as = hbs::au_scratch(n_nals);
+    const int rc = ensure_aws(c, as.total);
+    if (rc) return rc;
+    uint8_t* w = static_cast<uint8_t*>(c->aws);
+    hbs::AuArgs a;
+    memset(&a, 0, sizeof(a));
+    a.index = d_index; a.parsed = d_parsed; a.compact = d_compact; a.structs = d_structs;
+    a.n_nals = n_nals; a.sps_off = hbs_au_sps_poc_offset();
+    if (initial) a.initial = *initial;
+    a.au = d_au; a.au_cap = au_cap; a.nal_au = d_au ? d_nal_au : nullptr; a.carry_out = d_carry_out; a.summary = d_summary;
+    a.digest = reinterpret_cast<hbs::AuDigest*>(w + as.digest);
+    a.part1 = reinterpret_cast<uint32_t*>(w + as.part1);
+    a.part2 = reinterpret_cast<uint32_t*>(w + as.part2);
+    a.part3 = reinterpret_cast<uint32_t*>(w + as.part3);
+    a.lead = reinterpret_cast<uint32_t*>(w + as.lead);
+    a.ctl = reinterpret_cast<uint32_t*>(w + as.ctl);
+    if (c->timing) {                                          /* this call's slot of the ring: all of its kernels */
+        const int slot = (int)(c->timed_calls % kTimingRing);
+        c->ev0 = c->ring0[slot]; c->ev1 = c->ring1[slot];
+        c->timed_calls += 1;
+        a.ev_begin = c->ev0; a.ev_end = c->ev1;
+        c->ev_valid = 1;
+    }
+    const hipError_t e = hbs::launch_access_units(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_access_units");
+}
+
+int hbs_au_keep(hbs_ctx* c, const uint32_t* d_nal_au, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
+                uint64_t first_au, uint64_t au_count, int flags, uint8_t* d_keep)
+{
+    if (!c || n_nals > 0xFFFFFFFFull || (flags & ~HBS_AUKEEP_PARAM_SETS)) return HBS_E_ARG;
+    if (n_nals && (!d_nal_au || !d_parsed || !d_keep)) return HBS_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_nal_au) & 3) || (reinterpret_cast<uintptr_t>(d_parsed) & 7)) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    const int rc = ensure_aws(c, 256);
+    if (rc) return rc;
+    hbs::AuKeepArgs a;
+    a.nal_au = d_nal_au; a.parsed = d_parsed; a.n_nals = n_nals; a.first_au = first_au; a.au_count = au_count; a.flags = flags;
+    a.keep = d_keep;
+    a.sets = reinterpret_cast<uint32_t*>(c->aws);
+    const hipError_t e = hbs::launch_au_keep(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_au_keep");
 }
 
 int hbs_synth_rbsp(hbs_ctx* c, uint64_t seed, uint64_t n_nals, int mode,

@@ -631,7 +631,7 @@ class Synth:
         n += sum(1 for u in lt_used_flags if u)
         return n
 
-    def slice_nal(self, nal_type, first=True, payload=b"", slice_type=None, address=0, tid=1, pps_id=0):
+    def slice_nal(self, nal_type, first=True, payload=b"", slice_type=None, address=0, tid=1, pps_id=0, poc_lsb=None):
         s, p = self.sps, self.pps
         w = BitWriter()
         w.u1(1 if first else 0)
@@ -663,7 +663,10 @@ class Synth:
             lt_used_flags = []
             tmvp_slice = 0
             if not idr:
-                w.u(s["poc_bits"], self.ri(0, (1 << s["poc_bits"]) - 1))
+                lsb = self.ri(0, (1 << s["poc_bits"]) - 1)
+                if poc_lsb is not None:             # overrides the value behind the draw: the streams of every other caller stay as they were
+                    lsb = int(poc_lsb) & ((1 << s["poc_bits"]) - 1)
+                w.u(s["poc_bits"], lsb)
                 sps_flag = 1 if (s["num_sets"] > 0 and self.rng.rand() < 0.6) else 0
                 w.u1(sps_flag)
                 if not sps_flag:

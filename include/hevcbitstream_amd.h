@@ -420,6 +420,103 @@ int hbs_index_parse_compact(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stre
                     hbs_parsed_nal* d_parsed, hbs_slice_compact* d_compact, uint8_t* d_structs, uint64_t structs_cap, uint64_t* d_payload_off,
                     hbs_summary* d_scan_summary, hbs_summary* d_parse_summary, uint64_t* nal_count_out);
 
+/*
+ * ---- access units ------------------------------------------------------------------------------------------------
+ * hbs_access_units groups the NALs of an indexed and parsed stream into access units (AUs: one coded picture of layer 0
+ * with the NALs that belong to it, H.265 7.4.2.4.4) and gives every picture its PicOrderCntVal (8.3.1), on the device.
+ * The inputs are what hbs_parse_headers_compact / hbs_parse_materialize / hbs_index_parse_compact wrote, untouched:
+ * d_index, d_parsed, d_compact (n_nals records each, 16-byte aligned) and the struct arena d_structs (may be NULL: every
+ * SPS then counts as "without a struct").  The fields are taken as the parse writes them (nal_unit_type -1..63, anything
+ * else counts as -1; nuh_temporal_id_plus1 0..7); nothing is checked against the stream.  This comment is the specification;
+ * tests/_au_ref.py restates it as one loop over the NALs and one over the pictures.
+ *
+ * Grouping (layer 0 only; NAL types are looked at whatever the layer unless said otherwise).
+ *   VCL(k):   nal_unit_type 0..31 and nuh_layer_id 0.
+ *   FIRST(k): VCL(k) and d_compact[k].first_slice_segment_in_pic_flag != 0.
+ *   CAND(k):  FIRST(k), or nuh_layer_id 0 and type in {32, 33, 34, 35, 39, 41..44, 48..55}.
+ *   NAL k starts an AU iff k == 0, or CAND(k) and no CAND NAL lies strictly between the last VCL NAL in front of k and k
+ *   (with v(k) / c(k) = the number of the last VCL / CAND NAL < k, -1 for none: CAND(k) && c(k) <= v(k)).  Every other
+ *   NAL -- suffix SEI, EOS, filler, NALs of other layers, NALs of type -1, slice segments that continue a picture --
+ *   belongs to the AU in progress.  The picture NAL of an AU is its first VCL NAL; an AU without one has
+ *   HBS_AU_NO_PICTURE (a batch without any VCL NAL is one such AU).
+ *
+ * Picture order count, over the pictures (AUs with a picture NAL) in stream order.
+ *   Max(p) = 1 << (4 + clamp(v, 0, 12)), v = log2_max_pic_order_cnt_lsb_minus4 of the last SPS NAL (type 33, any layer) in
+ *   front of the picture NAL whose struct_off != ~0, read at d_structs + struct_off + hbs_au_sps_poc_offset() (struct_off
+ *   is a multiple of 4); none in front in THIS call: v = 0, the parser's all-zero set.  The carry holds no SPS: a batch
+ *   that continues another one must begin with (a copy of) the SPS in force if its first pictures are to use it.
+ *   A(p) = the nearest picture in front of p with HBS_AU_ANCHOR, else the carry's anchor, else lsb 0, msb 0.
+ *   With prev = lsb(A(p)) and lsb = poc_lsb(p) = d_compact[picture NAL].slice_pic_order_cnt_lsb:
+ *     d(p) = +Max(p) if lsb < prev && prev - lsb >= Max(p) / 2;  -Max(p) if lsb > prev && lsb - prev > Max(p) / 2;  else 0
+ *     msb(p) = 0 if p has HBS_AU_CVS_START, else msb(A(p)) + d(p);   pic_order_cnt = msb(p) + lsb
+ *   in 32-bit wrap-around arithmetic.  Out-of-spec input (an IRAP with temporal id > 0, Max changing inside a CVS, any
+ *   lsb) has no special case: these formulas are the definition.
+ *
+ * d_summary: nal_count = AUs, nal_found = n_nals, reserved[0] = pictures, reserved[1] = AUs with HBS_AU_CVS_START,
+ * stream_bytes = unit_end of the last AU, rbsp_bytes = 0, stop_reason = 0, error = HBS_E_CAPACITY when au_cap < AUs (then
+ * nothing is written to d_au, d_nal_au, d_carry_out; the counts are still right).  d_au == NULL: plan only (the summary
+ * alone is written).  n_nals == 0 is valid: no AU, the carry passes through.  n_nals > 2^32 - 1, a missing or misaligned
+ * pointer: HBS_E_ARG at once, nothing touched.  `initial` (HOST pointer; NULL: the start of a stream) is the d_carry_out
+ * of the batch in front; a continuing batch is expected to begin at an AU boundary (NAL 0 always starts an AU), and with a
+ * carry "the first picture of the call" reads "no picture seen yet".  Nothing is stored outside d_au[0, AUs),
+ * d_nal_au[0, n_nals), the carry and the summary; no load goes past n_nals records or, in d_structs, outside the word named.
+ */
+typedef struct hbs_access_unit {      /* 64 bytes */
+    uint64_t first_nal;               /* number of the AU's first NAL                                              */
+    uint64_t unit_begin;              /* stream offset where that NAL's unit begins: index[first_nal-1].end, 0 for NAL 0
+                                         (the filter's definition of a unit)                                       */
+    uint64_t unit_end;                /* index[last NAL of the AU].end                                             */
+    uint32_t nal_count;               /* NALs in the AU                                                            */
+    uint32_t vcl_count;               /* of them VCL NALs (type < 32) with nuh_layer_id 0                          */
+    uint32_t first_vcl;               /* the picture NAL: first such VCL NAL, relative to first_nal; ~0u: none     */
+    int32_t  nal_unit_type;           /* of the picture NAL (-1: none)                                             */
+    int32_t  temporal_id_plus1;       /* of the picture NAL (0: none)                                              */
+    int32_t  pic_order_cnt;           /* PicOrderCntVal (8.3.1), two's-complement wrap-around; 0 without a picture */
+    int32_t  poc_lsb;                 /* slice_pic_order_cnt_lsb of the picture NAL as the parse reports it        */
+    uint32_t slice_types;             /* bit t set: a VCL NAL of the AU with dependent_slice_segment_flag == 0 has
+                                         slice_type t (0..2), both as d_compact reports them                       */
+    uint32_t flags;                   /* HBS_AU_*                                                                  */
+    uint32_t reserved;                /* 0                                                                         */
+} hbs_access_unit;
+
+#define HBS_AU_IRAP        1   /* picture NAL type 16..23                                                     */
+#define HBS_AU_IDR         2   /* 19, 20                                                                      */
+#define HBS_AU_CVS_START   4   /* IRAP with NoRaslOutputFlag = 1: IDR, BLA (16..18), or a CRA / reserved IRAP
+                                  (21..23) that is the first picture of the call (no carry) or the first picture
+                                  behind an end-of-sequence NAL (type 36)                                     */
+#define HBS_AU_ANCHOR      8   /* may serve as prevTid0Pic: temporal_id_plus1 == 1, type not 6..9 (RADL, RASL)
+                                  and not a sub-layer non-reference picture (even types 0..14)                */
+#define HBS_AU_NO_PICTURE 16   /* no VCL NAL with layer 0                                                     */
+#define HBS_AU_DAMAGED    32   /* holds a NAL whose d_parsed rc < 0 and whose type is not one of the types
+                                  read_hevc_nal_unit never reads (35..40, 41..47, 48..63), or nal_unit_type -1 */
+#define HBS_AU_PARAM_SETS 64   /* holds a VPS, SPS or PPS                                                     */
+#define HBS_AU_END_OF_SEQ 128  /* holds an end-of-sequence (36) or end-of-bitstream (37) NAL                  */
+
+typedef struct hbs_au_carry {         /* 16 bytes: the state behind a batch, for the batch that continues it */
+    uint32_t flags;                   /* 1: a picture was seen, 2: an anchor exists, 4: an EOS NAL is pending */
+    int32_t  anchor_poc_lsb, anchor_poc_msb;
+    uint32_t reserved;
+} hbs_au_carry;
+
+int hbs_access_units(hbs_ctx* ctx, const hbs_nal_entry* d_index, const hbs_parsed_nal* d_parsed,
+                     const hbs_slice_compact* d_compact, const uint8_t* d_structs, uint64_t n_nals,
+                     const hbs_au_carry* initial /* HOST pointer, NULL: start of a stream */,
+                     hbs_access_unit* d_au, uint64_t au_cap, uint32_t* d_nal_au /* optional: AU number per NAL */,
+                     hbs_au_carry* d_carry_out /* optional, device */, hbs_summary* d_summary);
+uint64_t hbs_au_sps_poc_offset(void);   /* offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4), like hbs_sps_tables_offset() */
+
+/*
+ * From a range of access units to the keep mask of hbs_filter_annexb(..., rule = NULL, d_keep, ...):
+ * d_keep[k] = 1 iff first_au <= d_nal_au[k] < first_au + au_count, else 0.  With HBS_AUKEEP_PARAM_SETS additionally 1 for
+ * the last VPS (32), the last SPS (33) and the last PPS (34) NAL (any layer), each with d_parsed rc >= 0, in front of the
+ * first NAL of AU first_au -- the library's own model of "the sets in force": the last of each kind, ids ignored.  An empty
+ * range (au_count 0, or first_au past the last AU) is all zeros, parameter sets included; a range that ends past the last
+ * AU is clipped.  d_nal_au is what hbs_access_units wrote for the same n_nals.
+ */
+#define HBS_AUKEEP_PARAM_SETS 1
+int hbs_au_keep(hbs_ctx* ctx, const uint32_t* d_nal_au, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
+                uint64_t first_au, uint64_t au_count, int flags, uint8_t* d_keep /* n_nals bytes */);
+
 /* Same, for a batch that continues an earlier one: d_initial_sps_slot (an SPS
  * slot = hevc_sps_t followed at hbs_sps_tables_offset() by its derived RPS
  * tables, hbs_sps_slot_bytes() in all) and d_initial_pps (hevc_pps_t) are the

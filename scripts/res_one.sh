@@ -11,5 +11,5 @@ hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Ihevcbitstream_amd/c
     /Occupancy/     { o=$0; sub(/.*SIMD\]: /,"",o); sub(/ .*/,"",o) }
     /SGPRs Spill:/  { ss=$0; sub(/.*Spill: /,"",ss); sub(/ .*/,"",ss) }
     /VGPRs Spill:/  { vs=$0; sub(/.*Spill: /,"",vs); sub(/ .*/,"",vs) }
-    /LDS Size/      { lds=$0; sub(/.*block\]: /,"",lds); sub(/ .*/,"",lds); cmd="echo " name " | c++filt"; cmd | getline dn; close(cmd); sub(/\(.*/,"",dn); sub(/^void /,"",dn);
+    /LDS Size/      { lds=$0; sub(/.*block\]: /,"",lds); sub(/ .*/,"",lds); cmd="echo " name " | c++filt"; cmd | getline dn; close(cmd); gsub(/\(anonymous namespace\)::/,"",dn); sub(/\(.*/,"",dn); sub(/^void /,"",dn);
                       printf "%-48s VGPR %4s SGPR %4s vsp %3s ssp %4s scratch %4s occ %2s lds %6s\n", substr(dn,1,48), v, sg, vs, ss, s, o, lds }'
