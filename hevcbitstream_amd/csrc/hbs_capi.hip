@@ -825,6 +825,8 @@ static int index_parse_impl(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream
     if (!c || !d_scan_summary || !d_parse_summary || !d_index || !index_cap || !d_parsed) return HBS_E_ARG;
     if (header_window == 0) header_window = 512;
     if (header_window < 64 || header_window > (1u << 16) || (header_window & 15u)) return HBS_E_ARG;
+    /* what the parse behind the scan would refuse is refused here, before the scan has written the index and its summary */
+    if (reinterpret_cast<uintptr_t>(d_structs) & 15) return HBS_E_ARG;
     /* 1. find_nal_unit over the stream: no arena */
     int rc = hbs_index_extract(c, d_stream, stream_bytes, d_index, index_cap, nullptr, 0, d_scan_summary);
     if (rc) return rc;

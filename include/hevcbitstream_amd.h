@@ -25,7 +25,12 @@
  *                       8(d) (no reference counterpart: it ships no streams)
  *
  * All `d_` pointers are DEVICE pointers of the context's GPU (hipMalloc'ed or
- * torch-allocated), 16-byte aligned.  Calls enqueue work on the context's HIP
+ * torch-allocated), 16-byte aligned -- anywhere inside an allocation: a buffer
+ * need not begin one, nothing in front of or behind a buffer is written, and no
+ * byte outside an input decides a result.  Where an entry point takes less it
+ * says so ("Alignment:" in its comment; tests/test_gpu_carved.py runs each call
+ * at every alignment stated); a pointer below the stated alignment is refused
+ * with HBS_E_ARG before anything is written.  Calls enqueue work on the context's HIP
  * stream and return without synchronising unless stated otherwise.  Return
  * value: 0 on success, a negative HBS_E_* code otherwise.  There is no CPU
  * fallback: without a usable gfx950 device every call fails with
@@ -187,6 +192,7 @@ const char* hbs_version(void);
  *     bytes (the reference leaves its output unspecified there);
  *   - bytes past the end of the stream are taken as 0xFF where the reference
  *     reads them unchecked (h264_nal.c:47-48, 65-66).
+ * Alignment: d_stream, d_rbsp, d_summary 16 bytes; d_index 8 bytes.
  */
 int hbs_index_extract(hbs_ctx* ctx,
                       const uint8_t* d_stream, uint64_t stream_bytes,
@@ -246,6 +252,7 @@ int hbs_ctx_set_ingest_window_max(hbs_ctx* ctx, uint64_t max_window_bytes /* 0: 
  * for byte when every NAL was accepted (no HBS_ST_ERROR), none ended in
  * 00 00 03 (HBS_ST_TRAILING03: the reference drops that byte for good), the
  * bytes between NALs were zeros + 01, and the stream ends with its last NAL.
+ * Alignment: d_rbsp and d_out any byte; d_index_in, d_index_out 8 bytes; d_summary 16 bytes.
  */
 int hbs_emit_annexb(hbs_ctx* ctx, const uint8_t* d_rbsp, uint64_t rbsp_bytes,
                     const hbs_nal_entry* d_index_in, uint64_t n_nals, int gap_mode,
@@ -281,6 +288,7 @@ uint64_t hbs_annexb_bound_gaps(uint64_t rbsp_bytes, uint64_t n_nals, uint64_t ga
  * out_cap is smaller than the output; in both cases nothing is written to d_out or d_index_out.  n_nals = 0 is valid (empty
  * output).  Nothing outside [d_out, d_out + output bytes) is stored, and no load touches a 16-byte granule that holds no byte
  * of the stream.  Returns HBS_E_ARG at once on bad arguments (both or neither of rule / d_keep, misaligned pointers).
+ * Alignment: d_stream, d_out, d_summary 16 bytes; d_index, d_index_out 8 bytes; d_keep any byte.
  */
 typedef struct hbs_nal_filter {
     uint64_t keep_types;             /* bit t set: NAL units with nal_unit_type t pass                                   */
@@ -409,6 +417,8 @@ int hbs_parse_extended(hbs_ctx* ctx, const uint8_t* d_rbsp, const hbs_nal_entry*
  * call again with a larger window, or take the arena path.  The call waits once, for the scan's NAL count (returned in
  * *nal_count_out when not NULL); the parse is enqueued behind it.  On the 2.1 GiB 4K30 sequence of bench.py: scan 1 B/B
  * + ~3 % for the windows, against 2 B/B for the arena.
+ * Alignment: d_stream, d_parsed, d_structs, both summaries 16 bytes; d_index, d_payload_off 8 bytes.  A misaligned d_structs
+ * is refused before the scan runs: no output is written.
  */
 int hbs_index_parse(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
                     hbs_nal_entry* d_index, uint64_t index_cap, uint32_t header_window,
@@ -503,6 +513,7 @@ int hbs_access_units(hbs_ctx* ctx, const hbs_nal_entry* d_index, const hbs_parse
                      const hbs_au_carry* initial /* HOST pointer, NULL: start of a stream */,
                      hbs_access_unit* d_au, uint64_t au_cap, uint32_t* d_nal_au /* optional: AU number per NAL */,
                      hbs_au_carry* d_carry_out /* optional, device */, hbs_summary* d_summary);
+/* Alignment: d_index, d_parsed, d_compact, d_au, d_summary 16 bytes; d_structs, d_nal_au, d_carry_out 4 bytes. */
 uint64_t hbs_au_sps_poc_offset(void);   /* offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4), like hbs_sps_tables_offset() */
 
 /*
@@ -512,6 +523,7 @@ uint64_t hbs_au_sps_poc_offset(void);   /* offsetof(hevc_sps_t, log2_max_pic_ord
  * first NAL of AU first_au -- the library's own model of "the sets in force": the last of each kind, ids ignored.  An empty
  * range (au_count 0, or first_au past the last AU) is all zeros, parameter sets included; a range that ends past the last
  * AU is clipped.  d_nal_au is what hbs_access_units wrote for the same n_nals.
+ * Alignment: d_nal_au 4 bytes; d_parsed 8 bytes; d_keep any byte.
  */
 #define HBS_AUKEEP_PARAM_SETS 1
 int hbs_au_keep(hbs_ctx* ctx, const uint32_t* d_nal_au, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
