@@ -114,7 +114,7 @@ struct AuArgs {
     uint64_t n_nals, sps_off;
     hbs_au_carry initial;
     hbs_access_unit* au; uint64_t au_cap; uint32_t* nal_au; hbs_au_carry* carry_out; hbs_summary* summary;
-    /* scratch (au_scratch) */
+    /* scratch (lay_access_units) */
     AuDigest* digest;               /* n_nals                                                                   */
     uint32_t* part1;                /* 8 per block: last VCL, CAND, EOS, SPS with a slot (number + 1), VCL NALs  */
     uint32_t* part2;                /* 8 per block: AU starts, pictures, last start, last picture, last anchor   */
@@ -123,20 +123,16 @@ struct AuArgs {
     uint32_t* ctl;                  /* 64: error, totals                                                         */
     hipEvent_t ev_begin, ev_end;
 };
-struct AuScratch { uint64_t digest, part1, part2, part3, lead, ctl, total; };
-inline AuScratch au_scratch(uint64_t n_nals)
+/* the scratch the call needs, sized by a.n_nals */
+inline void lay_access_units(Carver& w, AuArgs& a)
 {
-    auto r256 = [](uint64_t v) { return (v + 255) & ~255ull; };
-    const uint64_t blocks = (n_nals + kAuNalsPerBlock - 1) / kAuNalsPerBlock;
-    AuScratch s;
-    s.digest = 0;
-    s.part1 = r256(n_nals * sizeof(AuDigest));
-    s.part2 = s.part1 + r256(blocks * 32);
-    s.part3 = s.part2 + r256(blocks * 32);
-    s.lead = s.part3 + r256(blocks * 32);
-    s.ctl = s.lead + r256(blocks * 32);
-    s.total = s.ctl + 256;
-    return s;
+    const uint64_t blocks = (a.n_nals + kAuNalsPerBlock - 1) / kAuNalsPerBlock;
+    a.digest = w.take<AuDigest>(a.n_nals * sizeof(AuDigest));
+    a.part1 = w.take<uint32_t>(blocks * 32);
+    a.part2 = w.take<uint32_t>(blocks * 32);
+    a.part3 = w.take<uint32_t>(blocks * 32);
+    a.lead = w.take<uint32_t>(blocks * 32);
+    a.ctl = w.take<uint32_t>(256);
 }
 hipError_t launch_access_units(const AuArgs& a, hipStream_t st);
 

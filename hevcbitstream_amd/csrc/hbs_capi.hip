@@ -1,6 +1,6 @@
 /*
  * hbs_capi.hip -- the extern "C" boundary (include/hevcbitstream_amd.h).
- * Thin: owns the per-GPU context (HIP stream, look-back workspace) and turns
+ * Thin: owns the per-GPU context (HIP stream, grow-only scratch) and turns
  * each call into kernel launches.  No CPU implementation of any entry point
  * exists here: without a gfx950 device the context cannot be created.
  */
@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include "hbs_scan.h"
 #include "hbs_emit_launch.h"
@@ -21,16 +22,26 @@
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
+struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow) */
+/* The scratch hbs_ctx_device_bytes counts, each allocated by the first call that needs it:
+ * kDesc   look-back words, two per 64 KiB tile of the stream
+ * kWs     K3 / generator / parse workspace; the index-only kernels' tile aggregates and elements
+ * kAhead  K12's dense tiles counted ahead (streams from 3 GiB up), laid out for ahead_tiles tiles
+ * kWs2    hbs_index_parse: header windows and the index that points into them (alive across the parse, which carves kWs)
+ * kZeros  sizeof(hevc_sps_t) zero bytes: the "no parameter set yet" structs
+ * kFws    hbs_filter_annexb's scratch
+ * kAws    hbs_access_units' scratch.  hbs_au_keep uses its first 16 bytes (where hbs_access_units keeps its digest): the calls
+ *         of a context are ordered by its one stream, so neither sees the other's data */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kBufs };
+/* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
+struct Grid { int blocks, full, per_cu; };
+
 struct hbs_ctx {
     int device;
     int cus;                            /* compute units of `device` */
     hipStream_t own_stream;
     hipStream_t stream;
-    int grid_blocks;
-    int blocks_per_cu;
-    int grid_blocks4, blocks_per_cu4;   /* event-sparse kernel */
-    int grid_blocks6, grid_full6, blocks_per_cu6;   /* ... its 24-row geometry (variant 6) */
-    int grid_full, grid_full4;          /* ... what the GPU holds; grid_blocks / grid_blocks4 may be cut (hbs_ctx_reserve_workgroups) */
+    Grid grid, grid4, grid6;            /* LDS-image kernel, event-sparse kernel, its 24-row geometry (variant 6) */
     int grid_env, spare_wgs;            /* HBS_GRID_BLOCKS (0: unset); workgroup slots left free for other streams' kernels */
     int exclusive;                      /* hbs_ctx_set_device_exclusive: no other persistent kernel shares the device */
     int variant;                  /* 0 = automatic */
@@ -47,20 +58,12 @@ struct hbs_ctx {
     int emit_path_set;                /* hbs_ctx_set_emit_path was called: the environment no longer decides */
     const uint32_t* last_emit_tflag;  /* the last hbs_emit_annexb's verdict words: a COPY in emit_verdict (the words themselves live in the shared
                                          workspace, which the next call of any kind overwrites or reallocates); null: no verdict (small path) */
-    uint32_t* emit_verdict;           /* 16 bytes of device memory owned by the context */
+    Buf emit_verdict;                 /* 16 bytes of device memory owned by the context (hbs_ctx_device_bytes never counted them) */
     uint32_t emit_calls;              /* hbs_emit_annexb calls so far: stamps the dense tiles counted ahead (never 0) */
-    unsigned long long* desc;
-    uint64_t desc_tiles;
     hbs::RunHeader* hdr;
     uint8_t* tail;                      /* padded copy of the stream's last tile (event-sparse kernel) */
-    /* K3 / generator workspace */
-    void* ws; uint64_t ws_bytes;
-    void* ahead; uint64_t ahead_tiles;   /* K12's dense tiles counted ahead: a table entry and a byte per 192 KiB tile (streams from 3 GiB up) */
-    void* ws2; uint64_t ws2_bytes;   /* hbs_index_parse: header windows and the index that points into them (alive across the parse, which carves ws) */
-    uint8_t* zeros;              /* sizeof(hevc_sps_t) zero bytes: the "no parameter set yet" structs */
-    void* fws; uint64_t fws_bytes;   /* hbs_filter_annexb's scratch: allocated on its first call, grow-only */
-    void* aws; uint64_t aws_bytes;   /* hbs_access_units' scratch, grow-only like fws.  hbs_au_keep uses its first 16 bytes (where hbs_access_units
-                                        keeps its digest): the calls of a context are ordered by its one stream, so neither sees the other's data */
+    Buf buf[kBufs];
+    uint64_t ahead_tiles;               /* 192 KiB tiles buf[kAhead] is laid out for */
     /* optional timing of the dominant kernel */
     int timing; hipEvent_t ev0, ev1; int ev_valid;        /* ev0 / ev1: the slot of the ring the last call used */
     hipEvent_t ring0[kTimingRing], ring1[kTimingRing];    /* event pairs of the last kTimingRing timed calls */
@@ -76,30 +79,132 @@ int fail(hbs_ctx* c, hipError_t e, const char* what)
     return HBS_E_HIP;
 }
 
-int ensure_workspace(hbs_ctx* c, uint64_t stream_bytes)
+bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+/* makes `b` hold `bytes` at least.  1: it grew (what it held is gone), 0: it was large enough, < 0: the call's return code */
+int grow(hbs_ctx* c, Buf& b, uint64_t bytes, const char* what)
 {
-    const uint64_t tiles = (stream_bytes + hbs::kTileBytes - 1) / hbs::kTileBytes + 1;
-    if (tiles > c->desc_tiles) {
-        if (c->desc) { (void)hipFree(c->desc); c->desc = nullptr; c->desc_tiles = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->desc), tiles * 16);
-        if (e != hipSuccess) return fail(c, e, "hipMalloc(look-back descriptors)");
-        c->desc_tiles = tiles;
-    }
-    return 0;
+    if (bytes <= b.bytes) return 0;
+    if (b.ptr) { (void)hipStreamSynchronize(c->stream); (void)hipFree(b.ptr); b.ptr = nullptr; b.bytes = 0; }
+    const hipError_t e = hipMalloc(&b.ptr, bytes);
+    if (e != hipSuccess) return fail(c, e, what);
+    b.bytes = bytes;
+    return 1;
 }
 
-int ensure_ws(hbs_ctx* c, uint64_t bytes)
+/* a call's workspace in `b`: `lay` fills the call's *Args through the cursor, once to learn the size and again on `b` grown to
+ * it.  Returns as grow does. */
+template <class Lay> int carve(hbs_ctx* c, Buf& b, const char* what, Lay lay)
 {
-    if (bytes > c->ws_bytes) {
-        if (c->ws) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->ws); c->ws = nullptr; c->ws_bytes = 0; }
-        hipError_t e = hipMalloc(&c->ws, bytes);
-        if (e != hipSuccess) return fail(c, e, "hipMalloc(workspace)");
-        c->ws_bytes = bytes;
-    }
-    return 0;
+    hbs::Carver w{nullptr, 0};
+    lay(w);
+    const int rc = grow(c, b, w.at, what);
+    if (rc < 0) return rc;
+    w = hbs::Carver{static_cast<uint8_t*>(b.ptr), 0};
+    lay(w);
+    return rc;
 }
 
-uint64_t round256(uint64_t v) { return (v + 255) & ~255ull; }
+int ensure_zeros(hbs_ctx* c)
+{
+    const uint64_t zb = (sizeof(hevc_sps_t) + 255) & ~(uint64_t)255;
+    const int rc = grow(c, c->buf[kZeros], zb, "hipMalloc(zero structs)");
+    if (rc <= 0) return rc;
+    const hipError_t e = hipMemsetAsync(c->buf[kZeros].ptr, 0, zb, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "hipMemsetAsync(zero structs)");
+}
+
+/* the call takes its slot of the timing ring: the event pair around its kernels */
+void take_timing_slot(hbs_ctx* c, hipEvent_t* begin, hipEvent_t* end)
+{
+    const int slot = (int)(c->timed_calls % kTimingRing);
+    *begin = c->ev0 = c->ring0[slot]; *end = c->ev1 = c->ring1[slot];
+    c->timed_calls += 1;
+    c->ev_valid = 1;
+}
+
+/* what each scan kernel launches: what the GPU holds less the slots left free, under the HBS_GRID_BLOCKS debugging cap (a ceiling
+ * of its own: reserving workgroups never raises it) */
+void cut_grids(hbs_ctx* c)
+{
+    for (Grid* g : {&c->grid, &c->grid4, &c->grid6}) {
+        g->blocks = g->full - c->spare_wgs > 1 ? g->full - c->spare_wgs : 1;
+        if (c->grid_env > 0 && c->grid_env < g->blocks) g->blocks = c->grid_env;
+    }
+}
+
+int parse_impl(hbs_ctx* c, const uint8_t* d_rbsp, const hbs_nal_entry* d_index, uint64_t n_nals,
+               hbs_parsed_nal* d_parsed, uint8_t* d_structs, uint64_t structs_cap,
+               const uint8_t* d_initial_sps_slot, const uint8_t* d_initial_pps,
+               hbs_trace_rec* d_trace, uint32_t trace_cap, uint32_t* d_trace_count, hbs_summary* d_summary,
+               uint8_t* d_state_sps_slot, uint8_t* d_state_pps,
+               hbs_slice_compact* d_compact, const uint64_t* d_want, uint64_t n_want)
+{
+    static_assert(sizeof(hbs_slice_compact) == sizeof(hbs::SliceCompact), "public record == kernel record");
+    if ((d_state_sps_slot == nullptr) != (d_state_pps == nullptr)) return HBS_E_ARG;
+    if (d_state_sps_slot && (!d_structs || !n_nals)) return HBS_E_ARG;
+    static_assert(sizeof(hbs_trace_rec) == sizeof(hbs::TraceRec), "public record == kernel record");
+    static_assert(sizeof(hbs_parsed_nal) == sizeof(hbs::ParsedNal), "public record == kernel record");
+    if (!c || !d_summary || (n_nals && (!d_rbsp || !d_index || !d_parsed))) return HBS_E_ARG;
+    if (misaligned(d_structs, 15)) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    int rc = ensure_zeros(c);
+    if (rc) return rc;
+    hbs::ParseArgs a;
+    a.rbsp = d_rbsp; a.index = d_index; a.n = n_nals;
+    a.parsed = reinterpret_cast<hbs::ParsedNal*>(d_parsed);
+    a.structs = d_structs; a.structs_cap = d_structs ? structs_cap : 0; a.summary = d_summary;
+    a.zeros = static_cast<const uint8_t*>(c->buf[kZeros].ptr);
+    a.initial_sps_slot = d_initial_sps_slot;
+    a.initial_pps = d_initial_pps;
+    a.trace = reinterpret_cast<hbs::TraceRec*>(d_trace); a.trace_cap = trace_cap; a.trace_count = d_trace_count;
+    a.state_sps_slot_out = d_state_sps_slot; a.state_pps_out = d_state_pps;
+    a.compact = reinterpret_cast<hbs::SliceCompact*>(d_compact); a.want_list = d_want; a.want_n = d_compact ? n_want : 0;
+    a.sequential = (d_state_sps_slot || d_compact) ? 0 : c->parse_sequential;
+    rc = carve(c, c->buf[kWs], "hipMalloc(workspace)", [&](hbs::Carver& w) { hbs::lay_parse(w, a); });
+    if (rc < 0) return rc;
+    hipError_t e = hbs::launch_parse_headers(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_parse_headers");
+}
+
+int index_parse_impl(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                     hbs_nal_entry* d_index, uint64_t index_cap, uint32_t header_window,
+                     hbs_parsed_nal* d_parsed, hbs_slice_compact* d_compact, uint8_t* d_structs, uint64_t structs_cap, uint64_t* d_payload_off,
+                     hbs_summary* d_scan_summary, hbs_summary* d_parse_summary, uint64_t* nal_count_out)
+{
+    if (!c || !d_scan_summary || !d_parse_summary || !d_index || !index_cap || !d_parsed) return HBS_E_ARG;
+    if (header_window == 0) header_window = 512;
+    if (header_window < 64 || header_window > (1u << 16) || (header_window & 15u)) return HBS_E_ARG;
+    /* what the parse behind the scan would refuse is refused here, before the scan has written the index and its summary */
+    if (misaligned(d_structs, 15)) return HBS_E_ARG;
+    /* 1. find_nal_unit over the stream: no arena */
+    int rc = hbs_index_extract(c, d_stream, stream_bytes, d_index, index_cap, nullptr, 0, d_scan_summary);
+    if (rc) return rc;
+    /* the parse's launches are sized by the number of NALs: the one wait of the call */
+    hbs_summary s;
+    rc = hbs_read_summary(c, d_scan_summary, &s);
+    if (rc) return rc;
+    if (nal_count_out) *nal_count_out = s.nal_count;
+    if (s.error) return s.error;
+    const uint64_t nals = s.nal_count;
+    /* 2. the bytes the parse can look at, stripped into windows */
+    hbs::HdrWinArgs a;
+    /* everything below is sized by the NALs FOUND (known since the wait above), not by the caller's index capacity: a default
+     * capacity of stream_bytes / 64 entries would ask for 137 GB of windows on a 16 GiB stream (round 3's advice) */
+    const uint64_t slots = nals ? nals : 1;
+    a.stream = d_stream; a.index = d_index; a.nals = nals; a.index_cap = slots; a.window = header_window;
+    a.arena_bytes = hbs::hdrwin_arena_bytes(slots, header_window, stream_bytes);
+    rc = carve(c, c->buf[kWs2], "hipMalloc(header windows)", [&](hbs::Carver& w) { hbs::lay_hdrwin(w, a); });
+    if (rc < 0) return rc;
+    hipError_t e = hbs::launch_hdr_strip(a, c->stream);
+    if (e != hipSuccess) return fail(c, e, "launch_hdr_strip");
+    /* 3. K4 on the windows, 4. slice_data_size against the real lengths, windows that were too small reported */
+    rc = d_compact ? hbs_parse_headers_compact(c, a.arena, a.idx2, nals, d_parsed, d_compact, d_structs, structs_cap, nullptr, nullptr, d_parse_summary)
+                   : hbs_parse_headers(c, a.arena, a.idx2, nals, d_parsed, d_structs, structs_cap, d_parse_summary);
+    if (rc) return rc;
+    e = hbs::launch_hdr_fix(a, d_parsed, d_parse_summary, reinterpret_cast<unsigned long long*>(d_payload_off), c->stream, d_compact ? 1 : 0);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_hdr_fix");
+}
 
 } // namespace
 
@@ -128,52 +233,41 @@ int hbs_ctx_create(hbs_ctx** out, int device)
     memset(c, 0, sizeof(*c));
     c->device = device;
     c->cus = prop.multiProcessorCount;
-    hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return HBS_E_HIP; }
+    const bool ok = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void**>(&c->hdr), sizeof(hbs::RunHeader)) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void**>(&c->tail), (size_t)hbs::scan4_tail_bytes()) == hipSuccess &&
+                    (c->grid.full = hbs::scan_grid_blocks(device, &c->grid.per_cu)) > 0 &&
+                    (c->grid4.full = hbs::scan4_grid_blocks(device, &c->grid4.per_cu)) > 0 &&
+                    (c->grid6.full = hbs::scan4r24_grid_blocks(device, &c->grid6.per_cu)) > 0;
     c->stream = c->own_stream;
-    e = hipMalloc(reinterpret_cast<void**>(&c->hdr), sizeof(hbs::RunHeader));
-    if (e != hipSuccess) { (void)hipStreamDestroy(c->own_stream); delete c; return HBS_E_HIP; }
-    c->tail = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&c->tail), (size_t)hbs::scan4_tail_bytes()) != hipSuccess) { (void)hipFree(c->hdr); (void)hipStreamDestroy(c->own_stream); delete c; return HBS_E_HIP; }
-    c->grid_blocks = hbs::scan_grid_blocks(device, &c->blocks_per_cu);
-    if (c->grid_blocks <= 0) { (void)hipFree(c->hdr); (void)hipStreamDestroy(c->own_stream); delete c; return HBS_E_HIP; }
-    c->grid_blocks4 = hbs::scan4_grid_blocks(device, &c->blocks_per_cu4);
-    if (c->grid_blocks4 <= 0) { (void)hipFree(c->hdr); (void)hipStreamDestroy(c->own_stream); delete c; return HBS_E_HIP; }
-    c->grid_blocks6 = hbs::scan4r24_grid_blocks(device, &c->blocks_per_cu6);
-    if (c->grid_blocks6 <= 0) { (void)hipFree(c->hdr); (void)hipStreamDestroy(c->own_stream); delete c; return HBS_E_HIP; }
-    c->grid_full = c->grid_blocks; c->grid_full4 = c->grid_blocks4; c->grid_full6 = c->grid_blocks6;
+    if (!ok) { hbs_ctx_destroy(c); return HBS_E_HIP; }
     const char* g = getenv("HBS_GRID_BLOCKS");          /* debugging aid: 1 = fully sequential tiles */
-    c->grid_env = (g && atoi(g) > 0) ? atoi(g) : 0;
-    if (g && atoi(g) > 0 && atoi(g) < c->grid_blocks) c->grid_blocks = atoi(g);
-    if (g && atoi(g) > 0 && atoi(g) < c->grid_blocks4) c->grid_blocks4 = atoi(g);
-    if (g && atoi(g) > 0 && atoi(g) < c->grid_blocks6) c->grid_blocks6 = atoi(g);
+    const int cap = g ? atoi(g) : 0;
+    c->grid_env = cap > 0 ? cap : 0;
+    cut_grids(c);
     const char* ca = getenv("HBS_COUNT_AHEAD");
     c->count_ahead = (ca && ca[0] >= '0' && ca[0] <= '2') ? ca[0] - '0' : 1;
     const char* kv = getenv("HBS_KERNEL");              /* 0 automatic, 2 LDS-image, 4 event-sparse, 5 index-only streaming, 6 event-sparse with 24 rows */
-    c->variant = (kv && (atoi(kv) == 0 || atoi(kv) == 2 || atoi(kv) == 4 || atoi(kv) == 5 || atoi(kv) == 6)) ? atoi(kv) : 0;
+    const int k = kv ? atoi(kv) : 0;
+    c->variant = (k == 2 || k == 4 || k == 5 || k == 6) ? k : 0;
     c->last_variant = c->variant ? c->variant : 4;
     *out = c;
     return 0;
 }
 
+/* also the one failure path of hbs_ctx_create: whatever the context does not hold yet is null */
 void hbs_ctx_destroy(hbs_ctx* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     if (c->attachment && c->attachment_free) c->attachment_free(c->attachment);
-    if (c->desc) (void)hipFree(c->desc);
     if (c->hdr) (void)hipFree(c->hdr);
     if (c->tail) (void)hipFree(c->tail);
-    if (c->ws) (void)hipFree(c->ws);
-    if (c->ahead) (void)hipFree(c->ahead);
-    if (c->zeros) (void)hipFree(c->zeros);
-    if (c->emit_verdict) (void)hipFree(c->emit_verdict);
-    if (c->ws2) (void)hipFree(c->ws2);
-    if (c->fws) (void)hipFree(c->fws);
-    if (c->aws) (void)hipFree(c->aws);
+    if (c->emit_verdict.ptr) (void)hipFree(c->emit_verdict.ptr);
+    for (Buf& b : c->buf) if (b.ptr) (void)hipFree(b.ptr);
     if (c->ring0[0]) for (int i = 0; i < kTimingRing; ++i) { (void)hipEventDestroy(c->ring0[i]); (void)hipEventDestroy(c->ring1[i]); }
-    (void)hipStreamDestroy(c->own_stream);
+    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
@@ -249,13 +343,7 @@ int hbs_ctx_reserve_workgroups(hbs_ctx* c, int spare)
 {
     if (!c || spare < 0) return HBS_E_ARG;
     c->spare_wgs = spare;
-    c->grid_blocks = c->grid_full - spare > 1 ? c->grid_full - spare : 1;
-    c->grid_blocks4 = c->grid_full4 - spare > 1 ? c->grid_full4 - spare : 1;
-    c->grid_blocks6 = c->grid_full6 - spare > 1 ? c->grid_full6 - spare : 1;
-    /* the HBS_GRID_BLOCKS debugging cap is a ceiling of its own: reserving workgroups never raises it */
-    if (c->grid_env > 0 && c->grid_env < c->grid_blocks) c->grid_blocks = c->grid_env;
-    if (c->grid_env > 0 && c->grid_env < c->grid_blocks4) c->grid_blocks4 = c->grid_env;
-    if (c->grid_env > 0 && c->grid_env < c->grid_blocks6) c->grid_blocks6 = c->grid_env;
+    cut_grids(c);
     return 0;
 }
 
@@ -271,12 +359,14 @@ int hbs_ctx_set_device_exclusive(hbs_ctx* c, int on)
     return 0;
 }
 
+
 int hbs_ctx_grid(hbs_ctx* c, int* blocks, int* blocks_per_cu)
 {
     if (!c) return HBS_E_ARG;
     const int v = c->variant ? c->variant : c->last_variant;
-    if (blocks) *blocks = (v == 4) ? c->grid_blocks4 : (v == 6) ? c->grid_blocks6 : c->grid_blocks;
-    if (blocks_per_cu) *blocks_per_cu = (v == 4) ? c->blocks_per_cu4 : (v == 6) ? c->blocks_per_cu6 : c->blocks_per_cu;
+    const Grid& g = (v == 4) ? c->grid4 : (v == 6) ? c->grid6 : c->grid;
+    if (blocks) *blocks = g.blocks;
+    if (blocks_per_cu) *blocks_per_cu = g.per_cu;
     return 0;
 }
 
@@ -375,8 +465,9 @@ const char* hbs_last_error(hbs_ctx* c) { return c ? c->err : "no context"; }
 uint64_t hbs_ctx_device_bytes(hbs_ctx* c)
 {
     if (!c) return 0;
-    const uint64_t zb = c->zeros ? ((sizeof(hevc_sps_t) + 255) & ~(uint64_t)255) : 0;
-    return c->desc_tiles * 16 + sizeof(hbs::RunHeader) + hbs::scan4_tail_bytes() + c->ws_bytes + c->ws2_bytes + (c->ahead_tiles ? 64 + c->ahead_tiles * hbs::scan4_ahead_entry_bytes() : 0) + zb + c->fws_bytes + c->aws_bytes;
+    uint64_t sum = sizeof(hbs::RunHeader) + hbs::scan4_tail_bytes();
+    for (const Buf& b : c->buf) sum += b.bytes;
+    return sum;
 }
 
 uint64_t hbs_workspace_bytes(uint64_t stream_bytes)
@@ -389,59 +480,49 @@ int hbs_index_extract(hbs_ctx* c, const uint8_t* d_stream, uint64_t n,
                       uint8_t* d_rbsp, uint64_t rbsp_cap, hbs_summary* d_summary)
 {
     if (!c || !d_summary || (n && !d_stream) || (index_cap && !d_index)) return HBS_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_stream) & 15) || (reinterpret_cast<uintptr_t>(d_rbsp) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_index) & 7)) {
+    if (misaligned(d_stream, 15) || misaligned(d_rbsp, 15) || misaligned(d_index, 7)) {
         snprintf(c->err, sizeof(c->err), "stream/rbsp pointers must be 16-byte aligned");
         return HBS_E_ARG;
     }
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
-    int rc = ensure_workspace(c, n);
-    if (rc) return rc;
+    int rc = grow(c, c->buf[kDesc], ((n + hbs::kTileBytes - 1) / hbs::kTileBytes + 1) * 16, "hipMalloc(look-back descriptors)");
+    if (rc < 0) return rc;
     hbs::ScanArgs a;
     a.stream = d_stream; a.n = n;
     a.index = d_index; a.index_cap = index_cap;
     a.rbsp = d_rbsp; a.rbsp_cap = d_rbsp ? rbsp_cap : 0;
-    a.desc = c->desc; a.hdr = c->hdr; a.tail = c->tail; a.summary = d_summary;
+    a.desc = static_cast<unsigned long long*>(c->buf[kDesc].ptr); a.hdr = c->hdr; a.tail = c->tail; a.summary = d_summary;
     a.ws5 = nullptr;
     if (!d_rbsp && n) {                                       /* the index-only kernels keep tile aggregates and elements between their passes */
-        rc = ensure_ws(c, hbs::scan5_workspace_bytes(n));
-        if (rc) return rc;
-        a.ws5 = c->ws;
+        rc = grow(c, c->buf[kWs], hbs::scan5_workspace_bytes(n), "hipMalloc(workspace)");
+        if (rc < 0) return rc;
+        a.ws5 = c->buf[kWs].ptr;
     }
     a.ahead_cand = nullptr; a.ahead_tab = nullptr; a.ahead_list = nullptr; a.ahead_ctl = nullptr;
     if (d_rbsp && (c->count_ahead == 2 || (c->count_ahead == 1 && hbs::scan4_counts_ahead(n))) && n > (uint64_t)hbs::scan4_tile_bytes() &&
         (c->variant == 0 || c->variant == 4 || c->variant == 5) /* (6: the 24-row geometry counts nothing ahead) */ && !hbs::scan_takes_small_path(n, index_cap, c->variant)) {
-        /* K12's dense tiles counted ahead: [AheadCtl | table | a word per tile | list] */
+        /* K12's dense tiles counted ahead.  What the tiles' words carry from one call to the next stays where it is: the layout
+         * is that of the longest stream so far */
         const uint64_t tiles = (n + (uint64_t)hbs::scan4_tile_bytes() - 1) / (uint64_t)hbs::scan4_tile_bytes();
-        if (tiles > c->ahead_tiles) {
-            if (c->ahead) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->ahead); c->ahead = nullptr; c->ahead_tiles = 0; }
-            hipError_t e = hipMalloc(&c->ahead, 64 + tiles * hbs::scan4_ahead_entry_bytes());
-            if (e != hipSuccess) return fail(c, e, "hipMalloc(count-ahead table)");
-            /* the call number, the list's count and the tiles' words start at zero (table and list are written before they are read) */
-            e = hipMemsetAsync(c->ahead, 0, 64 + tiles * 72, c->stream);
+        const uint64_t room = tiles > c->ahead_tiles ? tiles : c->ahead_tiles;
+        uint64_t cleared = 0;
+        rc = carve(c, c->buf[kAhead], "hipMalloc(count-ahead table)", [&](hbs::Carver& w) { cleared = hbs::lay_scan_ahead(w, a, room); });
+        if (rc < 0) return rc;
+        if (rc) {
+            const hipError_t e = hipMemsetAsync(c->buf[kAhead].ptr, 0, cleared, c->stream);
             if (e != hipSuccess) return fail(c, e, "hipMemsetAsync(count-ahead words)");
-            c->ahead_tiles = tiles;
+            c->ahead_tiles = room;
         }
-        uint8_t* const p = static_cast<uint8_t*>(c->ahead);
-        a.ahead_ctl = reinterpret_cast<hbs::AheadCtl*>(p);
-        a.ahead_tab = p + 64;
-        a.ahead_cand = reinterpret_cast<unsigned long long*>(p + 64 + c->ahead_tiles * 64);
-        a.ahead_list = reinterpret_cast<uint32_t*>(p + 64 + c->ahead_tiles * 72);
     }
     c->last_index_only = (hbs::scan_uses_index_only(n, c->variant, d_rbsp) && !hbs::scan_takes_small_path(n, index_cap, c->variant)) ? 1 : 0;
     a.variant = c->variant;
     a.cus = c->cus;
-    a.grid_blocks = c->grid_blocks; a.grid_blocks4 = c->grid_blocks4; a.grid_blocks4r24 = c->grid_blocks6; a.spare_wgs = c->spare_wgs; a.first_static = c->exclusive;
+    a.grid_blocks = c->grid.blocks; a.grid_blocks4 = c->grid4.blocks; a.grid_blocks4r24 = c->grid6.blocks; a.spare_wgs = c->spare_wgs; a.first_static = c->exclusive;
     c->probe_pending = (c->variant == 0 && n) ? 1 : 0;
     if (hbs::scan_takes_small_path(n, index_cap, c->variant)) { c->probe_pending = 0; c->last_variant = 2; }
-    if (c->timing && n) {                                     /* this call's slot of the ring */
-        const int slot = (int)(c->timed_calls % kTimingRing);
-        c->ev0 = c->ring0[slot]; c->ev1 = c->ring1[slot];
-        c->timed_calls += 1;
-    }
-    a.ev_begin = (c->timing && n) ? c->ev0 : nullptr;
-    a.ev_end = (c->timing && n) ? c->ev1 : nullptr;
-    c->ev_valid = (c->timing && n) ? 1 : (c->ev_valid && c->timing);
+    a.ev_begin = nullptr; a.ev_end = nullptr;
+    if (c->timing && n) take_timing_slot(c, &a.ev_begin, &a.ev_end);
+    else c->ev_valid = c->ev_valid && c->timing;             /* a call of no bytes launches nothing: the last timed call stays the one reported */
     hipError_t e = hbs::launch_scan_extract(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_scan_extract");
 }
@@ -452,15 +533,14 @@ int hbs_emit_annexb(hbs_ctx* c, const uint8_t* d_rbsp, uint64_t rbsp_bytes,
 {
     if (!c || !d_summary || (n_nals && (!d_rbsp || !d_index_in || !d_out))) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
-    const uint64_t b_seg = 8192, b_n = round256((n_nals + 1) * 8);       /* b_seg: the scan's 1024 partial sums */
+    hbs::EmitArgs a;
+    a.rbsp = d_rbsp; a.rbsp_bytes = rbsp_bytes; a.index_in = d_index_in; a.n = n_nals; a.gap_mode = gap_mode;
+    a.out = d_out; a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
     /* NALs that do not overlap add up to at most rbsp_bytes; an index whose NALs add up to more gets HBS_E_CAPACITY */
-    const uint64_t items_cap = hbs::emit_items_bound(n_nals, out_cap < rbsp_bytes ? out_cap : rbsp_bytes);
-    const uint64_t b_items = round256(items_cap * 8), b_desc = round256(hbs::emit_desc_words(items_cap) * 8);
-    const uint64_t first_cap = rbsp_bytes / (192u * 1024u) + 4;          /* arena tiles of the tile kernel (hbs_emit.hip: kTTileBytes) */
-    const uint64_t b_first = round256(first_cap * 8);
-    const uint64_t b_cand = round256(first_cap * 4), b_dz = round256(first_cap * hbs::emit_dz_table_words() * 4);   /* dense tiles counted ahead */
-    int rc = ensure_ws(c, b_seg + 2 * b_n + b_items + b_desc + 1024 + b_first + b_cand + b_dz);
-    if (rc) return rc;
+    a.items_cap = hbs::emit_items_bound(n_nals, out_cap < rbsp_bytes ? out_cap : rbsp_bytes);
+    a.first_cap = a.cand_cap = rbsp_bytes / (192u * 1024u) + 4;          /* arena tiles of the tile kernel (hbs_emit.hip: kTTileBytes) */
+    int rc = carve(c, c->buf[kWs], "hipMalloc(workspace)", [&](hbs::Carver& w) { hbs::lay_emit(w, a); });
+    if (rc < 0) return rc;
     if (c->emit_blocks <= 0) {
         c->emit_blocks = hbs::emit_grid_blocks(c->device);
         if (c->emit_blocks <= 0) return fail(c, hipErrorUnknown, "occupancy query of the emit kernel");
@@ -469,27 +549,6 @@ int hbs_emit_annexb(hbs_ctx* c, const uint8_t* d_rbsp, uint64_t rbsp_bytes,
         c->emit_tile_blocks = hbs::emit_tile_grid_blocks(c->device);
         if (c->emit_tile_blocks <= 0) return fail(c, hipErrorUnknown, "occupancy query of the arena-tile emit kernel");
     }
-    uint8_t* w = static_cast<uint8_t*>(c->ws);
-    hbs::EmitArgs a;
-    a.rbsp = d_rbsp; a.rbsp_bytes = rbsp_bytes; a.index_in = d_index_in; a.n = n_nals; a.gap_mode = gap_mode;
-    a.out = d_out; a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
-    a.scan_tmp = reinterpret_cast<unsigned long long*>(w);
-    a.nal_total = reinterpret_cast<unsigned long long*>(w + b_seg);
-    a.out_off = reinterpret_cast<unsigned long long*>(w + b_seg + b_n);
-    a.items = reinterpret_cast<unsigned long long*>(w + b_seg + 2 * b_n); a.items_cap = items_cap;
-    a.desc = reinterpret_cast<unsigned long long*>(w + b_seg + 2 * b_n + b_items);
-    uint8_t* tail = w + b_seg + 2 * b_n + b_items + b_desc;
-    a.total = reinterpret_cast<unsigned long long*>(tail);
-    a.err = reinterpret_cast<uint32_t*>(tail + 256);
-    a.ticket = reinterpret_cast<uint32_t*>(tail + 512);
-    a.n_items = reinterpret_cast<unsigned long long*>(tail + 768);
-    a.total_dense = reinterpret_cast<unsigned long long*>(tail + 768 + 64);
-    a.probe = reinterpret_cast<uint32_t*>(tail + 768 + 128);
-    a.tflag = reinterpret_cast<uint32_t*>(tail + 768 + 192);
-    a.first_k = reinterpret_cast<unsigned long long*>(tail + 1024); a.first_cap = first_cap;
-    a.cand_count = reinterpret_cast<uint32_t*>(tail + 640); a.cand_ticket = reinterpret_cast<uint32_t*>(tail + 704);   /* cleared with the counters */
-    a.cand_list = reinterpret_cast<uint32_t*>(tail + 1024 + b_first); a.cand_cap = first_cap;
-    a.dz_table = reinterpret_cast<uint32_t*>(tail + 1024 + b_first + b_cand);
     /* dense tiles counted ahead of the tile kernel (k3t_sample + a pass over the tiles it lists): from 3 GiB of arena up, as the scan's
      * (hbs_ctx_set_count_ahead: 0 never, 1 from 3 GiB, 2 always).  Until round 6 every call paid for it -- two launches, 11.5 us of a
      * 1 GiB call's 445 with nothing listed -- where mixed content is as unlikely as in the scan. */
@@ -498,16 +557,13 @@ int hbs_emit_annexb(hbs_ctx* c, const uint8_t* d_rbsp, uint64_t rbsp_bytes,
     a.call_no = c->emit_calls;
     a.first_static = c->exclusive;
     a.tiles = c->emit_tiles; a.tile_blocks = c->emit_tile_blocks;
-    a.clear_bytes = b_desc + 1024;                          /* look-back words and the counters behind them */
     a.grid_blocks = c->emit_blocks; a.two_pass = c->emit_two_pass; a.cus = c->cus;
-    if (!c->emit_verdict) {
-        const hipError_t ea = hipMalloc(reinterpret_cast<void**>(&c->emit_verdict), 16);
-        if (ea != hipSuccess) return fail(c, ea, "hipMalloc(emit verdict)");
-    }
+    rc = grow(c, c->emit_verdict, 16, "hipMalloc(emit verdict)");
+    if (rc < 0) return rc;
     /* the verdict words leave the shared workspace with the call's last kernel (round 4's advice: hbs_ctx_last_emit_by_tiles after
      * any other call read bytes that call had overwritten, or a freed workspace); the one-launch small path writes none */
-    a.verdict_out = c->emit_verdict;
-    c->last_emit_tflag = hbs::emit_takes_small_path(a.n, a.rbsp_bytes, a.two_pass) ? nullptr : c->emit_verdict;
+    a.verdict_out = static_cast<uint32_t*>(c->emit_verdict.ptr);
+    c->last_emit_tflag = hbs::emit_takes_small_path(a.n, a.rbsp_bytes, a.two_pass) ? nullptr : a.verdict_out;
     hipError_t e = hbs::launch_emit_annexb(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_emit_annexb");
 }
@@ -521,57 +577,25 @@ int hbs_filter_annexb(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes
     static_assert(sizeof(hbs_nal_filter) == 24, "hbs_nal_filter layout");
     if (!c || !d_summary || (rule == nullptr) == (d_keep == nullptr)) return HBS_E_ARG;
     if (n_nals && (!d_index || (stream_bytes && !d_stream))) return HBS_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_stream) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_index) & 7) || (reinterpret_cast<uintptr_t>(d_index_out) & 7)) {
+    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_index, 7) || misaligned(d_index_out, 7)) {
         snprintf(c->err, sizeof(c->err), "stream/output pointers must be 16-byte aligned, index pointers 8-byte aligned");
         return HBS_E_ARG;
     }
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     const uint64_t reach = d_out ? (out_cap < stream_bytes ? out_cap : stream_bytes) : 0;    /* the output is at most this long */
-    const uint64_t tiles = (reach + hbs::kFilterTileBytes - 1) / hbs::kFilterTileBytes;
-    const hbs::FilterScratch fs = hbs::filter_scratch(n_nals, tiles);
-    if (fs.total > c->fws_bytes) {
-        if (c->fws) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->fws); c->fws = nullptr; c->fws_bytes = 0; }
-        hipError_t e = hipMalloc(&c->fws, fs.total);
-        if (e != hipSuccess) return fail(c, e, "hipMalloc(filter scratch)");
-        c->fws_bytes = fs.total;
-    }
-    uint8_t* w = static_cast<uint8_t*>(c->fws);
     hbs::FilterArgs a;
     memset(&a, 0, sizeof(a));
     a.stream = d_stream; a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals;
     if (rule) { a.rule = *rule; a.use_rule = 1; }
     a.keep = d_keep;
     a.out = d_out; a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
-    a.part = reinterpret_cast<unsigned long long*>(w + fs.part);
-    a.ctl = reinterpret_cast<unsigned long long*>(w + fs.ctl);
-    a.kept_out = reinterpret_cast<unsigned long long*>(w + fs.kept_out);
-    a.kept_delta = reinterpret_cast<unsigned long long*>(w + fs.kept_delta);
-    a.tile_first = reinterpret_cast<unsigned long long*>(w + fs.tile_first);
-    a.tiles = tiles;
-    if (c->timing) {                                          /* this call's slot of the ring: all of its kernels */
-        const int slot = (int)(c->timed_calls % kTimingRing);
-        c->ev0 = c->ring0[slot]; c->ev1 = c->ring1[slot];
-        c->timed_calls += 1;
-        a.ev_begin = c->ev0; a.ev_end = c->ev1;
-        c->ev_valid = 1;
-    }
+    a.tiles = (reach + hbs::kFilterTileBytes - 1) / hbs::kFilterTileBytes;
+    const int rc = carve(c, c->buf[kFws], "hipMalloc(filter scratch)", [&](hbs::Carver& w) { hbs::lay_filter(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_filter_annexb(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_filter_annexb");
 }
-
-namespace {
-int ensure_aws(hbs_ctx* c, uint64_t bytes)
-{
-    if (bytes > c->aws_bytes) {
-        if (c->aws) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->aws); c->aws = nullptr; c->aws_bytes = 0; }
-        hipError_t e = hipMalloc(&c->aws, bytes);
-        if (e != hipSuccess) return fail(c, e, "hipMalloc(access unit scratch)");
-        c->aws_bytes = bytes;
-    }
-    return 0;
-}
-} // namespace
 
 uint64_t hbs_au_sps_poc_offset(void) { return offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4); }
 
@@ -584,36 +608,21 @@ int hbs_access_units(hbs_ctx* c, const hbs_nal_entry* d_index, const hbs_parsed_
     static_assert(sizeof(hbs_parsed_nal) == 32 && sizeof(hbs_slice_compact) == 64 && sizeof(hbs_nal_entry) == 32, "record layouts");
     if (!c || !d_summary || n_nals > 0xFFFFFFFFull) return HBS_E_ARG;
     if (n_nals && (!d_index || !d_parsed || !d_compact)) return HBS_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_index) & 15) || (reinterpret_cast<uintptr_t>(d_parsed) & 15) || (reinterpret_cast<uintptr_t>(d_compact) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_au) & 15) || (reinterpret_cast<uintptr_t>(d_nal_au) & 3) || (reinterpret_cast<uintptr_t>(d_carry_out) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_structs) & 3)) {
+    if (misaligned(d_index, 15) || misaligned(d_parsed, 15) || misaligned(d_compact, 15) || misaligned(d_au, 15) ||
+        misaligned(d_nal_au, 3) || misaligned(d_carry_out, 3) || misaligned(d_structs, 3)) {
         snprintf(c->err, sizeof(c->err), "index / parsed / compact / au pointers must be 16-byte aligned");
         return HBS_E_ARG;
     }
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
-    const hbs::AuScratch as = hbs::au_scratch(n_nals);
-    const int rc = ensure_aws(c, as.total);
-    if (rc) return rc;
-    uint8_t* w = static_cast<uint8_t*>(c->aws);
     hbs::AuArgs a;
     memset(&a, 0, sizeof(a));
     a.index = d_index; a.parsed = d_parsed; a.compact = d_compact; a.structs = d_structs;
     a.n_nals = n_nals; a.sps_off = hbs_au_sps_poc_offset();
     if (initial) a.initial = *initial;
     a.au = d_au; a.au_cap = au_cap; a.nal_au = d_au ? d_nal_au : nullptr; a.carry_out = d_carry_out; a.summary = d_summary;
-    a.digest = reinterpret_cast<hbs::AuDigest*>(w + as.digest);
-    a.part1 = reinterpret_cast<uint32_t*>(w + as.part1);
-    a.part2 = reinterpret_cast<uint32_t*>(w + as.part2);
-    a.part3 = reinterpret_cast<uint32_t*>(w + as.part3);
-    a.lead = reinterpret_cast<uint32_t*>(w + as.lead);
-    a.ctl = reinterpret_cast<uint32_t*>(w + as.ctl);
-    if (c->timing) {                                          /* this call's slot of the ring: all of its kernels */
-        const int slot = (int)(c->timed_calls % kTimingRing);
-        c->ev0 = c->ring0[slot]; c->ev1 = c->ring1[slot];
-        c->timed_calls += 1;
-        a.ev_begin = c->ev0; a.ev_end = c->ev1;
-        c->ev_valid = 1;
-    }
+    const int rc = carve(c, c->buf[kAws], "hipMalloc(access unit scratch)", [&](hbs::Carver& w) { hbs::lay_access_units(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_access_units(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_access_units");
 }
@@ -623,14 +632,14 @@ int hbs_au_keep(hbs_ctx* c, const uint32_t* d_nal_au, const hbs_parsed_nal* d_pa
 {
     if (!c || n_nals > 0xFFFFFFFFull || (flags & ~HBS_AUKEEP_PARAM_SETS)) return HBS_E_ARG;
     if (n_nals && (!d_nal_au || !d_parsed || !d_keep)) return HBS_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_nal_au) & 3) || (reinterpret_cast<uintptr_t>(d_parsed) & 7)) return HBS_E_ARG;
+    if (misaligned(d_nal_au, 3) || misaligned(d_parsed, 7)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
-    const int rc = ensure_aws(c, 256);
-    if (rc) return rc;
+    const int rc = grow(c, c->buf[kAws], 256, "hipMalloc(access unit scratch)");
+    if (rc < 0) return rc;
     hbs::AuKeepArgs a;
     a.nal_au = d_nal_au; a.parsed = d_parsed; a.n_nals = n_nals; a.first_au = first_au; a.au_count = au_count; a.flags = flags;
     a.keep = d_keep;
-    a.sets = reinterpret_cast<uint32_t*>(c->aws);
+    a.sets = static_cast<uint32_t*>(c->buf[kAws].ptr);
     const hipError_t e = hbs::launch_au_keep(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_au_keep");
 }
@@ -640,17 +649,10 @@ int hbs_synth_rbsp(hbs_ctx* c, uint64_t seed, uint64_t n_nals, int mode,
 {
     if (!c || !d_summary || (n_nals && (!d_rbsp || !d_index)) || (mode != 0 && mode != 1)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
-    const uint64_t b_n = round256((n_nals + 1) * 8);
-    int rc = ensure_ws(c, 2 * b_n + 512 + 8192);
-    if (rc) return rc;
-    uint8_t* w = static_cast<uint8_t*>(c->ws);
     hbs::SynthArgs a;
     a.seed = seed; a.n = n_nals; a.mode = mode; a.rbsp = d_rbsp; a.rbsp_cap = rbsp_cap; a.index = d_index; a.summary = d_summary;
-    a.lens = reinterpret_cast<unsigned long long*>(w);
-    a.offs = reinterpret_cast<unsigned long long*>(w + b_n);
-    a.total = reinterpret_cast<unsigned long long*>(w + 2 * b_n);
-    a.err = reinterpret_cast<uint32_t*>(w + 2 * b_n + 256);
-    a.scan_tmp = reinterpret_cast<unsigned long long*>(w + 2 * b_n + 512);
+    const int rc = carve(c, c->buf[kWs], "hipMalloc(workspace)", [&](hbs::Carver& w) { hbs::lay_synth(w, a); });
+    if (rc < 0) return rc;
     hipError_t e = hbs::launch_synth_rbsp(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_synth_rbsp");
 }
@@ -696,13 +698,6 @@ int hbs_parse_headers_trace(hbs_ctx* c, const uint8_t* d_rbsp, const hbs_nal_ent
                                    d_trace, trace_cap, d_trace_count, d_summary, nullptr, nullptr);
 }
 
-static int parse_impl(hbs_ctx* c, const uint8_t* d_rbsp, const hbs_nal_entry* d_index, uint64_t n_nals,
-                      hbs_parsed_nal* d_parsed, uint8_t* d_structs, uint64_t structs_cap,
-                      const uint8_t* d_initial_sps_slot, const uint8_t* d_initial_pps,
-                      hbs_trace_rec* d_trace, uint32_t trace_cap, uint32_t* d_trace_count, hbs_summary* d_summary,
-                      uint8_t* d_state_sps_slot, uint8_t* d_state_pps,
-                      hbs_slice_compact* d_compact, const uint64_t* d_want, uint64_t n_want);
-
 int hbs_parse_headers_state(hbs_ctx* c, const uint8_t* d_rbsp, const hbs_nal_entry* d_index, uint64_t n_nals,
                             hbs_parsed_nal* d_parsed, uint8_t* d_structs, uint64_t structs_cap,
                             const uint8_t* d_initial_sps_slot, const uint8_t* d_initial_pps,
@@ -732,72 +727,6 @@ int hbs_parse_materialize(hbs_ctx* c, const uint8_t* d_rbsp, const hbs_nal_entry
                       nullptr, 0, nullptr, d_summary, nullptr, nullptr, d_compact, d_nal_list, n_list);
 }
 
-static int parse_impl(hbs_ctx* c, const uint8_t* d_rbsp, const hbs_nal_entry* d_index, uint64_t n_nals,
-                      hbs_parsed_nal* d_parsed, uint8_t* d_structs, uint64_t structs_cap,
-                      const uint8_t* d_initial_sps_slot, const uint8_t* d_initial_pps,
-                      hbs_trace_rec* d_trace, uint32_t trace_cap, uint32_t* d_trace_count, hbs_summary* d_summary,
-                      uint8_t* d_state_sps_slot, uint8_t* d_state_pps,
-                      hbs_slice_compact* d_compact, const uint64_t* d_want, uint64_t n_want)
-{
-    static_assert(sizeof(hbs_slice_compact) == sizeof(hbs::SliceCompact), "public record == kernel record");
-    if ((d_state_sps_slot == nullptr) != (d_state_pps == nullptr)) return HBS_E_ARG;
-    if (d_state_sps_slot && (!d_structs || !n_nals)) return HBS_E_ARG;
-    static_assert(sizeof(hbs_trace_rec) == sizeof(hbs::TraceRec), "public record == kernel record");
-    static_assert(sizeof(hbs_parsed_nal) == sizeof(hbs::ParsedNal), "public record == kernel record");
-    if (!c || !d_summary || (n_nals && (!d_rbsp || !d_index || !d_parsed))) return HBS_E_ARG;
-    if (reinterpret_cast<uintptr_t>(d_structs) & 15) return HBS_E_ARG;
-    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
-    if (!c->zeros) {
-        const size_t zb = (sizeof(hevc_sps_t) + 255) & ~(size_t)255;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->zeros), zb);
-        if (e != hipSuccess) return fail(c, e, "hipMalloc(zero structs)");
-        e = hipMemsetAsync(c->zeros, 0, zb, c->stream);
-        if (e != hipSuccess) return fail(c, e, "hipMemsetAsync(zero structs)");
-    }
-    const uint64_t b_n = round256((n_nals + 1) * 8);
-    const uint64_t b_rows = round256(hbs::parse_own_rows_bytes(n_nals));
-    /* the exact re-walk's records: three words per NAL, a summary word per 256, the temporaries of its lanes */
-    const uint64_t b_n4 = round256((n_nals + 1) * 4), b_bsum = round256((n_nals / 256 + 2) * 4), b_fix = round256(hbs::parse_fix_temps_bytes());
-    const uint64_t b_fixs = d_compact ? round256(hbs::parse_fix_structs_bytes()) : 0;     /* a compact parse's re-walk has no slots to walk into */
-    const uint64_t fix_off = 3 * b_n + 512 + round256(1024 * 24) + b_rows;
-    int rc = ensure_ws(c, fix_off + 3 * b_n4 + b_bsum + 256 + b_fix + b_fixs);
-    if (rc) return rc;
-    uint8_t* w = static_cast<uint8_t*>(c->ws);
-    hbs::ParseArgs a;
-    a.rbsp = d_rbsp; a.index = d_index; a.n = n_nals;
-    a.parsed = reinterpret_cast<hbs::ParsedNal*>(d_parsed);
-    a.structs = d_structs; a.structs_cap = d_structs ? structs_cap : 0; a.summary = d_summary;
-    a.slot_size = reinterpret_cast<unsigned long long*>(w);
-    a.ctx_sps = reinterpret_cast<long long*>(w + b_n);
-    a.ctx_pps = reinterpret_cast<long long*>(w + 2 * b_n);
-    a.zeros = c->zeros;
-    a.initial_sps_slot = d_initial_sps_slot;
-    a.initial_pps = d_initial_pps;
-    a.total = reinterpret_cast<unsigned long long*>(w + 3 * b_n);
-    a.err = reinterpret_cast<uint32_t*>(w + 3 * b_n + 256);
-    a.div_flag = reinterpret_cast<uint32_t*>(w + 3 * b_n + 256 + 64);
-    a.scan_tmp = w + 3 * b_n + 512;
-    a.own_rows = reinterpret_cast<hbs::RpsRow*>(w + 3 * b_n + 512 + round256(1024 * 24));
-    a.deps = reinterpret_cast<uint32_t*>(w + fix_off);
-    a.wmask = reinterpret_cast<uint32_t*>(w + fix_off + b_n4);
-    a.fix_list = reinterpret_cast<uint32_t*>(w + fix_off + 2 * b_n4);
-    a.bsum = reinterpret_cast<uint32_t*>(w + fix_off + 3 * b_n4);
-    a.fix_count = reinterpret_cast<uint32_t*>(w + fix_off + 3 * b_n4 + b_bsum);
-    a.fix_temps = reinterpret_cast<hbs::RpsRow*>(w + fix_off + 3 * b_n4 + b_bsum + 256);
-    a.trace = reinterpret_cast<hbs::TraceRec*>(d_trace); a.trace_cap = trace_cap; a.trace_count = d_trace_count;
-    a.state_sps_slot_out = d_state_sps_slot; a.state_pps_out = d_state_pps;
-    a.compact = reinterpret_cast<hbs::SliceCompact*>(d_compact); a.want_list = d_want; a.want_n = d_compact ? n_want : 0;
-    a.fix_structs = d_compact ? w + fix_off + 3 * b_n4 + b_bsum + 256 + b_fix : nullptr;
-    a.sequential = (d_state_sps_slot || d_compact) ? 0 : c->parse_sequential;
-    hipError_t e = hbs::launch_parse_headers(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_parse_headers");
-}
-
-static int index_parse_impl(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
-                            hbs_nal_entry* d_index, uint64_t index_cap, uint32_t header_window,
-                            hbs_parsed_nal* d_parsed, hbs_slice_compact* d_compact, uint8_t* d_structs, uint64_t structs_cap, uint64_t* d_payload_off,
-                            hbs_summary* d_scan_summary, hbs_summary* d_parse_summary, uint64_t* nal_count_out);
-
 int hbs_index_parse(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
                     hbs_nal_entry* d_index, uint64_t index_cap, uint32_t header_window,
                     hbs_parsed_nal* d_parsed, uint8_t* d_structs, uint64_t structs_cap, uint64_t* d_payload_off,
@@ -817,54 +746,6 @@ int hbs_index_parse_compact(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream
                             d_scan_summary, d_parse_summary, nal_count_out);
 }
 
-static int index_parse_impl(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
-                            hbs_nal_entry* d_index, uint64_t index_cap, uint32_t header_window,
-                            hbs_parsed_nal* d_parsed, hbs_slice_compact* d_compact, uint8_t* d_structs, uint64_t structs_cap, uint64_t* d_payload_off,
-                            hbs_summary* d_scan_summary, hbs_summary* d_parse_summary, uint64_t* nal_count_out)
-{
-    if (!c || !d_scan_summary || !d_parse_summary || !d_index || !index_cap || !d_parsed) return HBS_E_ARG;
-    if (header_window == 0) header_window = 512;
-    if (header_window < 64 || header_window > (1u << 16) || (header_window & 15u)) return HBS_E_ARG;
-    /* what the parse behind the scan would refuse is refused here, before the scan has written the index and its summary */
-    if (reinterpret_cast<uintptr_t>(d_structs) & 15) return HBS_E_ARG;
-    /* 1. find_nal_unit over the stream: no arena */
-    int rc = hbs_index_extract(c, d_stream, stream_bytes, d_index, index_cap, nullptr, 0, d_scan_summary);
-    if (rc) return rc;
-    /* the parse's launches are sized by the number of NALs: the one wait of the call */
-    hbs_summary s;
-    rc = hbs_read_summary(c, d_scan_summary, &s);
-    if (rc) return rc;
-    if (nal_count_out) *nal_count_out = s.nal_count;
-    if (s.error) return s.error;
-    const uint64_t nals = s.nal_count;
-    /* 2. the bytes the parse can look at, stripped into windows */
-    hbs::HdrWinArgs a;
-    /* everything below is sized by the NALs FOUND (known since the wait above), not by the caller's index capacity: a default
-     * capacity of stream_bytes / 64 entries would ask for 137 GB of windows on a 16 GiB stream (round 3's advice) */
-    const uint64_t slots = nals ? nals : 1;
-    a.stream = d_stream; a.index = d_index; a.nals = nals; a.index_cap = slots; a.window = header_window;
-    a.arena_bytes = hbs::hdrwin_arena_bytes(slots, header_window, stream_bytes);
-    const uint64_t b_arena = round256(a.arena_bytes + 64), b_idx = round256(slots * sizeof(hbs_nal_entry));
-    const uint64_t b_notes = round256(slots * 16);
-    if (b_arena + b_idx + b_notes + 256 > c->ws2_bytes) {                 /* grow-only */
-        if (c->ws2) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->ws2); c->ws2 = nullptr; c->ws2_bytes = 0; }
-        const hipError_t e = hipMalloc(&c->ws2, b_arena + b_idx + b_notes + 256);
-        if (e != hipSuccess) return fail(c, e, "hipMalloc(header windows)");
-        c->ws2_bytes = b_arena + b_idx + b_notes + 256;
-    }
-    uint8_t* w = static_cast<uint8_t*>(c->ws2);
-    a.arena = w; a.idx2 = reinterpret_cast<hbs_nal_entry*>(w + b_arena); a.bump = reinterpret_cast<unsigned long long*>(w + b_arena + b_idx);
-    a.notes = w + b_arena + b_idx + 256;
-    hipError_t e = hbs::launch_hdr_strip(a, c->stream);
-    if (e != hipSuccess) return fail(c, e, "launch_hdr_strip");
-    /* 3. K4 on the windows, 4. slice_data_size against the real lengths, windows that were too small reported */
-    rc = d_compact ? hbs_parse_headers_compact(c, a.arena, a.idx2, nals, d_parsed, d_compact, d_structs, structs_cap, nullptr, nullptr, d_parse_summary)
-                   : hbs_parse_headers(c, a.arena, a.idx2, nals, d_parsed, d_structs, structs_cap, d_parse_summary);
-    if (rc) return rc;
-    e = hbs::launch_hdr_fix(a, d_parsed, d_parse_summary, reinterpret_cast<unsigned long long*>(d_payload_off), c->stream, d_compact ? 1 : 0);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_hdr_fix");
-}
-
 int hbs_write_headers(hbs_ctx* c, const hbs_parsed_nal* d_parsed, uint64_t n_nals, uint8_t* d_structs,
                       const uint8_t* d_initial_sps_slot, const uint8_t* d_initial_pps,
                       uint8_t* d_rbsp_out, uint32_t rbsp_cap, hbs_written_nal* d_written)
@@ -872,27 +753,14 @@ int hbs_write_headers(hbs_ctx* c, const hbs_parsed_nal* d_parsed, uint64_t n_nal
     static_assert(sizeof(hbs_written_nal) == sizeof(hbs::WrittenNal), "public record == kernel record");
     if (!c || (n_nals && (!d_parsed || !d_structs || !d_rbsp_out || !d_written))) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
-    if (!c->zeros) {
-        const size_t zb = (sizeof(hevc_sps_t) + 255) & ~(size_t)255;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->zeros), zb);
-        if (e != hipSuccess) return fail(c, e, "hipMalloc(zero structs)");
-        e = hipMemsetAsync(c->zeros, 0, zb, c->stream);
-        if (e != hipSuccess) return fail(c, e, "hipMemsetAsync(zero structs)");
-    }
-    const uint64_t b_n = round256((n_nals + 1) * 8);
-    int rc = ensure_ws(c, 3 * b_n + 512 + round256(1024 * 24) + round256(hbs::parse_own_rows_bytes(n_nals)));
+    int rc = ensure_zeros(c);
     if (rc) return rc;
-    uint8_t* w = static_cast<uint8_t*>(c->ws);
     hbs::WriteArgs a;
     a.parsed = reinterpret_cast<const hbs::ParsedNal*>(d_parsed); a.n = n_nals; a.structs = d_structs;
     a.rbsp_out = d_rbsp_out; a.rbsp_cap = rbsp_cap; a.written = reinterpret_cast<hbs::WrittenNal*>(d_written);
-    a.slot_size = reinterpret_cast<unsigned long long*>(w);
-    a.ctx_sps = reinterpret_cast<long long*>(w + b_n);
-    a.ctx_pps = reinterpret_cast<long long*>(w + 2 * b_n);
-    a.zeros = c->zeros; a.initial_sps_slot = d_initial_sps_slot; a.initial_pps = d_initial_pps;
-    a.total = reinterpret_cast<unsigned long long*>(w + 3 * b_n);
-    a.scan_tmp = w + 3 * b_n + 512;
-    a.own_rows = reinterpret_cast<hbs::RpsRow*>(w + 3 * b_n + 512 + round256(1024 * 24));
+    a.zeros = static_cast<const uint8_t*>(c->buf[kZeros].ptr); a.initial_sps_slot = d_initial_sps_slot; a.initial_pps = d_initial_pps;
+    rc = carve(c, c->buf[kWs], "hipMalloc(workspace)", [&](hbs::Carver& w) { (void)hbs::lay_headers_common(w, a); });
+    if (rc < 0) return rc;
     hipError_t e = hbs::launch_write_headers(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_write_headers");
 }
@@ -985,3 +853,4 @@ int hbs_read_summary(hbs_ctx* c, const hbs_summary* d_summary, hbs_summary* h_su
 }
 
 } // extern "C"
+

@@ -101,6 +101,20 @@ struct AheadCtl { unsigned long long call; uint32_t listed; uint32_t pad[13]; };
 static_assert(sizeof(AheadCtl) == 64, "one line");
 HBS_HD unsigned long long ahead_stamp_of(unsigned long long call) { return (call + 1ull) << 2; }
 
+/* Carves a call's device workspace (host side): a layout function fills its *Args through take(), once with no base to learn
+ * the total (`at`), then again on the buffer grown to it -- the size and the pointers come from the same lines. */
+struct Carver {
+    uint8_t* base;
+    uint64_t at;
+    /* the next piece (null while there is no base); the cursor moves on by `bytes` rounded up to `pack` */
+    template <class T> T* take(uint64_t bytes, uint64_t pack = 256)
+    {
+        T* const p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += (bytes + pack - 1) / pack * pack;
+        return p;
+    }
+};
+
 /* The kernel-choice rule of the automatic mode (hbs_scan.hip launch_scan_extract): the event-sparse
  * kernel handles flagged chunks 64 at a time on one wavefront, so once more than one chunk in
  * kDenseOneIn may hold a zero pair the LDS-image kernel, whose cost does not depend on the data,

@@ -66,6 +66,51 @@ int emit_tile_grid_blocks(int device);
 uint64_t emit_items_bound(uint64_t n, uint64_t payload_bytes);
 uint64_t emit_desc_words(uint64_t items_cap);
 uint64_t emit_dz_table_words();
+
+/* the counters behind the look-back words, cleared with them: the contended ones on lines of their own */
+struct EmitCounters {
+    alignas(256) unsigned long long total;
+    alignas(256) uint32_t err;
+    alignas(256) uint32_t ticket;
+    alignas(128) uint32_t cand_count;
+    alignas(64) uint32_t cand_ticket;
+    alignas(64) unsigned long long n_items;
+    alignas(64) unsigned long long total_dense;
+    alignas(64) uint32_t probe[2];
+    alignas(64) uint32_t tflag[4];
+};
+static_assert(sizeof(EmitCounters) == 1024 && offsetof(EmitCounters, err) == 256 && offsetof(EmitCounters, ticket) == 512 &&
+              offsetof(EmitCounters, cand_count) == 640 && offsetof(EmitCounters, cand_ticket) == 704 && offsetof(EmitCounters, n_items) == 768 &&
+              offsetof(EmitCounters, total_dense) == 832 && offsetof(EmitCounters, probe) == 896 && offsetof(EmitCounters, tflag) == 960, "EmitCounters layout");
+
+/* hbs_emit_annexb's workspace, sized by a.n, a.items_cap and a.first_cap (= a.cand_cap) */
+inline void lay_emit(Carver& w, EmitArgs& a)
+{
+    a.scan_tmp = w.take<unsigned long long>(1024 * 8);
+    a.nal_total = w.take<unsigned long long>((a.n + 1) * 8);
+    a.out_off = w.take<unsigned long long>((a.n + 1) * 8);
+    a.items = w.take<unsigned long long>(a.items_cap * 8);
+    const uint64_t clear_from = w.at;
+    a.desc = w.take<unsigned long long>(emit_desc_words(a.items_cap) * 8);
+    if (EmitCounters* const k = w.take<EmitCounters>(sizeof(EmitCounters))) {
+        a.total = &k->total; a.err = &k->err; a.ticket = &k->ticket; a.cand_count = &k->cand_count; a.cand_ticket = &k->cand_ticket;
+        a.n_items = &k->n_items; a.total_dense = &k->total_dense; a.probe = k->probe; a.tflag = k->tflag;
+    }
+    a.clear_bytes = w.at - clear_from;                      /* look-back words and the counters behind them */
+    a.first_k = w.take<unsigned long long>(a.first_cap * 8);
+    a.cand_list = w.take<uint32_t>(a.cand_cap * 4);
+    a.dz_table = w.take<uint32_t>(a.first_cap * emit_dz_table_words() * 4);
+}
+
+/* hbs_synth_rbsp's, sized by a.n */
+inline void lay_synth(Carver& w, SynthArgs& a)
+{
+    a.lens = w.take<unsigned long long>((a.n + 1) * 8);
+    a.offs = w.take<unsigned long long>((a.n + 1) * 8);
+    a.total = w.take<unsigned long long>(8);
+    a.err = w.take<uint32_t>(4);
+    a.scan_tmp = w.take<unsigned long long>(1024 * 8);
+}
 hipError_t launch_emit_annexb(const EmitArgs& a, hipStream_t st);
 /* the whole call in one launch of one workgroup (a few small NALs): no verdict words are written */
 bool emit_takes_small_path(uint64_t n, uint64_t rbsp_bytes, int two_pass);

@@ -18,7 +18,7 @@ struct FilterArgs {
     uint8_t* out; uint64_t out_cap;                   /* out NULL: plan only                          */
     hbs_nal_entry* index_out;                         /* nullable                                     */
     hbs_summary* summary;
-    /* scratch (filter_scratch) */
+    /* scratch (lay_filter) */
     unsigned long long* part;       /* 8 per plan block: unit bytes, kept NALs, kept rbsp bytes, kept non-empty units, inconsistent */
     unsigned long long* ctl;        /* 8: error, output bytes, non-empty kept units, kept NALs                        */
     unsigned long long* kept_out;   /* n_nals + 1: output offset of the j-th non-empty kept unit (then the total)     */
@@ -28,20 +28,15 @@ struct FilterArgs {
     hipEvent_t ev_begin, ev_end;    /* when non-null: recorded around the call's kernels                              */
 };
 
-/* scratch the call needs, and where each part lies in it */
-struct FilterScratch { uint64_t part, ctl, kept_out, kept_delta, tile_first, total; };
-HBS_HD FilterScratch filter_scratch(uint64_t n_nals, uint64_t tiles)
+/* the scratch the call needs, sized by a.n_nals and a.tiles */
+inline void lay_filter(Carver& w, FilterArgs& a)
 {
-    auto r256 = [](uint64_t v) { return (v + 255) & ~255ull; };
-    FilterScratch s;
-    const uint64_t blocks = (n_nals + kFilterNalsPerBlock - 1) / kFilterNalsPerBlock;
-    s.part = 0;
-    s.ctl = r256(blocks * 64);                         /* 8 words a plan block: 4 sums, the "inconsistent" flag, 3 spare */
-    s.kept_out = s.ctl + 256;
-    s.kept_delta = s.kept_out + r256((n_nals + 1) * 8);
-    s.tile_first = s.kept_delta + r256(n_nals * 8);
-    s.total = s.tile_first + r256((tiles + 1) * 8);
-    return s;
+    const uint64_t blocks = (a.n_nals + kFilterNalsPerBlock - 1) / kFilterNalsPerBlock;
+    a.part = w.take<unsigned long long>(blocks * 64);       /* 8 words a plan block: 4 sums, the "inconsistent" flag, 3 spare */
+    a.ctl = w.take<unsigned long long>(64);
+    a.kept_out = w.take<unsigned long long>((a.n_nals + 1) * 8);
+    a.kept_delta = w.take<unsigned long long>(a.n_nals * 8);
+    a.tile_first = w.take<unsigned long long>((a.tiles + 1) * 8);
 }
 
 hipError_t launch_filter_annexb(const FilterArgs& a, hipStream_t st);

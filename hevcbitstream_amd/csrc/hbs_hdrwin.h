@@ -24,6 +24,14 @@ struct HdrWinArgs {
 };
 
 uint64_t hdrwin_arena_bytes(uint64_t index_cap, uint32_t window, uint64_t stream_bytes);
+/* the windows' workspace, sized by a.arena_bytes and a.index_cap */
+inline void lay_hdrwin(Carver& w, HdrWinArgs& a)
+{
+    a.arena = w.take<uint8_t>(a.arena_bytes + 64);
+    a.idx2 = w.take<hbs_nal_entry>(a.index_cap * sizeof(hbs_nal_entry));
+    a.bump = w.take<unsigned long long>(16);
+    a.notes = w.take<void>(a.index_cap * 16);
+}
 hipError_t launch_hdr_strip(const HdrWinArgs& a, hipStream_t st);
 hipError_t launch_hdr_fix(const HdrWinArgs& a, void* parsed, hbs_summary* summary, unsigned long long* payload_off, hipStream_t st, int compact = 0);
 

@@ -88,5 +88,33 @@ struct WriteArgs {
 
 hipError_t launch_write_headers(const WriteArgs& a, hipStream_t st);
 
+/* What the workspaces of the parse and of hbs_write_headers have in common (the kernels they share rely on it), sized by a.n.
+ * Returns the 256 bytes behind `total`, which only the parse uses. */
+template <class Args> uint32_t* lay_headers_common(Carver& w, Args& a)
+{
+    a.slot_size = w.take<unsigned long long>((a.n + 1) * 8);
+    a.ctx_sps = w.take<long long>((a.n + 1) * 8);
+    a.ctx_pps = w.take<long long>((a.n + 1) * 8);
+    a.total = w.take<unsigned long long>(8);
+    uint32_t* const flags = w.take<uint32_t>(256);
+    a.scan_tmp = w.take<void>(1024 * 24);
+    a.own_rows = w.take<RpsRow>(parse_own_rows_bytes(a.n));
+    return flags;
+}
+/* the parse's: behind the common part, the exact re-walk's records (three words per NAL, a summary word per 256, the temporaries
+ * of its lanes) and, for a compact parse (a.compact set), the slots its re-walk has none to walk into */
+inline void lay_parse(Carver& w, ParseArgs& a)
+{
+    a.err = lay_headers_common(w, a);
+    a.div_flag = a.err ? a.err + 16 : nullptr;
+    a.deps = w.take<uint32_t>((a.n + 1) * 4);
+    a.wmask = w.take<uint32_t>((a.n + 1) * 4);
+    a.fix_list = w.take<uint32_t>((a.n + 1) * 4);
+    a.bsum = w.take<uint32_t>((a.n / 256 + 2) * 4);
+    a.fix_count = w.take<uint32_t>(256);
+    a.fix_temps = w.take<RpsRow>(parse_fix_temps_bytes());
+    a.fix_structs = a.compact ? w.take<uint8_t>(parse_fix_structs_bytes()) : nullptr;
+}
+
 } // namespace hbs
 #endif

@@ -3,6 +3,7 @@
 #define HBS_SCAN_H
 
 #include <hip/hip_runtime_api.h>
+#include <cassert>
 #include "hbs_common.h"
 
 namespace hbs {
@@ -64,6 +65,20 @@ void scan4r24_launch_kernel(const ScanArgs& a, uint64_t num_tiles, int gate, hip
 uint64_t scan4_ahead_entry_bytes();
 bool scan4_counts_ahead(uint64_t n);
 void launch_scan_ahead4(const ScanArgs& a, uint64_t num_tiles, int gate, hipStream_t st);
+/* its workspace for `tiles` tiles, packed: [AheadCtl | table | a word per tile | list] = 64 + tiles * scan4_ahead_entry_bytes().
+ * Returns the bytes in front of the list: what a new buffer has cleared (the call number, the tiles' words; table and list are
+ * written before they are read). */
+inline uint64_t lay_scan_ahead(Carver& w, ScanArgs& a, uint64_t tiles)
+{
+    const uint64_t word = sizeof(unsigned long long), listed = sizeof(uint32_t), entry = scan4_ahead_entry_bytes() - word - listed;
+    assert(entry == 64);                                     /* an entry's 64 + 8 + 4 bytes: the kernels index the table by AheadEntry */
+    a.ahead_ctl = w.take<AheadCtl>(sizeof(AheadCtl), 1);
+    a.ahead_tab = w.take<void>(tiles * entry, 1);
+    a.ahead_cand = w.take<unsigned long long>(tiles * word, 1);
+    const uint64_t cleared = w.at;
+    a.ahead_list = w.take<uint32_t>(tiles * listed, 1);
+    return cleared;
+}
 
 /* index-only streaming kernel (hbs_scan5.hip) */
 uint64_t scan5_workspace_bytes(uint64_t stream_bytes);     /* for any tile height the launcher may pick */

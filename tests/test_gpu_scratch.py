@@ -1,0 +1,296 @@
+"""The context's device scratch (hbs_capi.hip: one grow-only buffer per kind, carved by the layout functions next to each
+call's arguments): what a context holds after one call of each kind, to the byte; a context whose buffers all grow under it
+answers as a fresh one does; every timed call takes its slot of the timing ring."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests.test_gpu_au import fabricate
+from tests.test_gpu_carved import emit_arena, emit_index, stream_of
+
+pytestmark = pytest.mark.gpu
+
+# hbs_ctx_device_bytes() of a fresh context after the one call (or the few calls of the convenience wrapper) of SCRATCH_CASES,
+# measured with this module's own cases on the library of commit 9853dbe, the last one whose hbs_capi.hip sized and carved every
+# workspace by hand.  Exact: the sizes are arithmetic on the call's arguments (none of them depends on the device's compute
+# units: the look-back words, the padded tail tile and every workspace are sized by bytes, NALs and tiles alone).
+SCRATCH_BYTES = {
+    "scan of 400 KiB into an arena, dense tiles counted ahead": 197876,
+    "scan of 70 KiB without an arena": 479104,
+    "emit of 8 NALs": 208720,
+    "emit of 5000 NALs": 332368,
+    "synth_rbsp of 100 NALs": 208208,
+    "parse of 300 NALs": 30627408,
+    "compact parse of 300 NALs": 63657552,
+    "write_headers of 300 NALs": 574800,
+    "index_parse of 200 NALs": 38991504,
+    "filter of 300 NALs": 203344,
+    "access_units and au_keep of 300 NALs": 203600,
+}
+
+
+def new_ctx():
+    import hevcbitstream_amd as hbs
+    return hbs.Context(0)
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+def make_video():
+    """a synthetic elementary stream of 2400 NALs and more (slices of 700 to 900 bytes) and the index of its NALs"""
+    from tests.hevc_synth import stream_4k30
+    raw, count = stream_4k30(21, n_pictures=620, slices_per_picture=4, idr_every=20, payload_bytes=(700, 900))
+    assert count >= 2400
+    s = np.frombuffer(raw, dtype=np.uint8).copy()
+    ctx = new_ctx()
+    try:
+        idx, _, sm = ctx.index_extract(dev(s))
+    finally:
+        ctx.close()
+    assert int(sm["error"]) == 0 and len(idx) == count
+    return s, idx
+
+
+@pytest.fixture(scope="module")
+def video():
+    return make_video()
+
+
+def first_nals(video, n):
+    """the stream cut behind its n-th NAL"""
+    s, idx = video
+    return s[: int(idx["end"][n - 1])]
+
+
+def scanned(ctx, s, arena=True):
+    """hbs_index_extract on ordinary buffers -> (index tensor, entries, rbsp tensor, rbsp bytes, NALs)"""
+    import hevcbitstream_amd as hbs
+    index, rbsp, summary, cap = ctx.alloc_outputs(len(s), want_rbsp=arena)
+    ctx.index_extract_async(dev(s), index, cap, rbsp, summary)
+    sm = ctx.read_summary(summary)
+    assert int(sm["error"]) == 0, sm
+    n = int(sm["nal_count"])
+    return index, index[: n * 32].cpu().numpy().view(hbs.NAL_ENTRY).copy(), rbsp, int(sm["rbsp_bytes"]), n
+
+
+def au_records(ctx, n, seed):
+    return fabricate(np.random.default_rng(seed), n, 0.6, 0.3, off=int(ctx.lib.hbs_au_sps_poc_offset()))
+
+
+# ---- scratch held is what it was ----------------------------------------------------------------------------------------------
+
+def case_scan_arena(video):
+    ctx = new_ctx()
+    ctx.set_count_ahead(2)
+    scanned(ctx, stream_of(np.random.default_rng(7001), 1, 400 << 10, 0))
+    return ctx
+
+
+def case_scan_index_only(video):
+    ctx = new_ctx()
+    scanned(ctx, stream_of(np.random.default_rng(7002), 1, 70 << 10, 0), arena=False)
+    return ctx
+
+
+def emit_case(lens, seed):
+    rng = np.random.default_rng(seed)
+    arena, lens = emit_arena(rng, lens)
+    ctx = new_ctx()
+    ctx.emit_annexb(dev(arena), emit_index(lens, rng.integers(3, 9, size=len(lens))))
+    return ctx
+
+
+def case_emit_small(video):
+    return emit_case(np.array([40, 0, 7, 120, 33, 64, 1, 250]), 7003)
+
+
+def case_emit_5000(video):
+    return emit_case(np.random.default_rng(7004).integers(50, 151, size=5000), 7005)
+
+
+def case_synth(video):
+    import torch
+    ctx = new_ctx()
+    cap = int(ctx.lib.hbs_synth_rbsp_bound(100))
+    rbsp = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    index = torch.empty(100 * 32, dtype=torch.uint8, device="cuda")
+    summary = torch.zeros(64, dtype=torch.uint8, device="cuda")
+    ctx._bind_stream()
+    ctx._check(ctx.lib.hbs_synth_rbsp(ctx.h, 11, 100, 0, C.c_void_p(rbsp.data_ptr()), cap, C.c_void_p(index.data_ptr()),
+                                      C.c_void_p(summary.data_ptr())), "hbs_synth_rbsp")
+    assert int(ctx.read_summary(summary)["error"]) == 0
+    return ctx
+
+
+def parse_inputs(video, n=300):
+    """index and arena of the first n NALs, made by a context of their own"""
+    other = new_ctx()
+    try:
+        index, _, rbsp, _, found = scanned(other, first_nals(video, n))
+    finally:
+        other.close()
+    assert found == n
+    return index, rbsp
+
+
+def case_parse(video):
+    index, rbsp = parse_inputs(video)
+    ctx = new_ctx()
+    ctx.parse_headers(rbsp, index, 300)
+    return ctx
+
+
+def case_parse_compact(video):
+    index, rbsp = parse_inputs(video)
+    ctx = new_ctx()
+    ctx.parse_headers_compact(rbsp, index, 300)
+    return ctx
+
+
+def case_write_headers(video):
+    index, rbsp = parse_inputs(video)
+    other = new_ctx()
+    try:
+        parsed, structs = other.parse_headers(rbsp, index, 300)
+    finally:
+        other.close()
+    ctx = new_ctx()
+    ctx.write_headers(parsed, structs, 300, 2048)
+    return ctx
+
+
+def case_index_parse(video):
+    import torch
+    s = first_nals(video, 200)
+    ctx = new_ctx()
+    index = torch.empty(256 * 32, dtype=torch.uint8, device="cuda")
+    parsed = torch.empty(256 * 32, dtype=torch.uint8, device="cuda")
+    s1, s2 = torch.zeros(64, dtype=torch.uint8, device="cuda"), torch.zeros(64, dtype=torch.uint8, device="cuda")
+    assert ctx.index_parse_async(dev(s), index, 256, parsed, None, s1, s2) == 200           # (the plan: no struct arena)
+    assert int(ctx.read_summary(s2)["error"]) == 0
+    return ctx
+
+
+def case_filter(video):
+    s = first_nals(video, 300)
+    ctx = new_ctx()
+    ctx.filter_annexb(dev(s), video[1][:300], max_temporal_id_plus1=1)
+    return ctx
+
+
+def case_access_units(video):
+    ctx = new_ctx()
+    index, parsed, compact, structs = au_records(ctx, 300, 7006)
+    au, nal_au, _, _ = ctx.access_units(index, parsed, compact, dev(structs), 300)
+    ctx.au_keep(dev(nal_au), dev(parsed), 300, len(au) // 3, max(len(au) // 3, 1), param_sets=True)
+    return ctx
+
+
+SCRATCH_CASES = {
+    "scan of 400 KiB into an arena, dense tiles counted ahead": case_scan_arena,
+    "scan of 70 KiB without an arena": case_scan_index_only,
+    "emit of 8 NALs": case_emit_small,
+    "emit of 5000 NALs": case_emit_5000,
+    "synth_rbsp of 100 NALs": case_synth,
+    "parse of 300 NALs": case_parse,
+    "compact parse of 300 NALs": case_parse_compact,
+    "write_headers of 300 NALs": case_write_headers,
+    "index_parse of 200 NALs": case_index_parse,
+    "filter of 300 NALs": case_filter,
+    "access_units and au_keep of 300 NALs": case_access_units,
+}
+
+
+@pytest.mark.parametrize("name", list(SCRATCH_CASES))
+def test_scratch_held_is_what_it_was(video, name):
+    ctx = SCRATCH_CASES[name](video)
+    try:
+        got = ctx.device_bytes()
+    finally:
+        ctx.close()
+    print("device_bytes after", name, got)
+    assert got == SCRATCH_BYTES[name], (name, got, SCRATCH_BYTES[name])
+
+
+# ---- growing under a live context ---------------------------------------------------------------------------------------------
+
+def every_call(ctx, video, n):
+    """scan, emit, parse, filter and access units on the first n NALs -> {what: bytes}"""
+    out = {}
+    s = first_nals(video, n)
+    index, entries, rbsp, rbsp_bytes, found = scanned(ctx, s)
+    assert found == n
+    out["index"], out["arena"] = entries.view(np.uint8).copy(), rbsp[:rbsp_bytes].cpu().numpy()
+    back, entries_out = ctx.emit_annexb(rbsp[:rbsp_bytes], entries)
+    out["emitted"], out["emitted index"] = back.copy(), entries_out.view(np.uint8).copy()
+    parsed, structs = ctx.parse_headers(rbsp, index, n, poison=0xA5)
+    out["parsed"], out["structs"] = parsed.view(np.uint8).copy(), structs.cpu().numpy()
+    kept, kept_entries, sm = ctx.filter_annexb(dev(s), entries, keep_types=~(1 << 34))             # (without the PPSs)
+    out["filtered"], out["filtered index"], out["filter summary"] = kept.cpu().numpy(), kept_entries.view(np.uint8).copy(), sm.tobytes()
+    au_index, au_parsed, compact, au_structs = au_records(ctx, n, 7100 + n)
+    au, nal_au, sm, carry = ctx.access_units(au_index, au_parsed, compact, dev(au_structs), n)
+    out["aus"], out["nal_au"], out["au summary"], out["carry"] = au.view(np.uint8).copy(), nal_au.copy(), sm.tobytes(), carry.tobytes()
+    return out
+
+
+def test_buffers_grow_under_a_live_context(video):
+    small, large = 300, 2400
+    want = {}
+    for n in (small, large):
+        fresh = new_ctx()
+        fresh.set_count_ahead(2)
+        try:
+            want[n] = every_call(fresh, video, n)
+        finally:
+            fresh.close()
+    assert np.array_equal(want[small]["emitted"], first_nals(video, small)), "the way back gives the stream"
+    ctx = new_ctx()
+    ctx.set_count_ahead(2)
+    try:
+        held = []
+        for run, n in enumerate((small, large, small)):
+            got = every_call(ctx, video, n)
+            held.append(ctx.device_bytes())
+            print("run", run, "NALs", n, "device_bytes", held[-1])
+            assert got.keys() == want[n].keys()
+            for what, w in want[n].items():
+                g = got[what]
+                assert (np.array_equal(g, w) if isinstance(w, np.ndarray) else g == w), ("run", run, "NALs", n, what, "differs from a fresh context's")
+    finally:
+        ctx.close()
+    assert held[1] > held[0], held
+    assert held[2] >= held[1], held
+
+
+# ---- timing slots -------------------------------------------------------------------------------------------------------------
+
+def test_every_timed_call_takes_a_slot(video):
+    import torch
+    s = first_nals(video, 300)
+    ctx = new_ctx()
+    try:
+        index, entries, rbsp, _, n = scanned(ctx, s)
+        records = [dev(r) for r in au_records(ctx, n, 7200)]
+        summary = torch.zeros(64, dtype=torch.uint8, device="cuda")
+        ctx.enable_timing(True)
+        d = dev(s)
+        ctx.index_extract_async(d, index, n + 1, rbsp, summary)
+        ctx.filter_annexb_async(d, len(s), index, n, None, None, summary, rule=ctx.nal_filter())
+        assert ctx.access_units_async(records[0], records[1], records[2], records[3], n, None, 0, None, None, summary) == 0
+        ms = [ctx.kernel_ms_back(back) for back in range(3)]
+        print("access units, filter, scan: ms", ms)
+        assert all(m > 0 for m in ms), ms
+        assert ctx.kernel_ms() == ms[0]
+        with pytest.raises(Exception):
+            ctx.kernel_ms_back(3)
+        # a scan of no bytes launches nothing and takes no slot: the last timed call is still the one reported
+        ctx.index_extract_async(torch.empty(0, dtype=torch.uint8, device="cuda"), index, n + 1, rbsp, summary)
+        assert ctx.kernel_ms() == ms[0] and ctx.kernel_ms_back(0) == ms[0]
+        with pytest.raises(Exception):
+            ctx.kernel_ms_back(3)
+    finally:
+        ctx.close()
