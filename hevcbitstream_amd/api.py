@@ -54,7 +54,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_ctx_set_sequential_parse", "hbs_ctx_set_emit_path", "hbs_parse_extended",
            "hbs_comm_unique_id", "hbs_comm_create", "hbs_comm_adopt", "hbs_comm_destroy", "hbs_comm_rank", "hbs_comm_world", "hbs_comm_reserve_hint", "hbs_parse_headers_compact", "hbs_parse_materialize", "hbs_index_parse_compact", "hbs_gather_parts", "hbs_index_parse", "hbs_ctx_reserve_workgroups",
            "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
-           "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset"]
+           "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset",
+           "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -182,6 +183,10 @@ def load_library():
                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hbs_au_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
     lib.hbs_au_sps_poc_offset.argtypes = []
+    lib.hbs_annexb_to_lenpref.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.hbs_lenpref_to_annexb.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.hbs_au_sps_poc_offset.restype = C.c_uint64
     _lib = lib
     return lib
@@ -668,6 +673,108 @@ class Context:
             raise HbsError("hbs_filter_annexb: error %d" % int(s["error"]))
         kept = int(s["nal_count"])
         return out[:need], d_out_idx[: kept * NAL_ENTRY.itemsize].cpu().numpy().view(NAL_ENTRY).copy(), s
+
+    # ---- length-prefixed NAL units (MP4 samples) ---------------------------------------
+
+    def annexb_to_lenpref_async(self, stream, stream_bytes, index, n_nals, out, index_out, summary, keep=None, length_size=4,
+                                nal_au=None, n_aus=0, sample_off=None, out_cap=None):
+        """Enqueue hbs_annexb_to_lenpref on the current torch stream.  stream / index / out / index_out / summary / keep / nal_au /
+        sample_off are device tensors (out None: plan only; index_out, keep, nal_au, sample_off may be None).  Returns the
+        call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        return self.lib.hbs_annexb_to_lenpref(self.h, p(stream) if stream_bytes else None, int(stream_bytes),
+                                              p(index) if n_nals else None, int(n_nals), p(keep), int(length_size),
+                                              p(nal_au), int(n_aus), p(sample_off), p(out), int(out_cap), p(index_out), p(summary))
+
+    def lenpref_to_annexb_async(self, data, in_bytes, sample_off, sample_size, n_samples, out, sample_off_out, summary,
+                                length_size=4, startcode_bytes=4, nal_cap=0, out_cap=None):
+        """Enqueue hbs_lenpref_to_annexb on the current torch stream.  data / sample_off / sample_size / out / sample_off_out /
+        summary are device tensors (out None: plan only; sample_off_out may be None).  Returns the call's return code."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        return self.lib.hbs_lenpref_to_annexb(self.h, p(data) if in_bytes else None, int(in_bytes), int(length_size),
+                                              p(sample_off) if n_samples else None, p(sample_size) if n_samples else None,
+                                              int(n_samples), int(startcode_bytes), int(nal_cap), p(out), int(out_cap),
+                                              p(sample_off_out), p(summary))
+
+    def annexb_to_lenpref(self, stream, index_entries, keep=None, length_size=4, nal_au=None, n_aus=0, stream_bytes=None):
+        """Convenience: the kept NAL units of `stream` (device uint8 tensor) as length-prefixed records.  index_entries:
+        ndarray[NAL_ENTRY] (host) or a device uint8 tensor of its entries; keep: None (all) or n_nals bytes, host or device;
+        nal_au: None or the AU number of every NAL (uint32, host or device) with n_aus, for the sample table.  Plans first,
+        allocates the exact output, runs.  Returns (out device tensor, entries_out ndarray[NAL_ENTRY], sample_off ndarray[uint64]
+        of n_aus + 1 or None, summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        if isinstance(index_entries, np.ndarray):
+            n = len(index_entries)
+            d_idx = t.from_numpy(np.ascontiguousarray(index_entries).view(np.uint8).copy()).to(dev) if n else None
+        else:
+            n = index_entries.numel() // NAL_ENTRY.itemsize
+            d_idx = index_entries
+        nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
+        d_keep = keep
+        if isinstance(keep, np.ndarray):
+            d_keep = t.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8).copy()).to(dev) if n else t.zeros(16, dtype=t.uint8, device=dev)
+        d_au = nal_au
+        if isinstance(nal_au, np.ndarray):
+            d_au = t.from_numpy(np.ascontiguousarray(nal_au, dtype=np.uint32).view(np.uint8).copy()).to(dev) if n else t.zeros(16, dtype=t.uint8, device=dev)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        args = dict(keep=d_keep, length_size=length_size, nal_au=d_au, n_aus=n_aus)
+        self._check(self.annexb_to_lenpref_async(stream, nbytes, d_idx, n, None, None, summary, **args), "hbs_annexb_to_lenpref")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_annexb_to_lenpref: error %d" % int(s["error"]))
+        need = int(s["stream_bytes"])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        d_out_idx = t.empty(max(n, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
+        d_so = t.empty((int(n_aus) + 1) * 8, dtype=t.uint8, device=dev) if d_au is not None else None
+        self._check(self.annexb_to_lenpref_async(stream, nbytes, d_idx, n, out, d_out_idx, summary, sample_off=d_so, out_cap=need, **args),
+                    "hbs_annexb_to_lenpref")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_annexb_to_lenpref: error %d" % int(s["error"]))
+        kept = int(s["nal_count"])
+        return (out[:need], d_out_idx[: kept * NAL_ENTRY.itemsize].cpu().numpy().view(NAL_ENTRY).copy(),
+                d_so.cpu().numpy().view(np.uint64).copy() if d_so is not None else None, s)
+
+    def lenpref_to_annexb(self, data, sample_off, sample_size, length_size=4, startcode_bytes=4, in_bytes=None):
+        """Convenience: the samples data[off_s, off_s + size_s) (sample_off / sample_size: uint64 arrays, host or device
+        tensors of their bytes) as one Annex-B stream.  Plans first, allocates the exact output, runs.  Returns (out device
+        tensor, sample_off_out ndarray[uint64] of n_samples + 1, summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x):
+            if isinstance(x, np.ndarray):
+                a = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8)
+                return (t.from_numpy(a.copy()).to(dev) if a.size else t.zeros(16, dtype=t.uint8, device=dev)), len(x)
+            return x, x.numel() * x.element_size() // 8
+        d_off, n = dv(sample_off)
+        d_size, n2 = dv(sample_size)
+        if n != n2:
+            raise HbsError("hbs_lenpref_to_annexb: %d sample offsets, %d sizes" % (n, n2))
+        nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        args = dict(length_size=length_size, startcode_bytes=startcode_bytes)
+        self._check(self.lenpref_to_annexb_async(data, nbytes, d_off, d_size, n, None, None, summary, nal_cap=(1 << 64) - 1, **args),
+                    "hbs_lenpref_to_annexb")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_lenpref_to_annexb: error %d (sample %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        need, recs = int(s["stream_bytes"]), int(s["nal_count"])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        d_so = t.empty((n + 1) * 8, dtype=t.uint8, device=dev)
+        self._check(self.lenpref_to_annexb_async(data, nbytes, d_off, d_size, n, out, d_so, summary, nal_cap=recs, out_cap=need, **args),
+                    "hbs_lenpref_to_annexb")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_lenpref_to_annexb: error %d" % int(s["error"]))
+        return out[:need], d_so.cpu().numpy().view(np.uint64).copy(), s
 
     # ---- access units -----------------------------------------------------------------
 

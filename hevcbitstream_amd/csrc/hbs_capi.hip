@@ -18,6 +18,7 @@
 #include "hbs_parse.h"
 #include "hbs_parse_compact.h"
 #include "hbs_filter.h"
+#include "hbs_lenpref.h"
 #include "hbs_au.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
@@ -31,8 +32,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kZeros  sizeof(hevc_sps_t) zero bytes: the "no parameter set yet" structs
  * kFws    hbs_filter_annexb's scratch
  * kAws    hbs_access_units' scratch.  hbs_au_keep uses its first 16 bytes (where hbs_access_units keeps its digest): the calls
- *         of a context are ordered by its one stream, so neither sees the other's data */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kBufs };
+ *         of a context are ordered by its one stream, so neither sees the other's data
+ * kLws    the scratch of hbs_annexb_to_lenpref and hbs_lenpref_to_annexb */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -595,6 +597,80 @@ int hbs_filter_annexb(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_filter_annexb(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_filter_annexb");
+}
+
+namespace {
+/* the output tiles a grid covers for an output of at most `reach` bytes (what a grid can hold is far beyond device memory) */
+uint64_t lenpref_tiles(uint64_t reach)
+{
+    const uint64_t t = reach / hbs::kLenprefTileBytes + (reach % hbs::kLenprefTileBytes ? 1 : 0);
+    return t < 0x7FFFFFFFull ? t : 0x7FFFFFFFull;
+}
+}
+
+int hbs_annexb_to_lenpref(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                          const hbs_nal_entry* d_index, uint64_t n_nals, const uint8_t* d_keep, int length_size,
+                          const uint32_t* d_nal_au, uint64_t n_aus, uint64_t* d_sample_off,
+                          uint8_t* d_out, uint64_t out_cap, hbs_nal_entry* d_index_out, hbs_summary* d_summary)
+{
+    if (!c || !d_summary || (length_size != 1 && length_size != 2 && length_size != 4)) return HBS_E_ARG;
+    if (n_nals && (!d_index || (stream_bytes && !d_stream))) return HBS_E_ARG;
+    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_index, 7) ||
+        misaligned(d_index_out, 7) || misaligned(d_sample_off, 7) || misaligned(d_nal_au, 3)) {
+        snprintf(c->err, sizeof(c->err), "stream/output/summary pointers must be 16-byte aligned, index and sample table 8-byte, AU numbers 4-byte");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::A2lArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals; a.keep = d_keep;
+    a.nal_au = d_nal_au; a.n_aus = n_aus; a.sample_off = d_nal_au ? reinterpret_cast<unsigned long long*>(d_sample_off) : nullptr;
+    a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
+    a.t.src = d_stream; a.t.out = d_out; a.t.prefix = (uint32_t)length_size; a.t.prefix_is_length = 1;
+    const uint64_t most = stream_bytes + n_nals * (uint64_t)length_size;                    /* the output is at most this long */
+    a.t.tiles = d_out ? lenpref_tiles(out_cap < most ? out_cap : most) : 0;
+    const int rc = carve(c, c->buf[kLws], "hipMalloc(lenpref scratch)", [&](hbs::Carver& w) { hbs::lay_a2l(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_annexb_to_lenpref(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_annexb_to_lenpref");
+}
+
+int hbs_lenpref_to_annexb(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, int length_size,
+                          const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
+                          int startcode_bytes, uint64_t nal_cap, uint8_t* d_out, uint64_t out_cap,
+                          uint64_t* d_sample_off_out, hbs_summary* d_summary)
+{
+    if (!c || !d_summary || (length_size != 1 && length_size != 2 && length_size != 4) ||
+        (startcode_bytes != 3 && startcode_bytes != 4)) return HBS_E_ARG;
+    if (n_samples && (!d_sample_off || !d_sample_size || (in_bytes && !d_in))) return HBS_E_ARG;
+    if (misaligned(d_in, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_sample_off, 7) ||
+        misaligned(d_sample_size, 7) || misaligned(d_sample_off_out, 7)) {
+        snprintf(c->err, sizeof(c->err), "input/output/summary pointers must be 16-byte aligned, sample tables 8-byte aligned");
+        return HBS_E_ARG;
+    }
+    if (d_out && out_cap > hbs::kLenprefOutCapMax) {
+        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::L2aArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = in_bytes; a.length_size = (uint32_t)length_size;
+    a.sample_off = reinterpret_cast<const unsigned long long*>(d_sample_off);
+    a.sample_size = reinterpret_cast<const unsigned long long*>(d_sample_size); a.n_samples = n_samples;
+    /* what sizes the piece table: a record is at least its start code in the output, so more than out_cap / startcode_bytes
+     * records do not fit out_cap either (HBS_E_CAPACITY) and the place kernel never sees them */
+    const uint64_t fit = out_cap / (uint64_t)startcode_bytes;
+    a.nal_cap = nal_cap; a.piece_cap = d_out ? (nal_cap < fit ? nal_cap : fit) : 0; a.out_cap = out_cap;
+    a.sample_off_out = reinterpret_cast<unsigned long long*>(d_sample_off_out); a.summary = d_summary;
+    a.t.src = d_in; a.t.out = d_out; a.t.prefix = (uint32_t)startcode_bytes; a.t.prefix_is_length = 0;
+    a.t.tiles = d_out ? lenpref_tiles(out_cap) : 0;              /* (samples may overlap: the input's size bounds nothing; out_cap is bounded above) */
+    const int rc = carve(c, c->buf[kLws], "hipMalloc(lenpref scratch)", [&](hbs::Carver& w) { hbs::lay_l2a(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_lenpref_to_annexb(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_lenpref_to_annexb");
 }
 
 uint64_t hbs_au_sps_poc_offset(void) { return offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4); }

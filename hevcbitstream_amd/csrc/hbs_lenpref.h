@@ -1,0 +1,85 @@
+/* hbs_lenpref.h -- host-visible launchers of hbs_annexb_to_lenpref / hbs_lenpref_to_annexb (hbs_lenpref.hip). */
+#ifndef HBS_LENPREF_H
+#define HBS_LENPREF_H
+
+#include <hip/hip_runtime_api.h>
+#include "hbs_common.h"
+
+namespace hbs {
+
+constexpr int kLenprefNalsPerBlock = 2048;           /* forward plan: 256 lanes x 8 consecutive NALs        */
+constexpr int kLenprefSamplesPerBlock = 256;         /* reverse plan: one lane per sample                   */
+constexpr uint64_t kLenprefTileBytes = 64 * 1024;    /* copy: output bytes of one workgroup                 */
+constexpr uint64_t kLenprefOutCapMax = 1ull << 46;   /* reverse: out_cap sizes scratch and grid (2^30 tiles, < 2^45 pieces: no size wraps) */
+
+/* What the copy kernel works on.  Piece j is the output bytes [piece_out[j], piece_out[j + 1]): `prefix` literal bytes, then
+ * source bytes; output byte o of its payload is src[o + piece_delta[j]]. */
+struct PieceTable {
+    const uint8_t* src;
+    uint8_t* out;                   /* NULL: plan only                                                              */
+    uint32_t prefix;                /* bytes of the literal in front of each payload: length_size / startcode_bytes */
+    int prefix_is_length;           /* 1: the payload's length, big-endian; 0: 00 .. 00 01                          */
+    unsigned long long* ctl;        /* 8: error, output bytes, pieces                                               */
+    unsigned long long* piece_out;  /* pieces + 1: output offset of piece j (then the total)                        */
+    unsigned long long* piece_delta;/* pieces: source offset minus output offset of its payload                     */
+    unsigned long long* tile_first; /* tiles + 1: the piece the output tile's first byte lies in                    */
+    uint64_t tiles;                 /* output tiles the grid covers                                                 */
+};
+
+struct A2lArgs {
+    uint64_t n;                                       /* stream bytes                                          */
+    const hbs_nal_entry* index; uint64_t n_nals;
+    const uint8_t* keep;                              /* NULL: all                                             */
+    const uint32_t* nal_au; uint64_t n_aus;           /* nal_au NULL: no sample table                          */
+    unsigned long long* sample_off;                   /* nullable                                              */
+    uint64_t out_cap;
+    hbs_nal_entry* index_out;                         /* nullable                                              */
+    hbs_summary* summary;
+    PieceTable t;
+    unsigned long long* part;       /* 8 per plan block: record bytes, kept NALs, kept rbsp bytes, 1 if anything was wrong */
+    hipEvent_t ev_begin, ev_end;    /* when non-null: recorded around the call's kernels               */
+};
+
+struct L2aArgs {
+    uint64_t n;                                       /* input bytes                                           */
+    uint32_t length_size;                             /* bytes of a length field: 1, 2 or 4                    */
+    const unsigned long long* sample_off; const unsigned long long* sample_size; uint64_t n_samples;
+    uint64_t nal_cap, out_cap;
+    uint64_t piece_cap;                               /* records the piece table holds: min(nal_cap, out_cap / start code), 0 plan-only */
+    unsigned long long* sample_off_out;               /* nullable                                              */
+    hbs_summary* summary;
+    PieceTable t;
+    unsigned long long* part;       /* 8 per plan block: output bytes, records, -, 1 + the lowest malformed sample (0: none) */
+    unsigned long long* samp;       /* 2 per sample: its output bytes, its records                                          */
+    hipEvent_t ev_begin, ev_end;
+};
+
+inline void lay_pieces(Carver& w, PieceTable& t, uint64_t piece_cap)
+{
+    t.ctl = w.take<unsigned long long>(64);
+    t.piece_out = w.take<unsigned long long>((piece_cap + 1) * 8);
+    t.piece_delta = w.take<unsigned long long>(piece_cap * 8);
+    t.tile_first = w.take<unsigned long long>((t.tiles + 1) * 8);
+}
+
+/* the scratch the calls need, sized by n_nals / n_samples and nal_cap, and by t.tiles */
+inline void lay_a2l(Carver& w, A2lArgs& a)
+{
+    const uint64_t blocks = (a.n_nals + kLenprefNalsPerBlock - 1) / kLenprefNalsPerBlock;
+    a.part = w.take<unsigned long long>(blocks * 64);
+    lay_pieces(w, a.t, a.t.out ? a.n_nals : 0);            /* (a plan-only call fills no piece table) */
+}
+
+inline void lay_l2a(Carver& w, L2aArgs& a)
+{
+    const uint64_t blocks = (a.n_samples + kLenprefSamplesPerBlock - 1) / kLenprefSamplesPerBlock;
+    a.part = w.take<unsigned long long>(blocks * 64);
+    a.samp = w.take<unsigned long long>(a.n_samples * 16);
+    lay_pieces(w, a.t, a.piece_cap);
+}
+
+hipError_t launch_annexb_to_lenpref(const A2lArgs& a, hipStream_t st);
+hipError_t launch_lenpref_to_annexb(const L2aArgs& a, hipStream_t st);
+
+} // namespace hbs
+#endif

@@ -310,6 +310,90 @@ int hbs_filter_annexb(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_byt
                       hbs_nal_entry* d_index_out, hbs_summary* d_summary);
 
 /*
+ * Length-prefixed NAL units: the framing of an MP4 / ISOBMFF `hvc1` sample (ISO/IEC 14496-15), of Matroska and of RTP
+ * aggregation.  Each NAL unit is a RECORD: a big-endian length field of L = length_size bytes (1, 2 or 4: lengthSizeMinusOne
+ * + 1 of hvcC) followed by that many payload bytes; a SAMPLE is one access unit's records back to back.  The two calls convert
+ * between this and Annex-B on the device.  Throughout, any other length_size returns HBS_E_ARG at once.
+ *
+ * hbs_annexb_to_lenpref: Annex-B stream + index (+ keep mask, + the AU number of every NAL) -> records (+ sample table).
+ *
+ *   d_keep        n_nals bytes, non-zero = keep (hbs_au_keep writes this); NULL: every NAL is kept
+ *   d_nal_au      optional: n_nals AU numbers, as hbs_access_units wrote them; n_aus = its AU count.  NULL: no sample table
+ *                 (n_aus and d_sample_off are ignored)
+ *   d_sample_off  with d_nal_au: n_aus + 1 offsets (optional even then: the AU table is checked either way)
+ *   d_out         the output; NULL = plan only: only d_summary is written, stream_bytes = the output's size
+ *   d_index_out   optional: room for n_nals entries
+ *
+ * The output is the records of the kept NALs in index order, back to back.  The record of NAL k is L bytes holding
+ * end_k - start_k big-endian, then stream[start_k, end_k) verbatim; a kept NAL with end == start is a record of L zero bytes.
+ * Nothing between NALs (zeros, start codes, junk) is copied.  d_index_out[j] describes the j-th kept NAL: start and end are
+ * its payload's offsets in the output (behind the length field), rbsp_len is copied, rbsp_off is the running sum of the kept
+ * rbsp_len, status is the input status with HBS_ST_UNTERMINATED cleared.
+ * Sample table: d_sample_off[a], a = 0 .. n_aus, is the sum of the record bytes of the kept NALs k with d_nal_au[k] < a, so
+ * sample a is out[d_sample_off[a], d_sample_off[a + 1]) and an AU with nothing kept is an empty sample.  The AU numbers are
+ * checked, not trusted: d_nal_au[0] == 0, each step d_nal_au[k] - d_nal_au[k-1] is 0 or 1, d_nal_au[n_nals-1] == n_aus - 1;
+ * with n_nals == 0, n_aus must be 0.
+ * d_summary: nal_count = kept NALs, nal_found = n_nals, rbsp_bytes = sum of the kept rbsp_len, stream_bytes = output bytes,
+ * stop_reason = 0, reserved = 0.  error = HBS_E_ARG when the index is inconsistent by hbs_filter_annexb's definition
+ * (start > end, end > stream_bytes or start_k < end_{k-1}; each entry is checked before it is used), when a kept NAL has
+ * end - start > 2^(8 L) - 1, or when the AU numbers break a rule above; else HBS_E_CAPACITY when out_cap is smaller than the
+ * output (the sizes in the summary are right then; with HBS_E_ARG nal_count, rbsp_bytes and stream_bytes mean nothing).  On
+ * either error nothing is written to d_out, d_index_out or d_sample_off.  n_nals = 0 is valid (empty output, d_sample_off[0] = 0).
+ * Nothing outside [d_out, d_out + output bytes) is stored, no load touches a 16-byte granule that holds no byte of the
+ * stream, and the call does not synchronise with the host.
+ * Alignment: d_stream, d_out, d_summary 16 bytes; d_index, d_index_out, d_sample_off 8 bytes; d_nal_au 4 bytes; d_keep any byte.
+ *
+ * hbs_lenpref_to_annexb: samples of records anywhere in a buffer -> one Annex-B stream.
+ *
+ *   d_sample_off / d_sample_size   n_samples each: sample s is d_in[off_s, off_s + size_s).  Samples may lie anywhere in the
+ *                 buffer, in any order, overlap, and have other data between them (an mdat with interleaved tracks)
+ *   startcode_bytes   3: 00 00 01, 4: 00 00 00 01 in front of every NAL unit (anything else: HBS_E_ARG at once)
+ *   nal_cap       the most records the call may find: with out_cap it sizes the scratch, as index_cap does elsewhere
+ *   d_out         the output; NULL = plan only: only d_summary is written (and nal_cap and out_cap size nothing)
+ *   out_cap       bytes of room at d_out.  It sizes the copy's grid and the scratch -- 8 bytes a 64 KiB of out_cap, 16 bytes a
+ *                 record for min(nal_cap, out_cap / startcode_bytes) records -- so pass what the plan gave, not "plenty";
+ *                 with d_out, an out_cap above 2^46 is refused with HBS_E_ARG at once (nal_cap may be anything, UINT64_MAX
+ *                 for "no limit" included)
+ *   d_sample_off_out  optional: n_samples + 1 offsets
+ *
+ * A sample is a chain of records: at p, L bytes of big-endian length n, then n payload bytes, then the next record at
+ * p + L + n, until p reaches the sample's end.  The output is, for every sample in table order and every record in chain
+ * order, the start code and then the payload; a zero-length record gives a bare start code.  d_sample_off_out[s] = the output
+ * offset where sample s begins, entry n_samples the total.  No index is produced: run hbs_index_extract on the output.
+ * Scanning it (find_nal_unit's walk) finds exactly the payloads, in order, as long as no payload but the last ends in 00 and
+ * none holds 00 00 00 or 00 00 01 -- which holds for payloads that such a walk found (a found payload never ends in 00 unless
+ * it is the stream's last, so the start code behind it cannot shorten it).  One exception, at the output's end: a last record
+ * of length 0 behind a 3-byte start code, with a record in front of it, is not found, and the payload in front of it comes out
+ * three bytes longer (the walk's `i+3 >= size` rule ends it at the buffer's end before the last start code is looked at).
+ * A walk does yield such an index: a stream that ends in 00 00 00 01 behind a NAL has an empty last NAL; 4-byte codes keep it.
+ * d_summary: nal_count = records, nal_found = n_samples, stream_bytes = output bytes, rbsp_bytes = 0, stop_reason = -1 if
+ * nal_count > 0, else 0.  error = HBS_E_ARG when a sample leaves the buffer (off + size > in_bytes, or the sum wraps) or a
+ * chain is malformed (fewer than L bytes left in front of the sample's end, or a length larger than what is left); then
+ * reserved[0] = 1 + the lowest such sample (0 otherwise), and nal_count / stream_bytes count the well-formed records in front
+ * of each sample's end or fault (none for a sample that leaves the buffer).  Else error = HBS_E_CAPACITY when
+ * nal_count > nal_cap or out_cap is smaller than the output; the counts are right.  On an error nothing is written to d_out
+ * or d_sample_off_out.  n_samples = 0 is valid.
+ * The chain is the one sequential thing here and it is per sample: one lane walks one sample (twice: to count, and to place
+ * once the offsets are known), so a single sample with very many records is walked by one lane, at the latency of one
+ * dependent load a record.
+ * The same store and load guarantees as above (loads: 16-byte granules that hold a byte of d_in[0, in_bytes)); no host
+ * synchronisation.  Alignment: d_in, d_out, d_summary 16 bytes; d_sample_off, d_sample_size, d_sample_off_out 8 bytes.
+ */
+int hbs_annexb_to_lenpref(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
+                          const hbs_nal_entry* d_index, uint64_t n_nals,
+                          const uint8_t* d_keep /* n_nals bytes, non-zero = keep; NULL: all */,
+                          int length_size,
+                          const uint32_t* d_nal_au /* optional: AU number per NAL, as hbs_access_units wrote it */,
+                          uint64_t n_aus, uint64_t* d_sample_off /* n_aus + 1, with d_nal_au */,
+                          uint8_t* d_out, uint64_t out_cap,
+                          hbs_nal_entry* d_index_out /* optional, n_nals entries */, hbs_summary* d_summary);
+int hbs_lenpref_to_annexb(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, int length_size,
+                          const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
+                          int startcode_bytes /* 3: 00 00 01, 4: 00 00 00 01 */, uint64_t nal_cap,
+                          uint8_t* d_out, uint64_t out_cap,
+                          uint64_t* d_sample_off_out /* optional, n_samples + 1 */, hbs_summary* d_summary);
+
+/*
  * K4: header parse, one NAL per lane (64 per wavefront), over the RBSP arena and index that
  * hbs_index_extract produced.  For NAL k it does what read_hevc_nal_unit()
  * does after nal_to_rbsp (hevc_stream.c:175-239): NAL header, then by type the
