@@ -28,6 +28,14 @@ ACCESS_UNIT = np.dtype([("first_nal", "<u8"), ("unit_begin", "<u8"), ("unit_end"
 AU_CARRY = np.dtype([("flags", "<u4"), ("anchor_poc_lsb", "<i4"), ("anchor_poc_msb", "<i4"), ("reserved", "<u4")])
 AU_IRAP, AU_IDR, AU_CVS_START, AU_ANCHOR, AU_NO_PICTURE, AU_DAMAGED, AU_PARAM_SETS, AU_END_OF_SEQ = 1, 2, 4, 8, 16, 32, 64, 128
 AUKEEP_PARAM_SETS = 1
+# layout of hbs_ts_pes / hbs_ts_packet, the packet classes and the flags of hbs_ts_demux
+TS_PES = np.dtype([("out_off", "<u8"), ("pts", "<u8"), ("dts", "<u8"), ("packet", "<u4"), ("flags", "<u4")])
+TS_PACKET = np.dtype([("cls", "<i4"), ("pid", "<u4"), ("off", "<u4"), ("len", "<u4"), ("es_off", "<u4"), ("es_len", "<u4"),
+                      ("cc", "<u4"), ("flags", "<u4"), ("pts", "<u8"), ("dts", "<u8")])
+TS_FAULT, TS_OTHER, TS_SKIPPED, TS_NO_PAYLOAD, TS_PAYLOAD, TS_PES_START = -1, 0, 1, 2, 3, 4
+TS_F_PTS, TS_F_DTS, TS_F_RANDOM_ACCESS, TS_F_DISCONTINUITY, TS_F_DATA_ALIGNED = 1, 2, 4, 8, 16
+TS_NO_TIME = (1 << 64) - 1
+STREAM_TYPE_HEVC = 0x24
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -55,7 +63,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_comm_unique_id", "hbs_comm_create", "hbs_comm_adopt", "hbs_comm_destroy", "hbs_comm_rank", "hbs_comm_world", "hbs_comm_reserve_hint", "hbs_parse_headers_compact", "hbs_parse_materialize", "hbs_index_parse_compact", "hbs_gather_parts", "hbs_index_parse", "hbs_ctx_reserve_workgroups",
            "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
            "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset",
-           "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb"]
+           "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb",
+           "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -188,8 +197,34 @@ def load_library():
     lib.hbs_lenpref_to_annexb.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
                                           C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.hbs_au_sps_poc_offset.restype = C.c_uint64
+    lib.hbs_ts_demux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                 C.c_void_p]
+    lib.hbs_ts_packet_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.hbs_ts_find_pid_host.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int)]
     _lib = lib
     return lib
+
+
+def ts_packet(packet, pid, packet_bytes=188):
+    """hbs_ts_packet_host: the packet rule of hbs_ts_demux for one packet (bytes or a uint8 array of packet_bytes bytes) in host
+    memory -> a TS_PACKET record.  No GPU involved."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(packet), dtype=np.uint8) if isinstance(packet, (bytes, bytearray)) else packet, dtype=np.uint8)
+    if len(a) != packet_bytes:
+        raise HbsError("hbs_ts_packet_host: %d bytes given, packets are %d" % (len(a), packet_bytes))
+    out = np.zeros(1, dtype=TS_PACKET)
+    rc = load_library().hbs_ts_packet_host(a.ctypes.data, int(packet_bytes), int(pid), out.ctypes.data)
+    if rc != 0:
+        raise HbsError("hbs_ts_packet_host failed: %d" % rc)
+    return out[0]
+
+
+def ts_find_pid(head, packet_bytes=188, stream_type=STREAM_TYPE_HEVC):
+    """hbs_ts_find_pid_host: (PID, program number) of the first elementary stream of `stream_type` in the first program of the
+    transport stream whose first bytes are `head` (bytes or a uint8 array, host memory), or None.  No GPU involved."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(head), dtype=np.uint8) if isinstance(head, (bytes, bytearray)) else head, dtype=np.uint8)
+    prog = C.c_int(0)
+    pid = load_library().hbs_ts_find_pid_host(a.ctypes.data if len(a) else None, len(a), int(packet_bytes), int(stream_type), C.byref(prog))
+    return None if pid < 0 else (pid, prog.value)
 
 
 class Context:
@@ -775,6 +810,40 @@ class Context:
         if int(s["error"]) != 0:
             raise HbsError("hbs_lenpref_to_annexb: error %d" % int(s["error"]))
         return out[:need], d_so.cpu().numpy().view(np.uint64).copy(), s
+
+    # ---- MPEG transport stream -----------------------------------------------------------
+
+    def ts_demux_async(self, ts, ts_bytes, packet_bytes, pid, out, pes, summary, out_cap=None, pes_cap=None):
+        """Enqueue hbs_ts_demux on the current torch stream.  ts / out / pes / summary are device tensors (out None: plan only;
+        pes may be None).  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        if pes_cap is None:
+            pes_cap = pes.numel() * pes.element_size() // TS_PES.itemsize if pes is not None else 0
+        return self.lib.hbs_ts_demux(self.h, p(ts) if ts_bytes else None, int(ts_bytes), int(packet_bytes), int(pid),
+                                     p(out), int(out_cap), p(pes), int(pes_cap), p(summary))
+
+    def ts_demux(self, ts, pid, packet_bytes=188, ts_bytes=None):
+        """Convenience: the elementary stream of `pid` in the transport stream `ts` (device uint8 tensor).  Plans first,
+        allocates the exact outputs, runs.  Returns (out device tensor, pes ndarray[TS_PES], summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        nbytes = int(ts.numel()) if ts_bytes is None else int(ts_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.ts_demux_async(ts, nbytes, packet_bytes, pid, None, None, summary), "hbs_ts_demux")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_ts_demux: error %d (packet %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        need, n_pes = int(s["stream_bytes"]), int(s["nal_count"])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        pes = t.empty(max(n_pes, 1) * TS_PES.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.ts_demux_async(ts, nbytes, packet_bytes, pid, out, pes, summary, out_cap=need, pes_cap=n_pes), "hbs_ts_demux")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_ts_demux: error %d" % int(s["error"]))
+        return out[:need], pes[: n_pes * TS_PES.itemsize].cpu().numpy().view(TS_PES).copy(), s
 
     # ---- access units -----------------------------------------------------------------
 

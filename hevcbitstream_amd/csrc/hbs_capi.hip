@@ -20,6 +20,7 @@
 #include "hbs_filter.h"
 #include "hbs_lenpref.h"
 #include "hbs_au.h"
+#include "hbs_ts.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -33,8 +34,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kFws    hbs_filter_annexb's scratch
  * kAws    hbs_access_units' scratch.  hbs_au_keep uses its first 16 bytes (where hbs_access_units keeps its digest): the calls
  *         of a context are ordered by its one stream, so neither sees the other's data
- * kLws    the scratch of hbs_annexb_to_lenpref and hbs_lenpref_to_annexb */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kBufs };
+ * kLws    the scratch of hbs_annexb_to_lenpref and hbs_lenpref_to_annexb
+ * kTws    hbs_ts_demux's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -671,6 +673,29 @@ int hbs_lenpref_to_annexb(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, in
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_lenpref_to_annexb(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_lenpref_to_annexb");
+}
+
+int hbs_ts_demux(hbs_ctx* c, const uint8_t* d_ts, uint64_t ts_bytes, int packet_bytes, int pid,
+                 uint8_t* d_out, uint64_t out_cap, hbs_ts_pes* d_pes, uint64_t pes_cap, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_ts_pes) == 32 && sizeof(hbs_ts_packet) == 48, "hbs_ts_pes / hbs_ts_packet layout");
+    if (!c || !d_summary || !hbs::ts_packet_bytes_ok(packet_bytes) || pid < 0 || pid > 8191) return HBS_E_ARG;
+    if (ts_bytes % (uint64_t)packet_bytes || ts_bytes / (uint64_t)packet_bytes > 0xFFFFFFFFull || (ts_bytes && !d_ts)) return HBS_E_ARG;
+    if (misaligned(d_ts, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_pes, 7)) {
+        snprintf(c->err, sizeof(c->err), "transport stream/output/summary pointers must be 16-byte aligned, the PES table 8-byte aligned");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::TsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ts = d_ts; a.n = ts_bytes; a.packets = ts_bytes / (uint64_t)packet_bytes;
+    a.B = (uint32_t)packet_bytes; a.lead = hbs::ts_lead(packet_bytes); a.pid = pid;
+    a.out = d_out; a.out_cap = out_cap; a.pes = d_pes; a.pes_cap = pes_cap; a.summary = d_summary;
+    const int rc = carve(c, c->buf[kTws], "hipMalloc(transport stream scratch)", [&](hbs::Carver& w) { hbs::lay_ts(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_ts_demux(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_ts_demux");
 }
 
 uint64_t hbs_au_sps_poc_offset(void) { return offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4); }

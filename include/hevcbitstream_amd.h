@@ -394,6 +394,104 @@ int hbs_lenpref_to_annexb(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, 
                           uint64_t* d_sample_off_out /* optional, n_samples + 1 */, hbs_summary* d_summary);
 
 /*
+ * ---- MPEG transport stream (ISO/IEC 13818-1) -> Annex-B elementary stream, PES times ----------------------------------
+ * hbs_ts_demux takes the packets of one PID out of a transport stream in device memory and writes their elementary-stream
+ * bytes back to back: the Annex-B stream hbs_index_extract / hbs_index_parse_compact take.  With it comes a table of the
+ * PES packets begun, each with its PTS / DTS and the output offset of its first byte; a muxer that puts one access unit
+ * into one PES packet makes that offset hbs_access_unit.unit_begin, which is how a time finds its sample.
+ *
+ * THE PACKET RULE.  B = packet_bytes is 188, 192 (M2TS: a 4-byte time prefix in front) or 204 (16 Reed-Solomon bytes
+ * behind); anything else is HBS_E_ARG at once.  Packet p is d_ts[p B, (p + 1) B); its 188 transport bytes b[] begin at
+ * h = 4 when B == 192, else at h = 0; the other bytes of the packet are ignored.  In this order:
+ *   sync fault    b[0] != 0x47: a FAULT, whatever the PID.
+ *   fields        tei = b[1] >> 7, pusi = (b[1] >> 6) & 1, pid = (b[1] & 0x1F) << 8 | b[2], tsc = b[3] >> 6,
+ *                 afc = (b[3] >> 4) & 3, cc = b[3] & 15.
+ *   other PID     pid != the wanted one: the packet plays no further part (HBS_TS_OTHER).
+ *   skipped       tei set or tsc != 0: HBS_TS_SKIPPED -- counted, not copied, nothing else of it is looked at.
+ *   adaptation    off = 4.  With afc & 2: afl = b[4]; afl > 183 is a FAULT; off = 5 + afl; with afl >= 1,
+ *                 discontinuity_indicator = b[5] >> 7 and random_access_indicator = (b[5] >> 6) & 1 (else both 0).
+ *   payload       (afc & 1) == 0 or off == 188: HBS_TS_NO_PAYLOAD -- neither copied nor counted as skipped, pusi ignored.
+ *                 Else the payload is b[off, 188), len = 188 - off.
+ *   PES start     with pusi the payload begins a PES packet q[] = b[off ...]: len >= 9, q[0..2] == 00 00 01,
+ *                 (q[6] & 0xC0) == 0x80, f = q[7] >> 6 is not 1, H = 9 + q[8] <= len, q[8] >= 5 when f == 2 and >= 10 when
+ *                 f == 3 must all hold, else FAULT.  HBS_TS_PES_START; its ES bytes are q[H, len) (there may be none).
+ *                 Without pusi the ES bytes are the whole payload (HBS_TS_PAYLOAD).
+ *   times         PTS from q[9..13] (f >= 2), DTS from q[14..18] (f == 3), each as
+ *                 ((x0 >> 1) & 7) << 30 | x1 << 22 | (x2 >> 1) << 15 | x3 << 7 | x4 >> 1.  Marker bits are not checked,
+ *                 PES_packet_length is not used.
+ * STATED LIMIT: a PES header that does not end inside the packet it begins in is a fault (H > len); it is not followed
+ * into the next packet.
+ *
+ * THE CALL.  ts_bytes must be a multiple of packet_bytes and hold at most 2^32 - 1 packets, pid is 0..8191; anything else
+ * is refused with HBS_E_ARG at once, before anything is written.  ts_bytes == 0 is valid.
+ * Let C be the packets of the PID with HBS_TS_PAYLOAD or HBS_TS_PES_START that lie at or behind the first HBS_TS_PES_START
+ * packet of the PID, in order.  Every packet of the PID in front of that first PES start (all of them when there is none)
+ * counts as skipped, whatever its class.  The output is the ES bytes of C, back to back.  d_pes (optional) receives one
+ * record per PES start in C, in order.  d_out == NULL: plan only -- the summary alone is written, no capacity is looked at.
+ *   d_summary   nal_count = PES packets begun; nal_found = packets of the PID, whatever their class; stream_bytes = output
+ *               bytes; rbsp_bytes = 0; stop_reason = 0;
+ *               reserved[1] = continuity breaks: members of C (but the first) whose cc is not (cc of the member in front
+ *               + 1) & 15 and whose discontinuity_indicator is 0.  A duplicate packet (same cc twice, which the standard
+ *               allows a muxer to send) therefore counts as a break AND is copied like any other member: duplicates are
+ *               not dropped;
+ *               reserved[2] = skipped packets (HBS_TS_SKIPPED at or behind the first PES start, and all in front of it).
+ *               error = HBS_E_ARG on any fault: reserved[0] = 1 + the lowest faulty packet number, the counts mean
+ *               nothing.  Else error = HBS_E_CAPACITY when out_cap is below the output or, with d_pes, pes_cap is below
+ *               the PES count; the counts are right.  On either error nothing is written to d_out or d_pes.
+ * Nothing outside [d_out, d_out + output bytes) and d_pes[0, PES count) is stored; no load touches a 16-byte granule that
+ * holds no byte of d_ts[0, ts_bytes); no host synchronisation.  Alignment: d_ts, d_out, d_summary 16 bytes; d_pes 8 bytes.
+ * Not done: PES headers continued in a following packet, dropping duplicates, resynchronising after
+ * sync loss, PSI on the device, several PIDs in one call, PCR.
+ */
+#define HBS_TS_FAULT      (-1)
+#define HBS_TS_OTHER        0
+#define HBS_TS_SKIPPED      1
+#define HBS_TS_NO_PAYLOAD   2
+#define HBS_TS_PAYLOAD      3
+#define HBS_TS_PES_START    4
+#define HBS_TS_PTS            1u   /* flags of hbs_ts_pes / hbs_ts_packet: a PTS is present  */
+#define HBS_TS_DTS            2u   /* a DTS is present                                        */
+#define HBS_TS_RANDOM_ACCESS  4u   /* random_access_indicator of the packet                   */
+#define HBS_TS_DISCONTINUITY  8u   /* discontinuity_indicator of the packet                   */
+#define HBS_TS_DATA_ALIGNED  16u   /* data_alignment_indicator of the PES header (q[6] & 4)   */
+
+typedef struct hbs_ts_pes {   /* 32 bytes */
+    uint64_t out_off;  /* output offset of the first ES byte of this PES packet */
+    uint64_t pts;      /* 33 bits; ~0 when absent */
+    uint64_t dts;      /* the DTS; = pts when only a PTS is present; ~0 when neither */
+    uint32_t packet;   /* number of the transport packet it begins in */
+    uint32_t flags;    /* HBS_TS_PTS | HBS_TS_DTS | HBS_TS_RANDOM_ACCESS | HBS_TS_DISCONTINUITY | HBS_TS_DATA_ALIGNED */
+} hbs_ts_pes;
+
+int hbs_ts_demux(hbs_ctx* ctx, const uint8_t* d_ts, uint64_t ts_bytes, int packet_bytes, int pid,
+                 uint8_t* d_out, uint64_t out_cap, hbs_ts_pes* d_pes, uint64_t pes_cap, hbs_summary* d_summary);
+
+/*
+ * Host side, plain C, no GPU involved.
+ * hbs_ts_packet_host: the packet rule above for ONE packet of packet_bytes bytes in host memory -- the very function the
+ * kernels run (csrc/hbs_ts.h).  off / es_off count from transport byte 0 (add 4 for the position inside a 192-byte
+ * packet).  A fault leaves everything but cls and pid at 0 (pts, dts: ~0).  Returns 0, or HBS_E_ARG (null pointer,
+ * packet_bytes, pid).
+ * hbs_ts_find_pid_host: the PID of the first elementary stream of `stream_type` (0x24: HEVC) in the first program of a
+ * transport stream's head: the first PAT section (PID 0, payload_unit_start, behind its pointer_field, table_id 0), its first
+ * entry with program_number != 0 (whose PID carries the PMT; *program_out = that number, when not NULL), the first
+ * section with table_id 2 on that PID.  -1 when it is not found or a section does not lie inside one packet.  CRCs are not
+ * checked; every length read from the buffer is bounded against the packet before it is used; bytes behind the last whole
+ * packet are not read.
+ */
+typedef struct hbs_ts_packet {   /* 48 bytes */
+    int32_t  cls;             /* HBS_TS_*                                                         */
+    uint32_t pid;
+    uint32_t off, len;        /* the payload b[off, off + len)                                     */
+    uint32_t es_off, es_len;  /* its ES bytes b[es_off, es_off + es_len)                           */
+    uint32_t cc;              /* continuity_counter                                                */
+    uint32_t flags;           /* as hbs_ts_pes.flags                                               */
+    uint64_t pts, dts;        /* as hbs_ts_pes                                                     */
+} hbs_ts_packet;
+int hbs_ts_packet_host(const uint8_t* packet, int packet_bytes, int pid, hbs_ts_packet* out);
+int hbs_ts_find_pid_host(const uint8_t* bytes, uint64_t n, int packet_bytes, int stream_type, int* program_out);
+
+/*
  * K4: header parse, one NAL per lane (64 per wavefront), over the RBSP arena and index that
  * hbs_index_extract produced.  For NAL k it does what read_hevc_nal_unit()
  * does after nal_to_rbsp (hevc_stream.c:175-239): NAL header, then by type the
