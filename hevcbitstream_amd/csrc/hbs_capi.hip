@@ -589,25 +589,16 @@ int hbs_filter_annexb(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes
     const uint64_t reach = d_out ? (out_cap < stream_bytes ? out_cap : stream_bytes) : 0;    /* the output is at most this long */
     hbs::FilterArgs a;
     memset(&a, 0, sizeof(a));
-    a.stream = d_stream; a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals;
+    a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals;
     if (rule) { a.rule = *rule; a.use_rule = 1; }
     a.keep = d_keep;
-    a.out = d_out; a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
-    a.tiles = (reach + hbs::kFilterTileBytes - 1) / hbs::kFilterTileBytes;
+    a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
+    a.t.src = d_stream; a.t.out = d_out; a.t.tiles = hbs::piece_tiles(reach);
     const int rc = carve(c, c->buf[kFws], "hipMalloc(filter scratch)", [&](hbs::Carver& w) { hbs::lay_filter(w, a); });
     if (rc < 0) return rc;
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_filter_annexb(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_filter_annexb");
-}
-
-namespace {
-/* the output tiles a grid covers for an output of at most `reach` bytes (what a grid can hold is far beyond device memory) */
-uint64_t lenpref_tiles(uint64_t reach)
-{
-    const uint64_t t = reach / hbs::kLenprefTileBytes + (reach % hbs::kLenprefTileBytes ? 1 : 0);
-    return t < 0x7FFFFFFFull ? t : 0x7FFFFFFFull;
-}
 }
 
 int hbs_annexb_to_lenpref(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
@@ -630,7 +621,7 @@ int hbs_annexb_to_lenpref(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_b
     a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
     a.t.src = d_stream; a.t.out = d_out; a.t.prefix = (uint32_t)length_size; a.t.prefix_is_length = 1;
     const uint64_t most = stream_bytes + n_nals * (uint64_t)length_size;                    /* the output is at most this long */
-    a.t.tiles = d_out ? lenpref_tiles(out_cap < most ? out_cap : most) : 0;
+    a.t.tiles = d_out ? hbs::piece_tiles(out_cap < most ? out_cap : most) : 0;
     const int rc = carve(c, c->buf[kLws], "hipMalloc(lenpref scratch)", [&](hbs::Carver& w) { hbs::lay_a2l(w, a); });
     if (rc < 0) return rc;
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
@@ -667,7 +658,7 @@ int hbs_lenpref_to_annexb(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, in
     a.nal_cap = nal_cap; a.piece_cap = d_out ? (nal_cap < fit ? nal_cap : fit) : 0; a.out_cap = out_cap;
     a.sample_off_out = reinterpret_cast<unsigned long long*>(d_sample_off_out); a.summary = d_summary;
     a.t.src = d_in; a.t.out = d_out; a.t.prefix = (uint32_t)startcode_bytes; a.t.prefix_is_length = 0;
-    a.t.tiles = d_out ? lenpref_tiles(out_cap) : 0;              /* (samples may overlap: the input's size bounds nothing; out_cap is bounded above) */
+    a.t.tiles = d_out ? hbs::piece_tiles(out_cap) : 0;              /* (samples may overlap: the input's size bounds nothing; out_cap is bounded above) */
     const int rc = carve(c, c->buf[kLws], "hipMalloc(lenpref scratch)", [&](hbs::Carver& w) { hbs::lay_l2a(w, a); });
     if (rc < 0) return rc;
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */

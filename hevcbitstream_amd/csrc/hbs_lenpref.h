@@ -3,28 +3,13 @@
 #define HBS_LENPREF_H
 
 #include <hip/hip_runtime_api.h>
-#include "hbs_common.h"
+#include "hbs_pieces.h"
 
 namespace hbs {
 
 constexpr int kLenprefNalsPerBlock = 2048;           /* forward plan: 256 lanes x 8 consecutive NALs        */
 constexpr int kLenprefSamplesPerBlock = 256;         /* reverse plan: one lane per sample                   */
-constexpr uint64_t kLenprefTileBytes = 64 * 1024;    /* copy: output bytes of one workgroup                 */
 constexpr uint64_t kLenprefOutCapMax = 1ull << 46;   /* reverse: out_cap sizes scratch and grid (2^30 tiles, < 2^45 pieces: no size wraps) */
-
-/* What the copy kernel works on.  Piece j is the output bytes [piece_out[j], piece_out[j + 1]): `prefix` literal bytes, then
- * source bytes; output byte o of its payload is src[o + piece_delta[j]]. */
-struct PieceTable {
-    const uint8_t* src;
-    uint8_t* out;                   /* NULL: plan only                                                              */
-    uint32_t prefix;                /* bytes of the literal in front of each payload: length_size / startcode_bytes */
-    int prefix_is_length;           /* 1: the payload's length, big-endian; 0: 00 .. 00 01                          */
-    unsigned long long* ctl;        /* 8: error, output bytes, pieces                                               */
-    unsigned long long* piece_out;  /* pieces + 1: output offset of piece j (then the total)                        */
-    unsigned long long* piece_delta;/* pieces: source offset minus output offset of its payload                     */
-    unsigned long long* tile_first; /* tiles + 1: the piece the output tile's first byte lies in                    */
-    uint64_t tiles;                 /* output tiles the grid covers                                                 */
-};
 
 struct A2lArgs {
     uint64_t n;                                       /* stream bytes                                          */
@@ -53,14 +38,6 @@ struct L2aArgs {
     unsigned long long* samp;       /* 2 per sample: its output bytes, its records                                          */
     hipEvent_t ev_begin, ev_end;
 };
-
-inline void lay_pieces(Carver& w, PieceTable& t, uint64_t piece_cap)
-{
-    t.ctl = w.take<unsigned long long>(64);
-    t.piece_out = w.take<unsigned long long>((piece_cap + 1) * 8);
-    t.piece_delta = w.take<unsigned long long>(piece_cap * 8);
-    t.tile_first = w.take<unsigned long long>((t.tiles + 1) * 8);
-}
 
 /* the scratch the calls need, sized by n_nals / n_samples and nal_cap, and by t.tiles */
 inline void lay_a2l(Carver& w, A2lArgs& a)

@@ -1,0 +1,207 @@
+/*
+ * hbs_pieces.hip -- copy_pieces: the copy over a table of "pieces" (hbs_pieces.h) -- a short literal prefix, possibly of no
+ * bytes, followed by a run of source bytes at its own byte misalignment.  One copy for hbs_filter_annexb (hbs_filter.hip: a
+ * kept unit is a piece without a prefix), hbs_annexb_to_lenpref and hbs_lenpref_to_annexb (hbs_lenpref.hip); their plans
+ * fill the table.  Two launches, neither of which waits for another workgroup:
+ *
+ *   k_piece_tiles    one lane per 64 KiB output tile: binary search of the piece its first byte lies in
+ *   k_piece_copy     one workgroup per output tile: each lane takes 16-byte output chunks 4 KiB apart and finds the piece of
+ *                    each (the tile's pieces are staged in LDS; more than 2 048 are read from memory).  A chunk inside one
+ *                    payload is loaded as aligned 16-byte non-temporal loads, realigned with alignbyte and stored as one
+ *                    aligned 16-byte non-temporal store; a chunk that holds a prefix byte or spans pieces, and the output's
+ *                    last chunk, is assembled byte by byte and stored byte-exact.  A payload of any size spreads over the
+ *                    tiles it covers.  <kPrefix>: false for a table without prefixes, where all that is about them folds away.
+ *
+ * Traffic: the payloads read once and written once, 16 B a piece and 8 B a tile of scratch read.
+ */
+#include <hip/hip_runtime.h>
+#include "hbs_pieces.h"
+#include "hbs_wave.h"
+
+namespace hbs {
+namespace {
+
+constexpr int kCT = 256;                                              /* lanes of the copy workgroup             */
+constexpr uint32_t kTile = (uint32_t)kPieceTileBytes;
+constexpr int kChunks = (int)(kPieceTileBytes / 16 / kCT);            /* 16-byte output chunks a copy lane takes */
+constexpr int kBatch = 4;                                             /* ... loads of that many issued together  */
+constexpr uint32_t kLdsPieces = 2048;                                 /* pieces a tile stages in LDS; more: read from memory */
+constexpr int32_t kFar = -8;                                          /* a piece that begins this far in front of the tile or
+                                                                         further: its prefix (<= 4 bytes) is not in the tile */
+
+__global__ __launch_bounds__(256) void k_piece_tiles(PieceTable a)
+{
+    if (a.ctl[0] != 0) return;
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t total = a.ctl[1], pieces = a.ctl[2];
+    const uint64_t used = (total + kTile - 1) / kTile;
+    if (t > used || pieces == 0) return;
+    if (t == used) { a.tile_first[t] = pieces - 1; return; }
+    const uint64_t o = t * kTile;
+    uint64_t lo = 0, hi = pieces - 1;                /* the last piece that begins at or before o */
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (a.piece_out[mid] <= o) lo = mid; else hi = mid - 1;
+    }
+    a.tile_first[t] = lo;
+}
+
+/* bytes [sh, sh + 16) of the 32 bytes a:b */
+__device__ __forceinline__ u32x4 realign(u32x4 a, u32x4 b, uint32_t sh)
+{
+    const uint32_t q = sh >> 2, r = sh & 3u;
+    uint32_t x0, x1, x2, x3, x4;
+    if (q == 0)      { x0 = a.x; x1 = a.y; x2 = a.z; x3 = a.w; x4 = b.x; }
+    else if (q == 1) { x0 = a.y; x1 = a.z; x2 = a.w; x3 = b.x; x4 = b.y; }
+    else if (q == 2) { x0 = a.z; x1 = a.w; x2 = b.x; x3 = b.y; x4 = b.z; }
+    else             { x0 = a.w; x1 = b.x; x2 = b.y; x3 = b.z; x4 = b.w; }
+    u32x4 v;
+    v.x = alignbyte(x1, x0, r); v.y = alignbyte(x2, x1, r); v.z = alignbyte(x3, x2, r); v.w = alignbyte(x4, x3, r);
+    return v;
+}
+
+__device__ __forceinline__ u32x4 zero4() { u32x4 z; z.x = z.y = z.z = z.w = 0; return z; }
+
+/* the tile's pieces [j0, j0 + cnt): rel(i) = where piece j0 + i begins, relative to the tile, clamped to [kFar, kTile] (without
+ * prefixes to [0, kTile]: where a piece begins in front of the tile says nothing then) */
+template <bool kPrefix>
+struct TilePieces {
+    const int32_t* s_bound; const unsigned long long* s_delta;     /* staged: LDS */
+    const unsigned long long* piece_out; const unsigned long long* piece_delta;
+    uint64_t j0, t0;
+    bool lds;
+    __device__ __forceinline__ int32_t rel(uint32_t i) const
+    {
+        if (lds) return s_bound[i];
+        const uint64_t b = piece_out[j0 + i];
+        if (b >= t0) return b - t0 >= kTile ? (int32_t)kTile : (int32_t)(b - t0);
+        if (!kPrefix) return 0;
+        return t0 - b >= (uint64_t)(-kFar) ? kFar : -(int32_t)(t0 - b);
+    }
+    __device__ __forceinline__ uint64_t delta(uint32_t i) const { return lds ? s_delta[i] : piece_delta[j0 + i]; }
+    /* the last piece i in [lo, hi] with rel(i) <= r (rel(lo) <= r holds) */
+    __device__ __forceinline__ uint32_t find(uint32_t lo, uint32_t hi, uint32_t r) const
+    {
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (rel(mid) <= (int32_t)r) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    }
+};
+
+/* an output chunk [r, r + len) of the tile that holds prefix bytes or spans pieces (or ends the output): assembled byte by
+ * byte, each payload byte loaded from the piece it belongs to, each prefix byte computed */
+template <bool kPrefix>
+__device__ __forceinline__ void copy_chunk_bytes(const PieceTable& a, const TilePieces<kPrefix>& tp, uint32_t ip, uint32_t r, uint32_t len)
+{
+    uint64_t clo = 0, chi = 0;
+    int32_t b0 = tp.rel(ip), b1 = tp.rel(ip + 1);
+    uint64_t delta = tp.delta(ip);
+    uint64_t plen = 0;
+    bool have_len = false;
+    const int32_t P = kPrefix ? (int32_t)a.prefix : 0;
+#pragma unroll 1
+    for (uint32_t q = 0; q < len; ++q) {
+        const int32_t ro = (int32_t)(r + q);
+        if (ro >= b1) { ip += 1; b0 = b1; b1 = tp.rel(ip + 1); delta = tp.delta(ip); have_len = false; }
+        const int32_t pos = ro - b0;           /* (a piece clamped to kFar: pos >= 8, payload) */
+        uint64_t v;
+        if (!kPrefix || pos >= P) {
+            v = a.src[delta + tp.t0 + (uint32_t)ro];
+        } else if (a.prefix_is_length) {
+            if (!have_len) { plen = a.piece_out[tp.j0 + ip + 1] - a.piece_out[tp.j0 + ip] - (uint64_t)P; have_len = true; }
+            v = (plen >> (8 * (P - 1 - pos))) & 0xFFu;
+        } else {
+            v = pos == P - 1 ? 1u : 0u;
+        }
+        if (q < 8) clo |= v << (8 * q); else chi |= v << (8 * (q - 8));
+    }
+    uint8_t* dst = a.out + tp.t0 + r;
+    if (len == 16) {
+        u32x4 c;
+        c.x = (uint32_t)clo; c.y = (uint32_t)(clo >> 32); c.z = (uint32_t)chi; c.w = (uint32_t)(chi >> 32);
+        arena_store16(dst, c);
+    } else {
+        store_pieces(dst, clo, chi, len);
+    }
+}
+
+template <bool kPrefix>
+__global__ __launch_bounds__(kCT) void k_piece_copy(PieceTable a)
+{
+    __shared__ int32_t s_bound[kLdsPieces + 1];
+    __shared__ unsigned long long s_delta[kLdsPieces];
+    if (a.ctl[0] != 0) return;
+    const uint64_t total = a.ctl[1];
+    const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
+    if (t0 >= total) return;
+    const uint32_t tlen = total - t0 < kTile ? (uint32_t)(total - t0) : kTile;
+    const uint64_t j0 = a.tile_first[blockIdx.x], j1 = a.tile_first[blockIdx.x + 1];
+    const uint32_t cnt = (uint32_t)(j1 - j0 + 1);     /* pieces [j0, j1]; piece_out[j1 + 1] exists (the total at the end) */
+    TilePieces<kPrefix> tp;
+    tp.s_bound = s_bound; tp.s_delta = s_delta; tp.piece_out = a.piece_out; tp.piece_delta = a.piece_delta;
+    tp.j0 = j0; tp.t0 = t0; tp.lds = false;
+    if (cnt <= kLdsPieces) {
+        for (uint32_t i = threadIdx.x; i <= cnt; i += kCT) {
+            s_bound[i] = tp.rel(i);
+            if (i < cnt) s_delta[i] = a.piece_delta[j0 + i];
+        }
+        __syncthreads();
+        tp.lds = true;
+    }
+    const int32_t P = kPrefix ? (int32_t)a.prefix : 0;
+    uint32_t lo = 0;
+    uint32_t slow = 0;                        /* chunks done byte by byte, behind the batches: bit b + u */
+    uint32_t slow_ip[kChunks];
+#pragma unroll 1
+    for (int b = 0; b < kChunks; b += kBatch) {
+        u32x4 va[kBatch], vb[kBatch];
+        uint32_t sh[kBatch], ip[kBatch];
+        bool simple[kBatch];
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) {
+            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kCT * (uint32_t)(b + u));
+            simple[u] = false; sh[u] = 0; ip[u] = lo;
+            va[u] = zero4(); vb[u] = zero4();
+            if (r < tlen) {
+                lo = tp.find(lo, cnt - 1, r);
+                ip[u] = lo;
+                if (tlen - r >= 16 && tp.rel(lo + 1) - (int32_t)r >= 16 && (!kPrefix || (int32_t)r - tp.rel(lo) >= P)) {
+                    const uint64_t s = tp.delta(lo) + t0 + r;
+                    const uint64_t g = s & ~15ull;
+                    sh[u] = (uint32_t)(s & 15u);
+                    simple[u] = true;
+                    va[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g));
+                    if (sh[u]) vb[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g + 16));
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) {
+            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kCT * (uint32_t)(b + u));
+            if (simple[u]) arena_store16(a.out + t0 + r, realign(va[u], vb[u], sh[u]));
+            else if (r < tlen) { slow |= 1u << (b + u); slow_ip[b + u] = ip[u]; }
+        }
+    }
+#pragma unroll 1
+    while (slow) {
+        const int i = (int)__builtin_ctz(slow);
+        slow &= slow - 1;
+        const uint32_t r = 16u * (threadIdx.x + (uint32_t)kCT * (uint32_t)i);
+        copy_chunk_bytes(a, tp, slow_ip[i], r, tlen - r < 16 ? tlen - r : 16u);
+    }
+}
+
+} // namespace
+
+hipError_t copy_pieces(const PieceTable& t, hipStream_t st)
+{
+    if (!t.tiles) return hipSuccess;
+    hipLaunchKernelGGL(k_piece_tiles, dim3((unsigned)((t.tiles + 1 + 255) / 256)), dim3(256), 0, st, t);
+    if (t.prefix) hipLaunchKernelGGL(k_piece_copy<true>, dim3((unsigned)t.tiles), dim3(kCT), 0, st, t);
+    else hipLaunchKernelGGL(k_piece_copy<false>, dim3((unsigned)t.tiles), dim3(kCT), 0, st, t);
+    return hipSuccess;
+}
+
+} // namespace hbs

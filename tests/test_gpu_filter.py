@@ -1,6 +1,7 @@
 """hbs_filter_annexb on the device against the numpy reference (tests/_filter_ref.py): output bytes, output index and every
 summary field, on random streams, rules and keep masks; re-scan of the output; a 4K30 stream with temporal sub-layers; exact
-capacity with canaries; errors; dense tiny NALs; a stream above 4 GiB; two contexts at the same time."""
+capacity with canaries; errors; dense tiny NALs; tiles whose table does not fit LDS; a stream above 4 GiB; two contexts at the
+same time."""
 import numpy as np
 import pytest
 
@@ -9,6 +10,8 @@ from tests import _filter_ref as F
 pytestmark = pytest.mark.gpu
 CAN = 0xC3
 PAD = 4096
+TILE = 65536            # output bytes of one copy workgroup
+LDS_UNITS = 2048        # units of a tile the copy stages in LDS; more are read from memory
 
 
 @pytest.fixture(scope="module")
@@ -205,6 +208,36 @@ def test_dense_tiny_nals_every_other(ctx, orc):
     check(ctx, s, idx, keep)
     check(ctx, s, idx, ~keep)
     check(ctx, s, idx, rng.random(len(idx)) < 0.1)
+
+
+def units_per_tile(io):
+    """(non-empty units that overlap each 64 KiB tile of the output, non-empty units) from an output index"""
+    en = io["end"].astype(np.int64)
+    u = np.concatenate([[0], en[:-1]])
+    en, u = en[en > u], u[en > u]
+    tiles = -(-int(en[-1]) // TILE)
+    return [int(((u < (t + 1) * TILE) & (en > t * TILE)).sum()) for t in range(tiles)], len(en)
+
+
+def test_table_that_does_not_fit_lds(ctx):
+    """Payloads of 0-3 bytes behind 3- and 4-byte start codes: ~4.8 bytes a unit, ~13 600 units in a full output tile, so the
+    copy reads the tile's table from memory.  The index is the constructed one (the oracle's walk stops at the first empty
+    NAL; with payloads of 1-3 bytes it gives this index).  700 KB, not 300: a tenth of the NALs is then one full tile and a
+    last tile of ~3.5 KB, ~700 units, that is staged in LDS -- at this density a tenth of 300 KB is one tile of ~6 000 units."""
+    from tests.test_gpu_lenpref import made_stream
+    rng = np.random.default_rng(41)
+    n = 146000
+    s, idx = made_stream(rng, rng.integers(0, 4, size=n))
+    assert F.consistent(idx, len(s)) and len(s) > 700000
+    for keep, dense in ((np.ones(n, bool), True), (np.arange(n) % 2 == 0, True), (rng.random(n) < 0.1, False)):
+        want_out, want_io, _ = F.filter_ref(s, idx, keep)
+        per_tile, units = units_per_tile(want_io)
+        if dense:
+            assert units > LDS_UNITS * (len(want_out) / TILE) and min(per_tile[:-1]) > LDS_UNITS
+            check(ctx, s, idx, keep, rule=ctx.nal_filter(), use_rule=bool(keep.all()))
+        else:
+            assert min(per_tile) < LDS_UNITS < max(per_tile)
+            check(ctx, s, idx, keep)
 
 
 def test_stream_above_4gib(ctx):
