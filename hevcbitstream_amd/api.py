@@ -36,6 +36,11 @@ TS_FAULT, TS_OTHER, TS_SKIPPED, TS_NO_PAYLOAD, TS_PAYLOAD, TS_PES_START = -1, 0,
 TS_F_PTS, TS_F_DTS, TS_F_RANDOM_ACCESS, TS_F_DISCONTINUITY, TS_F_DATA_ALIGNED = 1, 2, 4, 8, 16
 TS_NO_TIME = (1 << 64) - 1
 STREAM_TYPE_HEVC = 0x24
+# layout of hbs_ts_mux_params and the flags of hbs_ts_mux
+TS_MUX_PARAMS = np.dtype([("packet_bytes", "<i4"), ("pid", "<i4"), ("pmt_pid", "<i4"), ("program_number", "<i4"),
+                          ("transport_stream_id", "<i4"), ("flags", "<u4"), ("cc_es", "<u4"), ("cc_pat", "<u4"), ("cc_pmt", "<u4"),
+                          ("reserved", "<u4"), ("pcr_lead", "<u8")])
+TSMUX_PCR, TSMUX_PSI_AT_IRAP, TSMUX_NO_PSI = 1, 2, 4
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -64,7 +69,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
            "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset",
            "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb",
-           "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host"]
+           "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
+           "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -201,6 +207,11 @@ def load_library():
                                  C.c_void_p]
     lib.hbs_ts_packet_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.hbs_ts_find_pid_host.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    lib.hbs_ts_mux.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.hbs_ts_mux_psi_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hbs_ts_mux_au_packets_host.argtypes = [C.c_uint64, C.c_int, C.c_int]
+    lib.hbs_ts_mux_au_packets_host.restype = C.c_uint64
     _lib = lib
     return lib
 
@@ -225,6 +236,31 @@ def ts_find_pid(head, packet_bytes=188, stream_type=STREAM_TYPE_HEVC):
     prog = C.c_int(0)
     pid = load_library().hbs_ts_find_pid_host(a.ctypes.data if len(a) else None, len(a), int(packet_bytes), int(stream_type), C.byref(prog))
     return None if pid < 0 else (pid, prog.value)
+
+
+def ts_mux_params(pid=0x100, pmt_pid=0x1000, packet_bytes=188, program_number=1, transport_stream_id=1, flags=0,
+                  cc_es=0, cc_pat=0, cc_pmt=0, pcr_lead=0, reserved=0):
+    """an hbs_ts_mux_params record (ndarray[TS_MUX_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=TS_MUX_PARAMS)
+    p[0] = (packet_bytes, pid, pmt_pid, program_number, transport_stream_id, flags, cc_es, cc_pat, cc_pmt, reserved, pcr_lead)
+    return p
+
+
+def ts_mux_psi(params=None, **kw):
+    """hbs_ts_mux_psi_host: the PAT and the PMT packet (188 bytes each) hbs_ts_mux places in front of AU 0, for an
+    ndarray[TS_MUX_PARAMS] of one or the keywords of ts_mux_params.  No GPU involved."""
+    p = np.ascontiguousarray(params, dtype=TS_MUX_PARAMS) if params is not None else ts_mux_params(**kw)
+    pat, pmt = np.zeros(188, dtype=np.uint8), np.zeros(188, dtype=np.uint8)
+    rc = load_library().hbs_ts_mux_psi_host(p.ctypes.data, pat.ctypes.data, pmt.ctypes.data)
+    if rc != 0:
+        raise HbsError("hbs_ts_mux_psi_host failed: %d" % rc)
+    return pat.tobytes(), pmt.tobytes()
+
+
+def ts_mux_au_packets(es_bytes, time_fields=0, pcr=False):
+    """hbs_ts_mux_au_packets_host: the transport packets of an access unit of es_bytes bytes; time_fields 0: no time, 1: a PTS,
+    2: a PTS and a DTS that differs.  No GPU involved."""
+    return int(load_library().hbs_ts_mux_au_packets_host(int(es_bytes), int(time_fields), 1 if pcr else 0))
 
 
 class Context:
@@ -844,6 +880,51 @@ class Context:
         if int(s["error"]) != 0:
             raise HbsError("hbs_ts_demux: error %d" % int(s["error"]))
         return out[:need], pes[: n_pes * TS_PES.itemsize].cpu().numpy().view(TS_PES).copy(), s
+
+    def ts_mux_async(self, stream, stream_bytes, au, n_aus, pts, dts, params, out, au_packet, summary, out_cap=None):
+        """Enqueue hbs_ts_mux on the current torch stream.  stream / au / pts / dts / out / au_packet / summary are device
+        tensors (pts, dts, au_packet may be None; out None: plan only); params is an ndarray[TS_MUX_PARAMS] of one in host
+        memory.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=TS_MUX_PARAMS)
+        return self.lib.hbs_ts_mux(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(au) if n_aus else None, int(n_aus),
+                                   p(pts), p(dts), params.ctypes.data_as(C.c_void_p) if params is not None else None,
+                                   p(out), int(out_cap), p(au_packet), p(summary))
+
+    def ts_mux(self, stream, au, pts=None, dts=None, stream_bytes=None, **params):
+        """Convenience: the access units `au` (ndarray[ACCESS_UNIT] or a device uint8 tensor of the records) of `stream` (device
+        uint8 tensor) as transport packets.  pts / dts: None or one uint64 per AU (TS_NO_TIME: absent), host arrays or device
+        tensors; params: the keywords of ts_mux_params.  Plans first, allocates the exact output, runs.  Returns (out device
+        tensor, au_packet ndarray[uint32] of n_aus + 1, summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x, dtype):
+            if isinstance(x, np.ndarray):
+                b = np.ascontiguousarray(x, dtype=dtype).view(np.uint8).reshape(-1)
+                return t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
+            return x
+        n = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
+        au, pts, dts = dv(au, ACCESS_UNIT), dv(pts, np.uint64), dv(dts, np.uint64)
+        prm = ts_mux_params(**params)
+        nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.ts_mux_async(stream, nbytes, au, n, pts, dts, prm, None, None, summary), "hbs_ts_mux")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_ts_mux: error %d (access unit %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        need = int(s["stream_bytes"])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        au_packet = t.empty(n + 1, dtype=t.int32, device=dev)
+        self._check(self.ts_mux_async(stream, nbytes, au, n, pts, dts, prm, out, au_packet, summary, out_cap=need), "hbs_ts_mux")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_ts_mux: error %d" % int(s["error"]))
+        return out[:need], au_packet.cpu().numpy().view(np.uint32).copy(), s
 
     # ---- access units -----------------------------------------------------------------
 

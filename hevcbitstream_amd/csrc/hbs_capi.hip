@@ -21,6 +21,7 @@
 #include "hbs_lenpref.h"
 #include "hbs_au.h"
 #include "hbs_ts.h"
+#include "hbs_tsmux.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -35,8 +36,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kAws    hbs_access_units' scratch.  hbs_au_keep uses its first 16 bytes (where hbs_access_units keeps its digest): the calls
  *         of a context are ordered by its one stream, so neither sees the other's data
  * kLws    the scratch of hbs_annexb_to_lenpref and hbs_lenpref_to_annexb
- * kTws    hbs_ts_demux's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kBufs };
+ * kTws    hbs_ts_demux's scratch
+ * kMws    hbs_ts_mux's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -687,6 +689,40 @@ int hbs_ts_demux(hbs_ctx* c, const uint8_t* d_ts, uint64_t ts_bytes, int packet_
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_ts_demux(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_ts_demux");
+}
+
+int hbs_ts_mux(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+               const hbs_access_unit* d_au, uint64_t n_aus, const uint64_t* d_pts, const uint64_t* d_dts,
+               const hbs_ts_mux_params* params, uint8_t* d_out, uint64_t out_cap, uint32_t* d_au_packet, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_ts_mux_params) == 48 && sizeof(hbs_access_unit) == 64, "hbs_ts_mux_params / hbs_access_unit layout");
+    if (!c || !d_summary || !hbs::tsm_params_ok(params) || n_aus > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_aus && (!d_au || (stream_bytes && !d_stream))) return HBS_E_ARG;
+    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_au, 15) || misaligned(d_summary, 15) ||
+        misaligned(d_pts, 7) || misaligned(d_dts, 7) || misaligned(d_au_packet, 3)) {
+        snprintf(c->err, sizeof(c->err), "stream/output/AU table/summary pointers must be 16-byte aligned, the times 8-byte, the packet numbers 4-byte");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::TsmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_stream; a.n = stream_bytes; a.au = d_au; a.n_aus = n_aus;
+    a.pts = reinterpret_cast<const unsigned long long*>(d_pts); a.dts = reinterpret_cast<const unsigned long long*>(d_dts);
+    a.B = (uint32_t)params->packet_bytes; a.lead = hbs::ts_lead(params->packet_bytes); a.pid = (uint32_t)params->pid;
+    a.flags = params->flags; a.cc_es = params->cc_es; a.cc_pat = params->cc_pat; a.cc_pmt = params->cc_pmt; a.pcr_lead = params->pcr_lead;
+    a.out = d_out; a.out_cap = out_cap; a.au_packet = d_out ? d_au_packet : nullptr; a.summary = d_summary;
+    uint8_t psi[2][188];
+    if (hbs::tsm_psi_host(params, psi[0], psi[1]) != 0) return HBS_E_ARG;
+    memcpy(&a.psi, psi, sizeof(a.psi));
+    /* the copy's grid: the packets out_cap has room for, and no more than the call can make */
+    const uint64_t fit = out_cap / a.B, most = hbs::tsm_packet_bound(n_aus, stream_bytes);
+    const uint64_t reach = d_out && n_aus ? (fit < most ? fit : most) : 0;
+    a.copy_blocks = (reach + hbs::kTsmPacketsPerBlock - 1) / hbs::kTsmPacketsPerBlock;
+    const int rc = carve(c, c->buf[kMws], "hipMalloc(transport mux scratch)", [&](hbs::Carver& w) { hbs::lay_tsm(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_ts_mux(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_ts_mux");
 }
 
 uint64_t hbs_au_sps_poc_offset(void) { return offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4); }

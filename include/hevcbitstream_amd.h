@@ -492,6 +492,94 @@ int hbs_ts_packet_host(const uint8_t* packet, int packet_bytes, int pid, hbs_ts_
 int hbs_ts_find_pid_host(const uint8_t* bytes, uint64_t n, int packet_bytes, int stream_type, int* program_out);
 
 /*
+ * ---- access units -> MPEG transport stream packets, PES times, PAT / PMT -----------------------------------------------
+ * hbs_ts_mux is the way back: every access unit of an Annex-B stream in device memory becomes one PES packet, cut into
+ * transport packets of one PID, with a PAT and a PMT where asked for.  hbs_ts_demux of the output returns the AUs' bytes back
+ * to back, their times, and RANDOM_ACCESS on the IRAP AUs.
+ *
+ * ES BYTES OF AU a.  stream[unit_begin_a, unit_end_a), E of them (E may be 0).  Of d_au only unit_begin, unit_end and
+ * flags & HBS_AU_IRAP are read; AUs need not touch.  An entry is well-formed when unit_begin <= unit_end <= stream_bytes and
+ * unit_begin_a >= unit_end_{a-1}; so a GOP cut is muxed by passing d_au + first, with no filter pass in between.
+ * TIMES.  pts = d_pts[a], dts = d_dts ? d_dts[a] : ~0; ~0 means absent, every other value must be below 2^33, a DTS without a
+ * PTS is an error.  f = 3 when a DTS is present and differs from the PTS, 2 when a PTS is present and f is not 3, else 0.
+ * d_pts == NULL: no AU has a PTS.
+ * PES HEADER.  00 00 01 E0 00 00 84 (f << 6) (H - 9), then the time bytes: H = 9, 14 or 19.  PES_packet_length is 0 (legal
+ * for video in a transport stream).  A time t is the five bytes
+ *   marker << 4 | ((t >> 30) & 7) << 1 | 1,  t >> 22,  ((t >> 15) & 0x7F) << 1 | 1,  t >> 7,  (t & 0x7F) << 1 | 1
+ * (each modulo 256), the marker 2 for a PTS alone, 3 for the PTS of a pair, 1 for the DTS.
+ * PACKETS OF AU a.  T = H + E.  The first packet always carries an adaptation field: its length byte, a flags byte (0x40 if
+ * IRAP, 0x10 if PCR) and, with a PCR, the six bytes base >> 25, base >> 17, base >> 9, base >> 1, (base & 1) << 7 | 0x7E, 0
+ * with base = ((f == 3 ? dts : pts) - pcr_lead) mod 2^33.  A PCR is present iff HBS_TSMUX_PCR is set and f != 0.  That is
+ * A1 = 2 or 8 bytes, and R1 = 184 - A1.  If T <= R1 the AU is one packet with adaptation_field_length 183 - T, FF stuffing
+ * behind the flags and the PCR.  Otherwise the first packet carries R1 bytes with adaptation_field_length A1 - 1 and the rest
+ * goes 184 bytes to a packet; only the last of these may be short: with r bytes, 1 <= r < 184, its
+ * adaptation_field_length is 183 - r -- a flags byte 00 and then FF when that is >= 1, the length byte alone when it is 0.
+ * N(a) = 1 + ceil((T - R1) / 184) packets (1 when T <= R1): what hbs_ts_mux_au_packets_host returns.
+ * TRANSPORT HEADER.  47, pusi << 6 | pid >> 8, pid & 0xFF, afc << 4 | cc: pusi on an AU's first packet, afc 3 with an
+ * adaptation field, else 1, cc = (cc_es + j) & 15 for the j-th ES packet of the call.
+ * PSI.  A PAT packet and then a PMT packet stand in front of AU 0 unless HBS_TSMUX_NO_PSI is set, and with
+ * HBS_TSMUX_PSI_AT_IRAP also in front of every later AU with HBS_AU_IRAP (HBS_TSMUX_NO_PSI wins over it).  The k-th pair
+ * (from 0) carries cc = (cc_pat + k) & 15 and (cc_pmt + k) & 15.  Both packets are 47 40|pid>>8 pid&FF 10|cc, a
+ * pointer_field 0, the section, then FF to byte 188:
+ *   PAT section   00 B0 0D tsid(2) C1 00 00 program(2) E0|pmt_pid>>8 pmt_pid&FF crc(4)                       (on PID 0)
+ *   PMT section   02 B0 18 program(2) C1 00 00 E0|pid>>8 pid&FF F0 00 24 E0|pid>>8 pid&FF F0 06 05 04 'H' 'E' 'V' 'C' crc(4)
+ *                 (on pmt_pid; the PCR PID is the ES PID)
+ * crc = MPEG-2 CRC-32 of the section in front of it: polynomial 0x04C11DB7, initial value 0xFFFFFFFF, not reflected, no
+ * final xor, most significant byte first.  hbs_ts_mux_psi_host writes the pair with k = 0; the call builds it once and hands
+ * it to the kernel by value, the device patches the cc nibble.
+ *
+ * THE CALL.  The output is those packets in that order, packet_bytes each: with 192 four zero bytes stand in front of the
+ * 188, with 204 sixteen behind.  d_au_packet[a] (optional, n_aus + 1 entries) = the number of the packet AU a's PES begins
+ * in -- PSI packets count, so an AU behind a pair begins two packets later -- and entry n_aus the total.
+ * d_out == NULL: plan only, the summary alone is written.  n_aus == 0 is valid (no packet at all).
+ *   d_summary   nal_count = packets, nal_found = n_aus, rbsp_bytes = ES bytes carried, stream_bytes = output bytes,
+ *               stop_reason = 0, reserved[1] = ES packets (the next call's cc_es is (cc_es + reserved[1]) & 15),
+ *               reserved[2] = PSI pairs.
+ *               error = HBS_E_ARG when an AU entry is malformed, a time rule is broken (reserved[0] = 1 + the lowest such
+ *               AU; the counts mean nothing) or the call has more than 2^32 - 1 packets (reserved[0] = 0).  Else
+ *               HBS_E_CAPACITY when out_cap is below the output; the counts are right.  On either error nothing is written
+ *               to d_out or d_au_packet.
+ * Refused with HBS_E_ARG at once, before anything is written: params NULL or out of range (packet_bytes not 188 / 192 / 204,
+ * a PID outside 16..8190 or pid == pmt_pid, program_number outside 1..65535, transport_stream_id outside 0..65535, unknown
+ * flags, a continuity counter above 15, reserved != 0), n_aus above 2^32 - 1, misaligned pointers.
+ * Nothing outside [d_out, d_out + output bytes) and d_au_packet[0, n_aus] is stored; no load touches a 16-byte granule that
+ * holds no byte of the stream; no host synchronisation; scratch comes from the context's workspace (8 bytes an AU, and 4 bytes
+ * per 2048 packets of what out_cap and the stream can hold).
+ * Alignment: d_stream, d_out, d_au, d_summary 16 bytes; d_pts, d_dts 8 bytes; d_au_packet 4 bytes.
+ * STATED LIMITS: one AU to one PES packet; one PID; no null-packet padding to a constant bitrate; no access-unit delimiters
+ * are inserted (13818-1 wants one per HEVC AU: that is the caller's stream); no descriptors beyond the registration descriptor.
+ *
+ * Host side, plain C, no GPU involved.
+ * hbs_ts_mux_psi_host: the PAT and PMT packets of the first pair (188 transport bytes each).  0, or HBS_E_ARG (a NULL
+ * pointer, params out of range).
+ * hbs_ts_mux_au_packets_host: N(a) for es_bytes ES bytes; time_fields 0: no time, 1: a PTS, 2: a PTS and a DTS that differs;
+ * pcr non-zero: HBS_TSMUX_PCR is set (it adds nothing to an AU without a time).  0 for another time_fields.
+ */
+typedef struct hbs_ts_mux_params {   /* HOST memory, 48 bytes */
+    int32_t  packet_bytes;        /* 188, 192 (4 zero bytes in front of each packet) or 204 (16 zero bytes behind) */
+    int32_t  pid, pmt_pid;        /* 16..8190, different from each other */
+    int32_t  program_number;      /* 1..65535 */
+    int32_t  transport_stream_id; /* 0..65535 */
+    uint32_t flags;               /* HBS_TSMUX_* */
+    uint32_t cc_es, cc_pat, cc_pmt; /* continuity counters of the first packet of each PID, 0..15 */
+    uint32_t reserved;            /* 0 */
+    uint64_t pcr_lead;            /* 90 kHz ticks the PCR runs behind the DTS */
+} hbs_ts_mux_params;
+#define HBS_TSMUX_PCR          1u  /* a PCR in the first packet of every AU that has a time */
+#define HBS_TSMUX_PSI_AT_IRAP  2u  /* PAT + PMT also in front of every AU with HBS_AU_IRAP */
+#define HBS_TSMUX_NO_PSI       4u  /* no PAT / PMT at all (a segment that continues another) */
+
+struct hbs_access_unit;            /* hbs_access_units' record, below */
+int hbs_ts_mux(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
+               const struct hbs_access_unit* d_au, uint64_t n_aus,
+               const uint64_t* d_pts, const uint64_t* d_dts /* nullable */,
+               const hbs_ts_mux_params* params,
+               uint8_t* d_out, uint64_t out_cap,
+               uint32_t* d_au_packet /* optional, n_aus + 1 */, hbs_summary* d_summary);
+int hbs_ts_mux_psi_host(const hbs_ts_mux_params* params, uint8_t pat188[188], uint8_t pmt188[188]);
+uint64_t hbs_ts_mux_au_packets_host(uint64_t es_bytes, int time_fields /* 0, 1, 2 */, int pcr);
+
+/*
  * K4: header parse, one NAL per lane (64 per wavefront), over the RBSP arena and index that
  * hbs_index_extract produced.  For NAL k it does what read_hevc_nal_unit()
  * does after nal_to_rbsp (hevc_stream.c:175-239): NAL header, then by type the
