@@ -1114,6 +1114,9 @@ HBS_D void write_one_nal(ParserT<kModeWrite>& ps, int nal_unit_type, int nal_lay
     out->rc = ps.b.overrun() ? -1 : 0;
     const uint32_t whole = ps.b.pos >> 3;
     out->rbsp_size = whole > ps.b.size ? ps.b.size : whole;
+    /* an SPS ends without trailing bits: the bits of its unfinished byte are not part of the result (bs_pos, :1324), and
+     * the buffer behind rbsp_size stays as cleared */
+    if ((ps.b.pos & 7u) != 0u && whole < ps.b.size) ps.b.wbuf[whole] = 0;
 }
 
 } // namespace hbs

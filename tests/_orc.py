@@ -256,5 +256,12 @@ class ReferenceHevc(_HevcParser):
         buf = np.frombuffer(bytes(nal) + b"\xff" * 8, dtype=np.uint8).copy()
         return self.L.read_hevc_nal_unit(self.h, _ptr(buf), len(nal))
 
+    def write(self, size):
+        """write_hevc_nal_unit (hevc_stream.c:1249-1327) of the NAL the parser holds into a buffer of `size` bytes:
+        (return value, NAL bytes, what it left in h->slice_data->rbsp_size)"""
+        out = np.zeros(size + 16, dtype=np.uint8)
+        rc = int(self.L.write_hevc_nal_unit(self.h, _ptr(out), size))
+        return rc, bytes(out[:max(rc, 0)]), self.slice_data()[0]
+
     def close(self):
         pass        # the reference leaks slice_data->rbsp_buf; keep the object alive instead

@@ -176,8 +176,8 @@ def parse_trace(rbsp, idx, cap=65536):
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 
 
-def write_nal(nal_type, layer, tid, slot, sps_slot, pps, cap):
-    """write_one_nal single-stepped: (result record, RBSP bytes written)"""
+def write_nal(nal_type, layer, tid, slot, sps_slot, pps, cap, whole=False):
+    """write_one_nal single-stepped: (result record, RBSP bytes written; whole: all `cap` bytes of the buffer)"""
     L = lib()
     L.sim_write_nal.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.sim_write_nal.restype = C.c_int
@@ -188,4 +188,5 @@ def write_nal(nal_type, layer, tid, slot, sps_slot, pps, cap):
                     sps_slot.ctypes.data if sps_slot is not None else None, pps.ctypes.data if pps is not None else None,
                     out.ctypes.data, cap, res.ctypes.data)
     r = res[0]
-    return r, out[:int(r["rbsp_size"])].copy()
+    assert not out[cap:].any()
+    return r, out[:cap if whole else int(r["rbsp_size"])].copy()

@@ -8,6 +8,7 @@ import time
 import numpy as np
 import pytest
 
+from tests import _orc
 from tests._parsecmp import compare, oracle_pass
 from tests.hevc_synth import Synth, annexb, stream_4k30
 from tests.test_sim_parse_logic import broken, sequence
@@ -174,8 +175,9 @@ def test_out_of_spec_slices_are_walked_again_by_themselves(ctx):
 def test_write_headers_batch_roundtrip(ctx):
     """K5 over a whole parsed batch (config-3 style stream, ~8k NALs): VPS and PPS come back bit for bit
     (SURVEY: "round-trips VPS/PPS exactly"), an SPS comes back without its trailing bits and unfinished
-    last byte: a prefix of the RBSP it was parsed from.  (Slices: byte parity with the reference's writer,
-    which re-codes some fields, is in the golden tests; here only that every one is written.)"""
+    last byte: a prefix of the RBSP it was parsed from.  Slices: the reference's writer re-codes some fields; when the
+    compiled reference travelled with the tree, every slice is held against what it writes from the same NAL (bytes,
+    rbsp_size, slice_data_size); the golden batches of tests/test_gpu_write.py hold them against recorded answers."""
     stream, n = stream_4k30(17, n_pictures=1000, slices_per_picture=8, idr_every=60, payload_bytes=(60, 120))
     s, idx, arena, parsed, structs = gpu_parse(ctx, stream)
     assert (parsed["rc"] >= 0).all()
@@ -185,6 +187,9 @@ def test_write_headers_batch_roundtrip(ctx):
     out = out.cpu().numpy()
     assert (written["rc"] == 0).all()
     kinds = {32: 0, 33: 0, 34: 0, "slice": 0}
+    ref = _orc.ReferenceHevc() if _orc.reference() is not None else None
+    size = (4 * cap + 2) // 3                                   # the reference writes into size * 3 / 4 bytes (hevc_stream.c:1266)
+    assert size * 3 // 4 == cap
     for k in range(len(parsed)):
         t = int(parsed["nal_unit_type"][k])
         got = bytes(out[k * cap:k * cap + int(written["rbsp_size"][k])])
@@ -198,4 +203,15 @@ def test_write_headers_batch_roundtrip(ctx):
         else:
             assert 3 <= len(got) < cap and got[:2] == rb[:2], (k, len(got))
             kinds["slice"] += 1
+        if ref is not None:                                    # (stream_4k30 holds VPS, SPS, PPS and slices, nothing else: the reference writes every one)
+            nal = bytes(s[int(idx["start"][k]):int(idx["end"][k])])
+            assert ref.read(nal) == int(parsed["rc"][k]), k
+            if t not in (32, 33, 34):
+                wrc, out_nal, sds = ref.write(size)
+                assert wrc >= 0, (k, wrc)
+                want = _orc.reference().nal_to_rbsp(out_nal)[3]
+                assert got == want and not out[k * cap + len(got):(k + 1) * cap].any(), (k, got.hex(), want.hex())
+                assert int(written["slice_data_size"][k]) == sds, (k, int(written["slice_data_size"][k]), sds)
+                kinds["held to the reference"] = kinds.get("held to the reference", 0) + 1
     assert min(kinds.values()) > 0, kinds
+    assert kinds.get("held to the reference", kinds["slice"]) == kinds["slice"], kinds      # all of them, or none (no compiled reference here)

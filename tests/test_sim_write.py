@@ -10,22 +10,9 @@ from tests import _orc, _sim
 from tests._parsecmp import which_struct
 from tests.hevc_synth import annexb
 
+from tests._writegold import field_index, slot_bytes
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-SPS_SLOT = None
-
-
-def slot_bytes(kind):
-    size = _orc.layout()[_orc.STRUCT_TYPES[kind]]["size"]
-    if kind == "sps":
-        return ((size + 15) // 16) * 16 + 4 * (3 * 32 + 4 * 32 * 32)      # struct + derived RPS tables
-    return ((size + 15) // 16) * 16
-
-
-def field_index(kind, name):
-    for n, i, c in _orc.flat_fields(_orc.STRUCT_TYPES[kind]):
-        if n == name:
-            return i
-    raise KeyError(name)
 
 
 def run_sequence(orc, steps):
@@ -46,8 +33,11 @@ def run_sequence(orc, steps):
             for name, value in st["edits"]:
                 view[field_index(kind, name)] = value
             cap = st["size"] * 3 // 4
-            res, rbsp = _sim.write_nal(t, int(parsed["nal_layer_id"][k]), int(parsed["nal_temporal_id_plus1"][k]), slot,
-                                       last["sps"], last["pps"], cap)
+            res, region = _sim.write_nal(t, int(parsed["nal_layer_id"][k]), int(parsed["nal_temporal_id_plus1"][k]), slot,
+                                         last["sps"], last["pps"], cap, whole=True)
+            rbsp = region[:int(res["rbsp_size"])]
+            # behind rbsp_size the buffer stays as cleared: an SPS ends on an unfinished byte, whose bits are not part of the result
+            assert not region[int(res["rbsp_size"]):].any(), (k, kind)
             if st["write_rc"] < 0:
                 assert int(res["rc"]) < 0, k
             else:
@@ -67,3 +57,53 @@ def test_writers_match_reference(orc):
     assert len(vectors) >= 8
     for v in vectors:
         run_sequence(orc, v["steps"])
+
+
+def test_sequences_parse_the_same_in_one_batch():
+    """What tests/test_gpu_write.py builds on when it holds every NAL of a batch of all ten sequences (tiled: the ten again
+    behind themselves, W.TILES times) against what the reference wrote for the sequence alone: parsed as one stream, every step keeps
+    the rc and the struct (an SPS: with its derived tables) it has when its sequence is parsed by itself."""
+    from tests import _writegold as W
+    seqs = W.vectors()
+    alone = []
+    for v in seqs:
+        g = W.Gold([v])
+        idx, arena, _ = _sim.index_extract(np.frombuffer(annexb(g.nals), dtype=np.uint8))
+        parsed, structs = _sim.parse_headers(arena, idx, fix=1)
+        assert np.array_equal(parsed["rc"], g.read_rc), v["seed"]
+        for k in range(g.n):
+            off = int(parsed["struct_off"][k])
+            alone.append((v["seed"], k, int(parsed["rc"][k]), g.kind[k], structs[off:off + W.slot_bytes(g.kind[k])].copy() if g.kind[k] else None))
+    g = W.Gold(seqs)
+    assert g.n == 170 == len(alone)
+    idx, arena, _ = _sim.index_extract(np.frombuffer(annexb(g.nals * W.TILES), dtype=np.uint8))
+    parsed, structs = _sim.parse_headers(arena, idx, fix=1)
+    assert len(parsed) == W.TILES * g.n
+    for j in range(W.TILES * g.n):
+        seed, k, rc, kind, slot = alone[j % g.n]
+        if (seed, k) in W.LEFT_OUT:
+            continue
+        assert int(parsed["rc"][j]) == rc, (j, seed, k)
+        if kind:
+            off = int(parsed["struct_off"][j])
+            assert np.array_equal(structs[off:off + len(slot)], slot), (j, seed, k, kind)
+
+
+def test_slice_that_reads_its_own_row(orc):
+    """tests/golden/write_rows.json.gz: an IDR set to P type under lists_modification_present_flag counts the used pictures of
+    a row that nothing has written; single-stepped with a cleared row it comes out as the reference wrote it"""
+    from tests import _writegold as W
+    fx = W.rows_fixture()
+    idx, arena, _ = _sim.index_extract(np.frombuffer(annexb([bytes.fromhex(x) for x in fx["nals"]]), dtype=np.uint8))
+    parsed, structs = _sim.parse_headers(arena, idx, fix=1)
+    kinds = ["vps", "sps", "pps", "sh", "sh"]
+    part = lambda j: structs[int(parsed["struct_off"][j]):int(parsed["struct_off"][j]) + slot_bytes(kinds[j])].copy()      # noqa: E731
+    k = fx["reader"]
+    slot = part(k)
+    for name, value in fx["edits"]:
+        slot.view(np.int32)[field_index("sh", name)] = value
+    res, rbsp = _sim.write_nal(int(parsed["nal_unit_type"][k]), int(parsed["nal_layer_id"][k]), int(parsed["nal_temporal_id_plus1"][k]),
+                               slot, part(1), part(2), fx["size"] * 3 // 4)
+    rc, _, out = orc.rbsp_to_nal(bytes(rbsp))
+    assert int(res["rc"]) == 0 and rc == fx["write_rc"] and out.hex() == fx["out"]
+    assert int(res["slice_data_size"]) == fx["slice_data_size"]
