@@ -13,7 +13,8 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   TS_PES, TS_PACKET, TS_FAULT, TS_OTHER, TS_SKIPPED, TS_NO_PAYLOAD, TS_PAYLOAD, TS_PES_START,
                   TS_F_PTS, TS_F_DTS, TS_F_RANDOM_ACCESS, TS_F_DISCONTINUITY, TS_F_DATA_ALIGNED, TS_NO_TIME,
                   STREAM_TYPE_HEVC, ts_packet, ts_find_pid,
-                  TS_MUX_PARAMS, TSMUX_PCR, TSMUX_PSI_AT_IRAP, TSMUX_NO_PSI, ts_mux_params, ts_mux_psi, ts_mux_au_packets)
+                  TS_MUX_PARAMS, TSMUX_PCR, TSMUX_PSI_AT_IRAP, TSMUX_NO_PSI, ts_mux_params, ts_mux_psi, ts_mux_au_packets,
+                  AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST, aud_nal)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
            "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
@@ -23,4 +24,5 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "TS_PES", "TS_PACKET", "TS_FAULT", "TS_OTHER", "TS_SKIPPED", "TS_NO_PAYLOAD", "TS_PAYLOAD", "TS_PES_START",
            "TS_F_PTS", "TS_F_DTS", "TS_F_RANDOM_ACCESS", "TS_F_DISCONTINUITY", "TS_F_DATA_ALIGNED", "TS_NO_TIME",
            "STREAM_TYPE_HEVC", "ts_packet", "ts_find_pid",
-           "TS_MUX_PARAMS", "TSMUX_PCR", "TSMUX_PSI_AT_IRAP", "TSMUX_NO_PSI", "ts_mux_params", "ts_mux_psi", "ts_mux_au_packets"]
+           "TS_MUX_PARAMS", "TSMUX_PCR", "TSMUX_PSI_AT_IRAP", "TSMUX_NO_PSI", "ts_mux_params", "ts_mux_psi", "ts_mux_au_packets",
+           "AUINS_AUD", "AUINS_PARAM_SETS", "AUINS_PARAM_SETS_FIRST", "aud_nal"]

@@ -28,6 +28,8 @@ ACCESS_UNIT = np.dtype([("first_nal", "<u8"), ("unit_begin", "<u8"), ("unit_end"
 AU_CARRY = np.dtype([("flags", "<u4"), ("anchor_poc_lsb", "<i4"), ("anchor_poc_msb", "<i4"), ("reserved", "<u4")])
 AU_IRAP, AU_IDR, AU_CVS_START, AU_ANCHOR, AU_NO_PICTURE, AU_DAMAGED, AU_PARAM_SETS, AU_END_OF_SEQ = 1, 2, 4, 8, 16, 32, 64, 128
 AUKEEP_PARAM_SETS = 1
+# flags of hbs_au_insert
+AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST = 1, 2, 4
 # layout of hbs_ts_pes / hbs_ts_packet, the packet classes and the flags of hbs_ts_demux
 TS_PES = np.dtype([("out_off", "<u8"), ("pts", "<u8"), ("dts", "<u8"), ("packet", "<u4"), ("flags", "<u4")])
 TS_PACKET = np.dtype([("cls", "<i4"), ("pid", "<u4"), ("off", "<u4"), ("len", "<u4"), ("es_off", "<u4"), ("es_len", "<u4"),
@@ -70,7 +72,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset",
            "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb",
            "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
-           "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host"]
+           "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
+           "hbs_au_insert", "hbs_aud_nal_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -212,6 +215,10 @@ def load_library():
     lib.hbs_ts_mux_psi_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hbs_ts_mux_au_packets_host.argtypes = [C.c_uint64, C.c_int, C.c_int]
     lib.hbs_ts_mux_au_packets_host.restype = C.c_uint64
+    lib.hbs_au_insert.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_void_p]
+    lib.hbs_aud_nal_host.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
     _lib = lib
     return lib
 
@@ -261,6 +268,16 @@ def ts_mux_au_packets(es_bytes, time_fields=0, pcr=False):
     """hbs_ts_mux_au_packets_host: the transport packets of an access unit of es_bytes bytes; time_fields 0: no time, 1: a PTS,
     2: a PTS and a DTS that differs.  No GPU involved."""
     return int(load_library().hbs_ts_mux_au_packets_host(int(es_bytes), int(time_fields), 1 if pcr else 0))
+
+
+def aud_nal(temporal_id_plus1, slice_types):
+    """hbs_aud_nal_host: the seven bytes (start code included) of the access-unit delimiter hbs_au_insert places in front of an
+    AU whose record has that temporal_id_plus1 and slice_types.  No GPU involved."""
+    out = np.zeros(7, dtype=np.uint8)
+    rc = load_library().hbs_aud_nal_host(int(temporal_id_plus1), int(slice_types) & 0xFFFFFFFF, out.ctypes.data)
+    if rc != 0:
+        raise HbsError("hbs_aud_nal_host failed: %d" % rc)
+    return out.tobytes()
 
 
 class Context:
@@ -964,6 +981,55 @@ class Context:
             raise HbsError("hbs_access_units: error %d" % int(s["error"]))
         return (au[: aus * ACCESS_UNIT.itemsize].cpu().numpy().view(ACCESS_UNIT).copy(), nal_au[:n_nals].cpu().numpy().view(np.uint32).copy(),
                 s, carry_out.cpu().numpy().view(AU_CARRY).copy())
+
+    def au_insert_async(self, stream, stream_bytes, index, parsed, n_nals, au, nal_au, n_aus, first_au, au_count, flags,
+                        out, index_out, nal_src, nal_au_out, au_out, summary, out_cap=None, index_cap=0):
+        """Enqueue hbs_au_insert on the current torch stream.  Everything but the counts and flags is a device tensor (out None:
+        plan only; index_out, nal_src, nal_au_out, au_out may be None); index_cap: entries each per-NAL table has room for.
+        Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        return self.lib.hbs_au_insert(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None,
+                                      p(parsed) if n_nals else None, int(n_nals), p(au) if n_aus else None,
+                                      p(nal_au) if n_aus and n_nals else None, int(n_aus), int(first_au), int(au_count), int(flags),
+                                      p(out), int(out_cap), p(index_out), p(nal_src), p(nal_au_out), int(index_cap), p(au_out), p(summary))
+
+    def au_insert(self, stream, index, parsed, n_nals, au, nal_au, first_au=0, au_count=None, flags=AUINS_AUD | AUINS_PARAM_SETS,
+                  stream_bytes=None):
+        """Convenience: AUDs and the parameter sets in force in front of the access units [first_au, first_au + au_count) of
+        `stream` (device uint8 tensor).  index / parsed / au / nal_au: host ndarrays of the records or device tensors of them.
+        Plans first, allocates the exact outputs, runs.  Returns (out, index_out, nal_src, nal_au_out, au_out, summary): device
+        tensors (uint8 views of the records; int32 for the two number tables) cut to what was written, and the summary record."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x):
+            if isinstance(x, np.ndarray):
+                return t.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to(dev) if x.size else t.zeros(64, dtype=t.uint8, device=dev)
+            return x
+        n_aus = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
+        index, parsed, au, nal_au = dv(index), dv(parsed), dv(au), dv(nal_au)
+        if au_count is None:
+            au_count = max(n_aus - first_au, 0)
+        nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        args = (stream, nbytes, index, parsed, n_nals, au, nal_au, n_aus, first_au, au_count, flags)
+        self._check(self.au_insert_async(*args, None, None, None, None, None, summary), "hbs_au_insert")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_au_insert: error %d" % int(s["error"]))
+        need, m, r = int(s["stream_bytes"]), int(s["nal_count"]), int(s["reserved"][2])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        index_out = t.empty(max(m, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
+        nal_src, nal_au_out = (t.empty(max(m, 1), dtype=t.int32, device=dev) for _ in range(2))
+        au_out = t.empty(max(r, 1) * ACCESS_UNIT.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.au_insert_async(*args, out, index_out, nal_src, nal_au_out, au_out, summary, out_cap=need, index_cap=m), "hbs_au_insert")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_au_insert: error %d" % int(s["error"]))
+        return out[:need], index_out[: m * NAL_ENTRY.itemsize], nal_src[:m], nal_au_out[:m], au_out[: r * ACCESS_UNIT.itemsize], s
 
     def au_keep_async(self, nal_au, parsed, n_nals, first_au, au_count, keep, param_sets=False):
         """Enqueue hbs_au_keep: keep (device uint8 tensor of n_nals) becomes the mask hbs_filter_annexb takes as d_keep."""

@@ -22,6 +22,7 @@
 #include "hbs_au.h"
 #include "hbs_ts.h"
 #include "hbs_tsmux.h"
+#include "hbs_auins.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -37,8 +38,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  *         of a context are ordered by its one stream, so neither sees the other's data
  * kLws    the scratch of hbs_annexb_to_lenpref and hbs_lenpref_to_annexb
  * kTws    hbs_ts_demux's scratch
- * kMws    hbs_ts_mux's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kBufs };
+ * kMws    hbs_ts_mux's scratch
+ * kIws    hbs_au_insert's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -724,6 +726,47 @@ int hbs_ts_mux(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     const hipError_t e = hbs::launch_ts_mux(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_ts_mux");
 }
+
+int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                  const hbs_nal_entry* d_index, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
+                  const hbs_access_unit* d_au, const uint32_t* d_nal_au, uint64_t n_aus,
+                  uint64_t first_au, uint64_t au_count, uint32_t flags, uint8_t* d_out, uint64_t out_cap,
+                  hbs_nal_entry* d_index_out, uint32_t* d_nal_src, uint32_t* d_nal_au_out, uint64_t index_cap,
+                  hbs_access_unit* d_au_out, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_access_unit) == 64 && sizeof(hbs_parsed_nal) == 32 && sizeof(hbs_nal_entry) == 32, "record layouts");
+    if (!c || !d_summary || (flags & ~hbs::kAuinsFlags) || n_nals > 0xFFFFFFFFull || n_aus > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_nals && (!d_index || !d_parsed || (stream_bytes && !d_stream))) return HBS_E_ARG;
+    if (n_aus && (!d_au || (n_nals && !d_nal_au))) return HBS_E_ARG;
+    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_index, 15) || misaligned(d_parsed, 15) || misaligned(d_au, 15) ||
+        misaligned(d_au_out, 15) || misaligned(d_summary, 15) || misaligned(d_index_out, 7) || misaligned(d_nal_au, 3) ||
+        misaligned(d_nal_src, 3) || misaligned(d_nal_au_out, 3)) {
+        snprintf(c->err, sizeof(c->err), "stream/output/index/parsed/AU table/summary pointers must be 16-byte aligned, the output index 8-byte, the per-NAL numbers 4-byte");
+        return HBS_E_ARG;
+    }
+    if (d_out && out_cap > hbs::kAuinsOutCapMax) {
+        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::AuinsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = stream_bytes; a.index = d_index; a.parsed = d_parsed; a.n_nals = n_nals;
+    a.au = d_au; a.nal_au = d_nal_au; a.n_aus = n_aus;
+    a.a0 = first_au < n_aus ? first_au : 0;                         /* the range, clipped as hbs_au_keep clips it */
+    a.cnt = first_au < n_aus ? (au_count < n_aus - first_au ? au_count : n_aus - first_au) : 0;
+    if (!n_nals) a.cnt = 0;
+    a.flags = flags; a.out_cap = out_cap; a.index_cap = index_cap; a.summary = d_summary;
+    if (d_out) { a.index_out = d_index_out; a.nal_src = d_nal_src; a.nal_au_out = d_nal_au_out; a.au_out = d_au_out; }
+    a.t.src = d_stream; a.t.out = d_out; a.t.tiles = d_out && a.cnt ? hbs::piece_tiles(out_cap) : 0;
+    const int rc = carve(c, c->buf[kIws], "hipMalloc(AU insert scratch)", [&](hbs::Carver& w) { hbs::lay_auins(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_au_insert(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_au_insert");
+}
+
+int hbs_aud_nal_host(int temporal_id_plus1, uint32_t slice_types, uint8_t out[7]) { return hbs::auins_aud_host(temporal_id_plus1, slice_types, out); }
 
 uint64_t hbs_au_sps_poc_offset(void) { return offsetof(hevc_sps_t, log2_max_pic_order_cnt_lsb_minus4); }
 

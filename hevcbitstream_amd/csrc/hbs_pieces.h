@@ -1,5 +1,5 @@
 /* hbs_pieces.h -- the table of "pieces" a plan ends in and the copy over it (hbs_pieces.hip): what hbs_filter_annexb,
- * hbs_annexb_to_lenpref and hbs_lenpref_to_annexb share. */
+ * hbs_annexb_to_lenpref, hbs_lenpref_to_annexb and hbs_au_insert share. */
 #ifndef HBS_PIECES_H
 #define HBS_PIECES_H
 
@@ -19,6 +19,9 @@ struct PieceTable {
     uint32_t prefix;                /* bytes of the literal in front of each payload: length_size / startcode_bytes;
                                        0: none (a unit of the filter)                                               */
     int prefix_is_length;           /* 1: the payload's length, big-endian; 0: 00 .. 00 01                          */
+    unsigned long long* piece_lit;  /* NULL, or pieces words (prefix 0 then): piece j begins with its own literal of
+                                       piece_lit[j] >> 56 bytes (at most 7), byte i of it in bits [8 i, 8 i + 8); a piece of
+                                       such a table may be empty (hbs_au_insert: an AUD, a start code, nothing)              */
     unsigned long long* ctl;        /* 8: error, output bytes, pieces                                               */
     unsigned long long* piece_out;  /* pieces + 1: output offset of piece j (then the total)                        */
     unsigned long long* piece_delta;/* pieces: source offset minus output offset of its payload                     */

@@ -1,8 +1,9 @@
 /*
  * hbs_pieces.hip -- copy_pieces: the copy over a table of "pieces" (hbs_pieces.h) -- a short literal prefix, possibly of no
  * bytes, followed by a run of source bytes at its own byte misalignment.  One copy for hbs_filter_annexb (hbs_filter.hip: a
- * kept unit is a piece without a prefix), hbs_annexb_to_lenpref and hbs_lenpref_to_annexb (hbs_lenpref.hip); their plans
- * fill the table.  Two launches, neither of which waits for another workgroup:
+ * kept unit is a piece without a prefix), hbs_annexb_to_lenpref and hbs_lenpref_to_annexb (hbs_lenpref.hip) and hbs_au_insert
+ * (hbs_auins.hip: every piece with a literal of its own, of 0 to 7 bytes); their plans fill the table.  Two launches, neither
+ * of which waits for another workgroup:
  *
  *   k_piece_tiles    one lane per 64 KiB output tile: binary search of the piece its first byte lies in
  *   k_piece_copy     one workgroup per output tile: each lane takes 16-byte output chunks 4 KiB apart and finds the piece of
@@ -10,7 +11,9 @@
  *                    payload is loaded as aligned 16-byte non-temporal loads, realigned with alignbyte and stored as one
  *                    aligned 16-byte non-temporal store; a chunk that holds a prefix byte or spans pieces, and the output's
  *                    last chunk, is assembled byte by byte and stored byte-exact.  A payload of any size spreads over the
- *                    tiles it covers.  <kPrefix>: false for a table without prefixes, where all that is about them folds away.
+ *                    tiles it covers.  <kMode>: kPieceBare for a table without prefixes, where all that is about them folds
+ *                    away; kPiecePrefix for one prefix form a table; kPieceLiteral for a literal a piece (piece_lit), whose
+ *                    length is staged next to the piece and whose bytes are read where a chunk holds some.
  *
  * Traffic: the payloads read once and written once, 16 B a piece and 8 B a tile of scratch read.
  */
@@ -27,7 +30,8 @@ constexpr int kChunks = (int)(kPieceTileBytes / 16 / kCT);            /* 16-byte
 constexpr int kBatch = 4;                                             /* ... loads of that many issued together  */
 constexpr uint32_t kLdsPieces = 2048;                                 /* pieces a tile stages in LDS; more: read from memory */
 constexpr int32_t kFar = -8;                                          /* a piece that begins this far in front of the tile or
-                                                                         further: its prefix (<= 4 bytes) is not in the tile */
+                                                                         further: its prefix (<= 7 bytes) is not in the tile */
+enum : int { kPieceBare = 0, kPiecePrefix = 1, kPieceLiteral = 2 };
 
 __global__ __launch_bounds__(256) void k_piece_tiles(PieceTable a)
 {
@@ -64,10 +68,12 @@ __device__ __forceinline__ u32x4 zero4() { u32x4 z; z.x = z.y = z.z = z.w = 0; r
 
 /* the tile's pieces [j0, j0 + cnt): rel(i) = where piece j0 + i begins, relative to the tile, clamped to [kFar, kTile] (without
  * prefixes to [0, kTile]: where a piece begins in front of the tile says nothing then) */
-template <bool kPrefix>
+template <int kMode>
 struct TilePieces {
+    static constexpr bool kPrefix = kMode != kPieceBare;
     const int32_t* s_bound; const unsigned long long* s_delta;     /* staged: LDS */
-    const unsigned long long* piece_out; const unsigned long long* piece_delta;
+    const uint8_t* s_lit;                                          /* kPieceLiteral: the literals' lengths */
+    const unsigned long long* piece_out; const unsigned long long* piece_delta; const unsigned long long* piece_lit;
     uint64_t j0, t0;
     bool lds;
     __device__ __forceinline__ int32_t rel(uint32_t i) const
@@ -79,6 +85,7 @@ struct TilePieces {
         return t0 - b >= (uint64_t)(-kFar) ? kFar : -(int32_t)(t0 - b);
     }
     __device__ __forceinline__ uint64_t delta(uint32_t i) const { return lds ? s_delta[i] : piece_delta[j0 + i]; }
+    __device__ __forceinline__ int32_t lit_bytes(uint32_t i) const { return lds ? (int32_t)s_lit[i] : (int32_t)(piece_lit[j0 + i] >> 56); }
     /* the last piece i in [lo, hi] with rel(i) <= r (rel(lo) <= r holds) */
     __device__ __forceinline__ uint32_t find(uint32_t lo, uint32_t hi, uint32_t r) const
     {
@@ -92,23 +99,33 @@ struct TilePieces {
 
 /* an output chunk [r, r + len) of the tile that holds prefix bytes or spans pieces (or ends the output): assembled byte by
  * byte, each payload byte loaded from the piece it belongs to, each prefix byte computed */
-template <bool kPrefix>
-__device__ __forceinline__ void copy_chunk_bytes(const PieceTable& a, const TilePieces<kPrefix>& tp, uint32_t ip, uint32_t r, uint32_t len)
+template <int kMode>
+__device__ __forceinline__ void copy_chunk_bytes(const PieceTable& a, const TilePieces<kMode>& tp, uint32_t ip, uint32_t r, uint32_t len)
 {
+    constexpr bool kPrefix = kMode != kPieceBare;
     uint64_t clo = 0, chi = 0;
     int32_t b0 = tp.rel(ip), b1 = tp.rel(ip + 1);
     uint64_t delta = tp.delta(ip);
     uint64_t plen = 0;
     bool have_len = false;
-    const int32_t P = kPrefix ? (int32_t)a.prefix : 0;
+    int32_t P = kMode == kPiecePrefix ? (int32_t)a.prefix : 0;
+    uint64_t lit = 0;
+    if (kMode == kPieceLiteral) { lit = a.piece_lit[tp.j0 + ip]; P = (int32_t)(lit >> 56); }
 #pragma unroll 1
     for (uint32_t q = 0; q < len; ++q) {
         const int32_t ro = (int32_t)(r + q);
-        if (ro >= b1) { ip += 1; b0 = b1; b1 = tp.rel(ip + 1); delta = tp.delta(ip); have_len = false; }
+        if (kMode == kPieceLiteral) {          /* (pieces of such a table may be empty) */
+            if (ro >= b1) {
+                do { ip += 1; b0 = b1; b1 = tp.rel(ip + 1); } while (ro >= b1);
+                delta = tp.delta(ip); lit = a.piece_lit[tp.j0 + ip]; P = (int32_t)(lit >> 56);
+            }
+        } else if (ro >= b1) { ip += 1; b0 = b1; b1 = tp.rel(ip + 1); delta = tp.delta(ip); have_len = false; }
         const int32_t pos = ro - b0;           /* (a piece clamped to kFar: pos >= 8, payload) */
         uint64_t v;
         if (!kPrefix || pos >= P) {
             v = a.src[delta + tp.t0 + (uint32_t)ro];
+        } else if (kMode == kPieceLiteral) {
+            v = (lit >> (8 * pos)) & 0xFFu;
         } else if (a.prefix_is_length) {
             if (!have_len) { plen = a.piece_out[tp.j0 + ip + 1] - a.piece_out[tp.j0 + ip] - (uint64_t)P; have_len = true; }
             v = (plen >> (8 * (P - 1 - pos))) & 0xFFu;
@@ -127,11 +144,13 @@ __device__ __forceinline__ void copy_chunk_bytes(const PieceTable& a, const Tile
     }
 }
 
-template <bool kPrefix>
+template <int kMode>
 __global__ __launch_bounds__(kCT) void k_piece_copy(PieceTable a)
 {
+    constexpr bool kPrefix = kMode != kPieceBare;
     __shared__ int32_t s_bound[kLdsPieces + 1];
     __shared__ unsigned long long s_delta[kLdsPieces];
+    __shared__ uint8_t s_lit[kMode == kPieceLiteral ? kLdsPieces : 1];
     if (a.ctl[0] != 0) return;
     const uint64_t total = a.ctl[1];
     const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
@@ -139,18 +158,20 @@ __global__ __launch_bounds__(kCT) void k_piece_copy(PieceTable a)
     const uint32_t tlen = total - t0 < kTile ? (uint32_t)(total - t0) : kTile;
     const uint64_t j0 = a.tile_first[blockIdx.x], j1 = a.tile_first[blockIdx.x + 1];
     const uint32_t cnt = (uint32_t)(j1 - j0 + 1);     /* pieces [j0, j1]; piece_out[j1 + 1] exists (the total at the end) */
-    TilePieces<kPrefix> tp;
-    tp.s_bound = s_bound; tp.s_delta = s_delta; tp.piece_out = a.piece_out; tp.piece_delta = a.piece_delta;
+    TilePieces<kMode> tp;
+    tp.s_bound = s_bound; tp.s_delta = s_delta; tp.s_lit = s_lit;
+    tp.piece_out = a.piece_out; tp.piece_delta = a.piece_delta; tp.piece_lit = a.piece_lit;
     tp.j0 = j0; tp.t0 = t0; tp.lds = false;
     if (cnt <= kLdsPieces) {
         for (uint32_t i = threadIdx.x; i <= cnt; i += kCT) {
             s_bound[i] = tp.rel(i);
             if (i < cnt) s_delta[i] = a.piece_delta[j0 + i];
+            if (kMode == kPieceLiteral && i < cnt) s_lit[i] = (uint8_t)(a.piece_lit[j0 + i] >> 56);
         }
         __syncthreads();
         tp.lds = true;
     }
-    const int32_t P = kPrefix ? (int32_t)a.prefix : 0;
+    const int32_t P = kMode == kPiecePrefix ? (int32_t)a.prefix : 0;
     uint32_t lo = 0;
     uint32_t slow = 0;                        /* chunks done byte by byte, behind the batches: bit b + u */
     uint32_t slow_ip[kChunks];
@@ -167,7 +188,8 @@ __global__ __launch_bounds__(kCT) void k_piece_copy(PieceTable a)
             if (r < tlen) {
                 lo = tp.find(lo, cnt - 1, r);
                 ip[u] = lo;
-                if (tlen - r >= 16 && tp.rel(lo + 1) - (int32_t)r >= 16 && (!kPrefix || (int32_t)r - tp.rel(lo) >= P)) {
+                if (tlen - r >= 16 && tp.rel(lo + 1) - (int32_t)r >= 16 &&
+                    (!kPrefix || (int32_t)r - tp.rel(lo) >= (kMode == kPieceLiteral ? tp.lit_bytes(lo) : P))) {
                     const uint64_t s = tp.delta(lo) + t0 + r;
                     const uint64_t g = s & ~15ull;
                     sh[u] = (uint32_t)(s & 15u);
@@ -199,8 +221,9 @@ hipError_t copy_pieces(const PieceTable& t, hipStream_t st)
 {
     if (!t.tiles) return hipSuccess;
     hipLaunchKernelGGL(k_piece_tiles, dim3((unsigned)((t.tiles + 1 + 255) / 256)), dim3(256), 0, st, t);
-    if (t.prefix) hipLaunchKernelGGL(k_piece_copy<true>, dim3((unsigned)t.tiles), dim3(kCT), 0, st, t);
-    else hipLaunchKernelGGL(k_piece_copy<false>, dim3((unsigned)t.tiles), dim3(kCT), 0, st, t);
+    if (t.piece_lit) hipLaunchKernelGGL(k_piece_copy<kPieceLiteral>, dim3((unsigned)t.tiles), dim3(kCT), 0, st, t);
+    else if (t.prefix) hipLaunchKernelGGL(k_piece_copy<kPiecePrefix>, dim3((unsigned)t.tiles), dim3(kCT), 0, st, t);
+    else hipLaunchKernelGGL(k_piece_copy<kPieceBare>, dim3((unsigned)t.tiles), dim3(kCT), 0, st, t);
     return hipSuccess;
 }
 

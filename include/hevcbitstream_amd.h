@@ -547,7 +547,8 @@ int hbs_ts_find_pid_host(const uint8_t* bytes, uint64_t n, int packet_bytes, int
  * per 2048 packets of what out_cap and the stream can hold).
  * Alignment: d_stream, d_out, d_au, d_summary 16 bytes; d_pts, d_dts 8 bytes; d_au_packet 4 bytes.
  * STATED LIMITS: one AU to one PES packet; one PID; no null-packet padding to a constant bitrate; no access-unit delimiters
- * are inserted (13818-1 wants one per HEVC AU: that is the caller's stream); no descriptors beyond the registration descriptor.
+ * are inserted (13818-1 wants one per HEVC AU: hbs_au_insert adds them, and its d_au_out is this call's d_au); no descriptors
+ * beyond the registration descriptor.
  *
  * Host side, plain C, no GPU involved.
  * hbs_ts_mux_psi_host: the PAT and PMT packets of the first pair (188 transport bytes each).  0, or HBS_E_ARG (a NULL
@@ -798,6 +799,93 @@ uint64_t hbs_au_sps_poc_offset(void);   /* offsetof(hevc_sps_t, log2_max_pic_ord
 #define HBS_AUKEEP_PARAM_SETS 1
 int hbs_au_keep(hbs_ctx* ctx, const uint32_t* d_nal_au, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
                 uint64_t first_au, uint64_t au_count, int flags, uint8_t* d_keep /* n_nals bytes */);
+
+/*
+ * ---- access-unit delimiters and parameter sets in front of access units ---------------------------------------------
+ * hbs_au_insert makes an elementary stream fit for the container or segment it goes into: an access-unit delimiter (AUD, type
+ * 35; 13818-1 wants one per HEVC AU in a transport stream) in front of every picture that has none, and a copy of the
+ * parameter sets in force in front of every IRAP picture (and, when asked, of the first AU), so that every segment cut at an
+ * IRAP decodes alone.  Pure byte movement on the device over what the library already holds: the stream, d_index / d_parsed
+ * (n_nals records each) and what hbs_access_units wrote for them over the whole batch, d_au (n_aus records) and d_nal_au.  It
+ * also produces the output's index, AU table and per-NAL AU numbers, so hbs_ts_mux and hbs_annexb_to_lenpref run on the
+ * result without a second scan or parse.  This comment is the specification; tests/_auins_ref.py restates it as one loop over
+ * the AUs.
+ *
+ * THE RANGE.  AUs [first_au, first_au + au_count), clipped as hbs_au_keep clips it: empty when au_count is 0 or first_au is
+ * past the last AU, cut at n_aus otherwise.  An empty range gives an empty output.  NAL types and rc are taken from d_parsed
+ * as the parse wrote them (as hbs_au_keep takes them); nothing is read from the stream to classify.
+ *
+ * AU a OF THE RANGE.  f = first_nal, p = f + first_vcl, or f + nal_count when first_vcl == ~0u.
+ *   Insertion point   I = d_index[f].end if d_parsed[f].nal_unit_type == 35 (the AU begins with an AUD of its own: what is
+ *                     inserted goes behind it), else I = unit_begin.
+ *   AUD               inserted at I iff HBS_AUINS_AUD is set, the AU has no HBS_AU_NO_PICTURE and d_parsed[f].nal_unit_type
+ *                     != 35.  It is the seven bytes 00 00 00 01 46 T X: T = temporal_id_plus1 & 7 of the AU record,
+ *                     X = pic_type << 5 | 0x10 with pic_type 0 when slice_types == 4 (I only), 1 when slice_types != 0,
+ *                     != 4 and bit 0 is clear (P and I), else 2 (which includes slice_types == 0).  No special case for
+ *                     out-of-spec values: the formula is the definition.  hbs_aud_nal_host writes the same bytes.
+ *   Parameter sets    considered iff HBS_AUINS_PARAM_SETS is set and the AU has HBS_AU_IRAP, or HBS_AUINS_PARAM_SETS_FIRST is
+ *                     set and a is the first AU of the clipped range.  For each kind t = 32, 33, 34 in that order, q_t = the
+ *                     last NAL k < p with nal_unit_type == t and rc >= 0, of any layer and id, over the whole batch (the
+ *                     library's model of "the sets in force", as hbs_au_keep's).  No such NAL, or q_t >= f (the AU brings
+ *                     its own): nothing for t.  Otherwise 00 00 00 01 and stream[start_q, end_q) are inserted, behind the
+ *                     inserted AUD if there is one, else at I.
+ *   Output bytes      for every AU of the range in order: stream[unit_begin, I), the insertions, stream[I, unit_end).  An
+ *                     AU without insertions is copied verbatim.
+ *                     A copied set keeps its nuh_layer_id: one of another layer begins no access unit (7.4.2.4.4), so in
+ *                     front of an AU without an AUD a regrouping of the output counts it to the AU in front; d_au_out
+ *                     counts it to the AU it was inserted into.
+ *
+ * OUTPUT TABLES, all optional, all relative to the output, which has M NALs (index_cap: the room each of the three per-NAL
+ * tables has, in entries; d_au_out has room for the clipped range).
+ *   d_index_out[j]    start / end: the payload in the output.  rbsp_len 3 for an inserted AUD, the source entry's otherwise;
+ *                     rbsp_off the running sum of rbsp_len.  status 0 for an inserted AUD, else the source status with
+ *                     HBS_ST_UNTERMINATED cleared and then set on the last output entry only (the filter's rule).
+ *   d_nal_src[j]      the source NAL number; 0xFFFFFFFF for an inserted AUD, q_t for an inserted set: d_parsed / d_compact
+ *                     are carried over with a gather instead of a second parse.
+ *   d_nal_au_out[j]   the AU's number within the range, from 0 (what hbs_annexb_to_lenpref takes).
+ *   d_au_out[a - first_au]   the input record with first_nal, unit_begin, unit_end and nal_count moved to the output,
+ *                     first_vcl + the NALs inserted into the AU unless it is ~0u, HBS_AU_PARAM_SETS or-ed in when a set was
+ *                     inserted, everything else copied (what hbs_ts_mux takes).
+ * d_index_out is what hbs_index_extract of the output returns, with two exceptions: the filter's, for a short last NAL
+ * (hbs_filter_annexb above), and one of its own -- when something is inserted at stream offset 0 and the stream has bytes in
+ * front of its first start code, a scan of the output attaches those bytes to the inserted NAL.  Every other insertion point
+ * is followed by 00 00.
+ *
+ * d_summary: nal_count = M, nal_found = n_nals, rbsp_bytes = sum of the output rbsp_len, stream_bytes = output bytes,
+ * stop_reason = -1 if M > 0 else 0, reserved[0] = AUDs inserted, reserved[1] = parameter-set NALs inserted, reserved[2] = AUs
+ * in the clipped range.
+ *   error = HBS_E_ARG when the index is inconsistent by the filter's definition (any entry of the batch), or d_au / d_nal_au
+ *   do not tile the batch: first_nal_0 == 0, nal_count >= 1, first_nal_{a+1} == first_nal_a + nal_count_a, the last AU ends
+ *   at n_nals, unit_begin == d_index[first_nal - 1].end (0 for NAL 0), unit_end == d_index[first_nal + nal_count - 1].end,
+ *   first_vcl is ~0u or below nal_count, d_nal_au[k] names the AU that holds k -- for every AU and NAL of the batch, each
+ *   record checked before it is used.  Every count of the summary but nal_found is 0 then.
+ *   Otherwise error = HBS_E_CAPACITY when out_cap is below the output, or index_cap < M with any of the three per-NAL tables
+ *   given; the counts are right.  On either error nothing is written to any output but the summary.
+ * d_out == NULL: plan only -- the summary alone is written, no capacity is looked at.  n_nals == 0 or n_aus == 0 is valid:
+ * an empty output, nothing is checked.
+ * Refused with HBS_E_ARG at once, before anything is written: unknown flags, n_nals or n_aus above 2^32 - 1, out_cap above
+ * 2^46 with a d_out, missing or misaligned pointers.
+ * Nothing is stored outside [d_out, d_out + output bytes), the first M entries of the per-NAL tables, the range's entries of
+ * d_au_out and the summary; no load touches a 16-byte granule that holds no byte of the stream; no host synchronisation;
+ * scratch comes from the context's workspace (48 bytes an AU of the batch, 120 bytes an AU of the range, 8 bytes per 64 KiB of
+ * out_cap).
+ * Alignment: d_stream, d_out, d_index, d_parsed, d_au, d_au_out, d_summary 16 bytes; d_index_out 8 bytes; d_nal_au,
+ * d_nal_src, d_nal_au_out 4 bytes.
+ *
+ * hbs_aud_nal_host (plain C, no GPU): the seven bytes of the AUD the call inserts in front of an AU with that
+ * temporal_id_plus1 and slice_types.  0, or HBS_E_ARG (out NULL).
+ */
+#define HBS_AUINS_AUD               1u  /* an AUD in front of every AU with a picture that does not begin with one */
+#define HBS_AUINS_PARAM_SETS        2u  /* the sets in force in front of every AU with HBS_AU_IRAP                 */
+#define HBS_AUINS_PARAM_SETS_FIRST  4u  /* ... and in front of the first AU of the range, whatever it is          */
+int hbs_au_insert(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
+                  const hbs_nal_entry* d_index, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
+                  const hbs_access_unit* d_au, const uint32_t* d_nal_au, uint64_t n_aus,
+                  uint64_t first_au, uint64_t au_count, uint32_t flags,
+                  uint8_t* d_out, uint64_t out_cap,
+                  hbs_nal_entry* d_index_out, uint32_t* d_nal_src, uint32_t* d_nal_au_out, uint64_t index_cap,
+                  hbs_access_unit* d_au_out, hbs_summary* d_summary);
+int hbs_aud_nal_host(int temporal_id_plus1, uint32_t slice_types, uint8_t out[7]);
 
 /* Same, for a batch that continues an earlier one: d_initial_sps_slot (an SPS
  * slot = hevc_sps_t followed at hbs_sps_tables_offset() by its derived RPS

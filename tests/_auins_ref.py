@@ -1,0 +1,358 @@
+"""hbs_au_insert restated sequentially (include/hevcbitstream_amd.h is the specification): one plain loop over the access
+units of the range decides what is inserted where and lays the output out; the per-NAL tables follow from what the loop left.
+Written from the header's rules, not from the kernels.  Also the streams the tests run on: random_case, build, tiny_case."""
+import numpy as np
+
+from hevcbitstream_amd.api import ACCESS_UNIT, COMPACT, NAL_ENTRY, PARSED
+from tests import _au_ref as A
+from tests import _filter_ref as F
+
+AUD, PARAM_SETS, PARAM_SETS_FIRST = 1, 2, 4
+E_ARG, E_CAPACITY = -3, -4
+ST_UNTERMINATED = 4
+NONE = 0xFFFFFFFF
+SPS_OFF = 40
+
+
+def aud_nal(temporal_id_plus1, slice_types):
+    """the seven bytes of an inserted AUD"""
+    if slice_types == 4:
+        pic_type = 0
+    elif slice_types != 0 and slice_types & 1 == 0:
+        pic_type = 1
+    else:
+        pic_type = 2
+    return bytes([0, 0, 0, 1, 0x46, temporal_id_plus1 & 7, (pic_type << 5) | 0x10])
+
+
+def clip(n_aus, first_au, au_count):
+    if first_au >= n_aus:
+        return 0, 0
+    return first_au, min(au_count, n_aus - first_au)
+
+
+def tables_tile(index, au, nal_au):
+    """do d_au / d_nal_au tile the batch?"""
+    n, m = len(index), len(au)
+    f, c = au["first_nal"].astype(np.int64), au["nal_count"].astype(np.int64)
+    if m == 0 or int(f[0]) != 0 or np.any(c < 1) or np.any(f < 0) or np.any(f + c > n):
+        return False
+    if np.any(f[1:] != f[:-1] + c[:-1]) or int(f[-1] + c[-1]) != n:
+        return False
+    end = index["end"].astype(np.uint64)
+    begin = np.concatenate([[0], end[:-1]]).astype(np.uint64)
+    if np.any(au["unit_begin"] != begin[f]) or np.any(au["unit_end"] != end[f + c - 1]):
+        return False
+    fv = au["first_vcl"].astype(np.int64)
+    if np.any((fv != NONE) & (fv >= c)):
+        return False
+    na = nal_au.astype(np.int64)
+    if np.any(na >= m):
+        return False
+    k = np.arange(n)
+    return not np.any((f[na] > k) | (k >= f[na] + c[na]))
+
+
+def empty(n_nals, error=0, aus=0):
+    z = np.zeros(0, dtype=np.uint32)
+    s = dict(nal_count=0, nal_found=n_nals, rbsp_bytes=0, stream_bytes=0, stop_reason=0, error=error, reserved=[0, 0, aus])
+    return np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=NAL_ENTRY), z, z.copy(), np.zeros(0, dtype=ACCESS_UNIT), s
+
+
+def au_insert(stream, index, parsed, au, nal_au, first_au, au_count, flags, out_cap=None, index_cap=None):
+    """-> (out, index_out, nal_src, nal_au_out, au_out, summary).  out_cap None: a plan (no capacity is looked at); index_cap
+    None: no per-NAL table is given.  On an error the outputs are empty."""
+    stream = np.asarray(stream, dtype=np.uint8)
+    n, m = len(index), len(au)
+    if n == 0 or m == 0:
+        return empty(n)
+    if not F.consistent(index, len(stream)) or not tables_tile(index, au, nal_au):
+        return empty(n, E_ARG)
+    a0, cnt = clip(m, first_au, au_count)
+    if cnt == 0:
+        return empty(n)
+    typ, rc = parsed["nal_unit_type"].tolist(), parsed["rc"].tolist()
+    start, end = index["start"].tolist(), index["end"].tolist()
+    rlen, status = index["rbsp_len"].tolist(), index["status"].tolist()
+    # the last NAL of each kind in front of position p, 0 .. n, as number + 1 (0: none)
+    k1 = np.arange(1, n + 1, dtype=np.int64)
+    last = []
+    for t in (32, 33, 34):
+        hit = np.where((parsed["nal_unit_type"] == t) & (parsed["rc"] >= 0), k1, 0)
+        last.append(np.concatenate([[0], np.maximum.accumulate(hit)]).tolist())
+    rsum = np.concatenate([[0], np.cumsum(index["rbsp_len"].astype(np.int64))]).tolist()
+    A_first, A_count, A_vcl = au["first_nal"].tolist(), au["nal_count"].tolist(), au["first_vcl"].tolist()
+    A_begin, A_end, A_flags = au["unit_begin"].tolist(), au["unit_end"].tolist(), au["flags"].tolist()
+    A_tid, A_st = au["temporal_id_plus1"].tolist(), au["slice_types"].tolist()
+    k0, ub0 = A_first[a0], A_begin[a0]
+    kend = A_first[a0 + cnt - 1] + A_count[a0 + cnt - 1]
+
+    segs, cursor = [], ub0                     # the output: verbatim runs and what is inserted between them
+    pos = nals = rbsp = 0                      # bytes, NALs, rbsp_len inserted so far
+    auds = sets = 0
+    ins = []                                   # inserted entries: (j, start, end, rbsp_off, rbsp_len, status, src, au)
+    ex_b, ex_n, ex_r, own = [0] * cnt, [0] * cnt, [0] * cnt, [False] * cnt
+    in_b, in_n, in_r = [0] * cnt, [0] * cnt, [0] * cnt
+    au_out = au[a0:a0 + cnt].copy()
+    for a in range(a0, a0 + cnt):
+        i = a - a0
+        f = A_first[a]
+        p = f + (A_count[a] if A_vcl[a] == NONE else A_vcl[a])
+        has_aud = typ[f] == 35
+        point = end[f] if has_aud else A_begin[a]
+        ex_b[i], ex_n[i], ex_r[i], own[i] = pos, nals, rbsp, has_aud
+        items = []
+        if flags & AUD and not A_flags[a] & A.NO_PICTURE and not has_aud:
+            items.append(None)
+        if (flags & PARAM_SETS and A_flags[a] & A.IRAP) or (flags & PARAM_SETS_FIRST and a == a0):
+            for t in range(3):
+                q = last[t][p] - 1
+                if 0 <= q < f:
+                    items.append(q)
+        if items:
+            segs.append(stream[cursor:point])
+            cursor = point
+            j = f - k0 + nals + (1 if has_aud else 0)
+            o = point - ub0 + pos
+            r = rsum[f] - rsum[k0] + rbsp + (rlen[f] if has_aud else 0)
+            for q in items:
+                if q is None:
+                    lit = aud_nal(A_tid[a], A_st[a])
+                    segs.append(np.frombuffer(lit, dtype=np.uint8))
+                    ins.append((j, o + 4, o + 7, r, 3, 0, NONE, i))
+                    size, rl = 7, 3
+                    auds += 1
+                else:
+                    segs.append(np.frombuffer(b"\x00\x00\x00\x01", dtype=np.uint8))
+                    segs.append(stream[start[q]:end[q]])
+                    size, rl = 4 + end[q] - start[q], rlen[q]
+                    ins.append((j, o + 4, o + size, r, rl, status[q] & ~ST_UNTERMINATED, q, i))
+                    sets += 1
+                    au_out["flags"][i] |= A.PARAM_SETS
+                j, o, r = j + 1, o + size, r + rl
+                in_b[i] += size
+                in_n[i] += 1
+                in_r[i] += rl
+            pos, nals, rbsp = pos + in_b[i], nals + in_n[i], rbsp + in_r[i]
+    segs.append(stream[cursor:A_end[a0 + cnt - 1]])
+    out = np.concatenate(segs)
+    M = kend - k0 + nals
+    total_rbsp = rsum[kend] - rsum[k0] + rbsp
+    s = dict(nal_count=M, nal_found=n, rbsp_bytes=total_rbsp, stream_bytes=len(out), stop_reason=-1 if M else 0, error=0,
+             reserved=[auds, sets, cnt])
+    if (out_cap is not None and len(out) > out_cap) or (out_cap is not None and index_cap is not None and M > index_cap):
+        e = empty(n)
+        return e[:5] + (dict(s, error=E_CAPACITY),)
+
+    ex_b, ex_n, ex_r, own = (np.array(x, dtype=np.int64) for x in (ex_b, ex_n, ex_r, own))
+    in_b, in_n, in_r = (np.array(x, dtype=np.int64) for x in (in_b, in_n, in_r))
+    # the AU table, moved
+    fa = au["first_nal"][a0:a0 + cnt].astype(np.int64)
+    au_out["first_nal"] = fa - k0 + ex_n
+    au_out["unit_begin"] = au["unit_begin"][a0:a0 + cnt].astype(np.int64) - ub0 + ex_b
+    au_out["unit_end"] = au["unit_end"][a0:a0 + cnt].astype(np.int64) - ub0 + ex_b + in_b
+    au_out["nal_count"] = au["nal_count"][a0:a0 + cnt].astype(np.int64) + in_n
+    fv = au["first_vcl"][a0:a0 + cnt].astype(np.int64)
+    au_out["first_vcl"] = np.where(fv == NONE, NONE, fv + in_n)
+    # the NALs of the range: all of an AU move behind what was inserted into it, but an AUD of its own
+    k = np.arange(k0, kend)
+    i = nal_au[k0:kend].astype(np.int64) - a0
+    moved = ~(own[i].astype(bool) & (k == fa[i]))
+    j = k - k0 + ex_n[i] + np.where(moved, in_n[i], 0)
+    shift = ex_b[i] + np.where(moved, in_b[i], 0) - ub0
+    index_out = np.zeros(M, dtype=NAL_ENTRY)
+    nal_src, nal_au_out = np.zeros(M, dtype=np.uint32), np.zeros(M, dtype=np.uint32)
+    src = index[k0:kend]
+    index_out["start"][j] = src["start"].astype(np.int64) + shift
+    index_out["end"][j] = src["end"].astype(np.int64) + shift
+    index_out["rbsp_off"][j] = np.array(rsum[k0:kend], dtype=np.int64) - rsum[k0] + ex_r[i] + np.where(moved, in_r[i], 0)
+    index_out["rbsp_len"][j] = src["rbsp_len"]
+    index_out["status"][j] = src["status"] & ~ST_UNTERMINATED
+    nal_src[j], nal_au_out[j] = k, i
+    if ins:
+        t = np.array(ins, dtype=np.int64)
+        jj = t[:, 0]
+        index_out["start"][jj], index_out["end"][jj], index_out["rbsp_off"][jj] = t[:, 1], t[:, 2], t[:, 3]
+        index_out["rbsp_len"][jj], index_out["status"][jj] = t[:, 4], t[:, 5]
+        nal_src[jj], nal_au_out[jj] = t[:, 6], t[:, 7]
+    if M:
+        index_out["status"][-1] |= ST_UNTERMINATED
+    return out, index_out, nal_src, nal_au_out, au_out, s
+
+
+def gather_records(parsed, compact, nal_src, au_out, nal_au_out):
+    """d_parsed / d_compact of the output: the source records through d_nal_src, a type-35 record for an inserted AUD"""
+    aud = nal_src == NONE
+    g = np.where(aud, 0, nal_src).astype(np.int64)
+    p, c = parsed[g].copy(), compact[g].copy()
+    p[aud] = np.zeros(1, dtype=PARSED)
+    c[aud] = np.zeros(1, dtype=COMPACT)
+    p["rc"][aud], p["nal_unit_type"][aud] = -1, 35
+    p["nal_temporal_id_plus1"][aud] = au_out["temporal_id_plus1"][nal_au_out[aud]] & 7
+    p["struct_off"][aud] = A.NO_SLOT
+    return p, c
+
+
+def rescan_exceptions(stream, index, au, first_au, au_count, out, index_out, nal_src):
+    """the two stated exceptions -> (what a scan of the output finds instead of index_out, or None when it finds index_out; the
+    leading bytes attached to an inserted NAL; whether the scan misses a short last NAL)"""
+    a0, cnt = clip(len(au), first_au, au_count)
+    zero = np.flatnonzero(stream == 0)
+    lead = int(zero[0]) if len(zero) else len(stream)              # bytes in front of the first start code (none of them is 0)
+    want, junk = index_out.copy(), 0
+    if cnt and a0 == 0 and len(index_out) and int(nal_src[0]) != 0 and lead:
+        j = int(np.flatnonzero(nal_src == 0)[0]) - 1               # the last NAL inserted at stream offset 0
+        want["end"][j] += lead
+        want["rbsp_len"][j] += lead
+        want["rbsp_off"][j + 1:] += lead
+        junk = lead
+    short = F.rescan_misses_last(out, index_out)
+    if short:
+        want = want[:-1]
+    return (want if junk or short else None), junk, short
+
+
+# ---- streams ---------------------------------------------------------------------------------------------------------
+
+def nal(type, size=None, layer=0, tid1=1, rc=None, first=0, stype=1, lsb=0, dep=0, sc=3, zeros=0, junk=0):
+    return dict(type=type, size=size, layer=layer, tid1=tid1, rc=(-1 if type >= 35 else 1) if rc is None else rc, first=first, stype=stype,
+                lsb=lsb, dep=dep, sc=sc, zeros=zeros, junk=junk)
+
+
+def build(rng, nals, lead_junk=0, tail=b""):
+    """nals: a list of nal() dicts in stream order -> (stream, index, parsed, compact, au, nal_au): the bytes (payloads without
+    a zero byte, so rbsp_len = the size and the end is where the next unit begins), the index a scan of them gives, the records a
+    parse would give, and the AUs of tests/_au_ref.py over them."""
+    n = len(nals)
+    parts, at = [], 0
+    index, parsed, compact = np.zeros(n, dtype=NAL_ENTRY), np.zeros(n, dtype=PARSED), np.zeros(n, dtype=COMPACT)
+    parsed["struct_off"] = A.NO_SLOT
+    if lead_junk:
+        parts.append(rng.integers(1, 256, size=lead_junk, dtype=np.uint8).tobytes())
+        at += lead_junk
+    roff = 0
+    for k, d in enumerate(nals):
+        gap = b"\x00" * d["zeros"]
+        if d["junk"] and k:                  # junk belongs to the next unit when it follows the 00 00 00 that ended the NAL in front
+            gap += b"\x00\x00\x00" + rng.integers(4, 256, size=d["junk"], dtype=np.uint8).tobytes()
+        gap += b"\x00\x00\x00\x01" if d["sc"] == 4 else b"\x00\x00\x01"
+        size = int(rng.integers(3, 40)) if d["size"] is None else d["size"]
+        pay = rng.integers(1, 256, size=size, dtype=np.uint8)
+        hdr = [(d["type"] << 1) | (d["layer"] >> 5), ((d["layer"] & 31) << 3) | d["tid1"]]
+        pay[:min(size, 2)] = hdr[:min(size, 2)]
+        if size >= 2 and pay[1] == 0:
+            pay[1] = 1
+        parts += [gap, pay.tobytes()]
+        index[k] = (at + len(gap), at + len(gap) + size, roff, size, 0)
+        at += len(gap) + size
+        roff += size
+        parsed[k] = (d["rc"], d["type"], d["layer"], d["tid1"], A.NO_SLOT, 0, 0)
+        compact["first_slice_segment_in_pic_flag"][k] = d["first"]
+        compact["dependent_slice_segment_flag"][k] = d["dep"]
+        compact["slice_type"][k] = d["stype"]
+        compact["slice_pic_order_cnt_lsb"][k] = d["lsb"]
+    if n:
+        index["status"][-1] = ST_UNTERMINATED if not tail else 0
+    stream = np.frombuffer(b"".join(parts) + tail, dtype=np.uint8).copy()
+    au, nal_au, _, _ = A.access_units(index, parsed, compact, None, SPS_OFF)
+    return stream, index, parsed, compact, au, nal_au
+
+
+def random_aus(rng, n_aus, irap_every=6, max_slices=4, p_aud=0.3, p_own_sets=0.25, p_bad_set=0.3, p_layer=0.3, sets_at_start=True,
+               p_gap=0.3, last_without_picture=False, layer_sets=True):
+    """the NALs of n_aus access units: existing AUDs on some, parameter sets inside some, sets with rc < 0, NALs of other layers,
+    3- and 4-byte start codes, zeros and junk between units; the last AU without a picture when asked"""
+    out = []
+
+    opened = [False]                           # the AU in progress has begun: only then may a NAL of another layer stand in it
+
+    def put(type, **kw):
+        if kw.get("layer", 0) and not opened[0]:
+            kw["layer"] = 0
+        opened[0] = True
+        if rng.random() < p_gap:
+            kw["zeros"] = int(rng.integers(0, 4))
+            kw["junk"] = int(rng.integers(0, 5)) if rng.random() < 0.5 else 0
+        out.append(nal(type, sc=int(rng.choice([3, 4])), **kw))
+
+    def sets(always=False):
+        for t in (32, 33, 34):
+            if always or rng.random() < 0.7:
+                put(t, layer=1 if layer_sets and rng.random() < p_layer / 2 else 0, rc=-1 if (not always and rng.random() < p_bad_set) else 1,
+                    size=int(rng.integers(4, 60)))
+    for a in range(n_aus):
+        opened[0] = False
+        if last_without_picture and a == n_aus - 1:
+            if rng.random() < 0.5:
+                put(35)
+            put(39)
+            break
+        irap = a % irap_every == 0 if irap_every else False
+        if rng.random() < p_aud:
+            put(35, size=3)
+        if (a == 0 and sets_at_start) or rng.random() < p_own_sets:
+            sets(always=(a == 0 and sets_at_start and rng.random() < 0.7))
+        if rng.random() < 0.3:
+            put(39)
+        tid1 = 1 if irap else int(rng.integers(1, 4))
+        stypes = [2] if irap else [int(rng.integers(0, 3))]
+        for sl in range(int(rng.integers(1, max_slices + 1))):
+            st = stypes[0] if sl == 0 else (2 if irap else int(rng.integers(0, 3)))
+            put((19 if a % (2 * irap_every) == 0 else 21) if irap else (1 if tid1 == 1 else 0), tid1=tid1, first=1 if sl == 0 else 0, stype=st,
+                lsb=(a * 2) % 256, size=int(rng.integers(3, 120)))
+        if rng.random() < p_layer:
+            put(int(rng.choice([1, 33, 34] if layer_sets else [1, 39])), layer=1, first=1)             # another layer's: the AU in progress
+        if rng.random() < 0.2:
+            put(40, size=int(rng.choice([1, 2, 5])))
+    return out
+
+
+def random_case(rng, n_aus, lead_junk=None, **kw):
+    """-> (stream, index, parsed, compact, au, nal_au) with exactly n_aus access units"""
+    if n_aus == 0:
+        return build(rng, [])
+    nals = random_aus(rng, n_aus, **kw)
+    if lead_junk is None:
+        lead_junk = int(rng.integers(1, 9)) if rng.random() < 0.2 else 0
+    case = build(rng, nals, lead_junk)
+    assert len(case[4]) == n_aus, (len(case[4]), n_aus)
+    return case
+
+
+def tiny_case(n_aus, irap_every=32):
+    """n_aus access units of one 3-byte NAL behind a 3-byte start code each, but AU 0, which begins with a VPS, an SPS and a
+    PPS; every irap_every-th AU is an IDR picture.  Built without a loop, for counts in the hundred thousands."""
+    n = n_aus + 3
+    k = np.arange(n, dtype=np.int64)
+    a = np.maximum(k - 3, 0)
+    irap = a % irap_every == 0
+    typ = np.where(k < 3, 32 + k, np.where(irap, 19, 1))
+    rows = np.zeros((n, 6), dtype=np.uint8)
+    rows[:, 2] = 1
+    rows[:, 3] = typ << 1
+    rows[:, 4] = 1
+    rows[:, 5] = 0x80 | (k & 0x7F)
+    stream = rows.reshape(-1).copy()
+    index = np.zeros(n, dtype=NAL_ENTRY)
+    index["start"], index["end"], index["rbsp_off"], index["rbsp_len"] = 6 * k + 3, 6 * k + 6, 3 * k, 3
+    index["status"][-1] = ST_UNTERMINATED
+    parsed, compact = np.zeros(n, dtype=PARSED), np.zeros(n, dtype=COMPACT)
+    parsed["rc"], parsed["nal_unit_type"], parsed["nal_temporal_id_plus1"], parsed["struct_off"] = 1, typ, 1, A.NO_SLOT
+    compact["first_slice_segment_in_pic_flag"] = k >= 3
+    compact["slice_type"] = np.where(irap, 2, 1)
+    au = np.zeros(n_aus, dtype=ACCESS_UNIT)
+    j = np.arange(n_aus, dtype=np.int64)
+    ir = j % irap_every == 0
+    au["first_nal"] = np.where(j == 0, 0, j + 3)
+    au["unit_begin"] = 6 * au["first_nal"]
+    au["unit_end"] = 6 * (j + 4)
+    au["nal_count"] = np.where(j == 0, 4, 1)
+    au["vcl_count"] = 1
+    au["first_vcl"] = np.where(j == 0, 3, 0)
+    au["nal_unit_type"] = np.where(ir, 19, 1)
+    au["temporal_id_plus1"] = 1
+    au["slice_types"] = np.where(ir, 4, 2)
+    au["flags"] = np.where(ir, A.IRAP | A.IDR | A.CVS_START | A.ANCHOR, A.ANCHOR)
+    au["flags"][0] |= A.PARAM_SETS
+    nal_au = a.astype(np.uint32)
+    return stream, index, parsed, compact, au, nal_au
