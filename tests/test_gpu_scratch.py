@@ -1,13 +1,19 @@
 """The context's device scratch (hbs_capi.hip: one grow-only buffer per kind, carved by the layout functions next to each
 call's arguments): what a context holds after one call of each kind, to the byte; a context whose buffers all grow under it
-answers as a fresh one does; every timed call takes its slot of the timing ring."""
+answers as a fresh one does; every timed call takes its slot of the timing ring.  The five framing and transport calls
+(tests/test_gpu_sequences.py holds them against their reference loops) are in the last two, and their scratch is held by relations
+between readings."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests import _auins_ref as INS
+from tests import _seq_cases as S
+from tests import _tsmux_ref as TSM
 from tests.test_gpu_au import fabricate
 from tests.test_gpu_carved import emit_arena, emit_index, stream_of
+from tests.test_gpu_sequences import step
 
 pytestmark = pytest.mark.gpu
 
@@ -15,6 +21,9 @@ pytestmark = pytest.mark.gpu
 # measured with this module's own cases on the library of commit 9853dbe, the last one whose hbs_capi.hip sized and carved every
 # workspace by hand.  Exact: the sizes are arithmetic on the call's arguments (none of them depends on the device's compute
 # units: the look-back words, the padded tail tile and every workspace are sized by bytes, NALs and tiles alone).
+# hbs_annexb_to_lenpref, hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux and hbs_au_insert came after that commit: there is no
+# independent source for what they hold, and a number read off the code under test pins nothing.  They have no entry here;
+# test_scratch_relations_of_the_framing_calls holds relations between readings instead.
 SCRATCH_BYTES = {
     "scan of 400 KiB into an arena, dense tiles counted ahead": 197876,
     "scan of 70 KiB without an arena": 479104,
@@ -237,6 +246,36 @@ def every_call(ctx, video, n):
     return out
 
 
+def framing_calls(ctx, video, n):
+    """the five framing and transport calls, each planned and run by its convenience wrapper: the first n NALs as records with
+    a sample table and back, n random AUs as transport packets and back, AUDs and parameter sets in front of n // 2 AUs
+    -> {what: bytes}"""
+    out = {}
+    s, entries = first_nals(video, n), video[1][:n]
+    nal_au = (np.arange(n) // 3).astype(np.uint32)
+    rec, rec_entries, so, sm = ctx.annexb_to_lenpref(dev(s), entries, keep=(np.arange(n) % 5 != 0).astype(np.uint8), nal_au=nal_au, n_aus=int(nal_au[-1]) + 1)
+    out["records"], out["records index"], out["samples"], out["records summary"] = rec.cpu().numpy(), rec_entries.view(np.uint8).copy(), so, sm.tobytes()
+    back, so2, sm = ctx.lenpref_to_annexb(rec, so[:-1].copy(), np.diff(so.astype(np.int64)).astype(np.uint64), startcode_bytes=3)
+    out["records back"], out["samples back"], out["back summary"] = back.cpu().numpy(), so2, sm.tobytes()
+    stream, au, pts, dts = TSM.random_case(np.random.default_rng(7300 + n), n, TSM.params(), max_es=300)
+    ts, au_packet, sm = ctx.ts_mux(dev(stream), au, pts, dts, packet_bytes=192, flags=TSM.PCR | TSM.PSI_AT_IRAP)
+    out["packets"], out["au_packet"], out["mux summary"] = ts.cpu().numpy(), au_packet, sm.tobytes()
+    es, pes, sm = ctx.ts_demux(ts, 0x100, 192)
+    out["demuxed"], out["pes"], out["demux summary"] = es.cpu().numpy(), pes.view(np.uint8).copy(), sm.tobytes()
+    stream, index, parsed, _, au, nal_au = INS.random_case(np.random.default_rng(7400 + n), n // 2)
+    res = ctx.au_insert(dev(stream), index, parsed, len(index), au, nal_au, flags=INS.AUD | INS.PARAM_SETS | INS.PARAM_SETS_FIRST)
+    for what, t in zip(("inserted", "inserted index", "nal_src", "nal_au_out", "au_out"), res[:5]):
+        out[what] = t.cpu().numpy().view(np.uint8).copy()
+    out["insert summary"] = res[5].tobytes()
+    return out
+
+
+def all_calls(ctx, video, n):
+    out = every_call(ctx, video, n)
+    out.update(framing_calls(ctx, video, n))
+    return out
+
+
 def test_buffers_grow_under_a_live_context(video):
     small, large = 300, 2400
     want = {}
@@ -244,7 +283,7 @@ def test_buffers_grow_under_a_live_context(video):
         fresh = new_ctx()
         fresh.set_count_ahead(2)
         try:
-            want[n] = every_call(fresh, video, n)
+            want[n] = all_calls(fresh, video, n)
         finally:
             fresh.close()
     assert np.array_equal(want[small]["emitted"], first_nals(video, small)), "the way back gives the stream"
@@ -253,7 +292,7 @@ def test_buffers_grow_under_a_live_context(video):
     try:
         held = []
         for run, n in enumerate((small, large, small)):
-            got = every_call(ctx, video, n)
+            got = all_calls(ctx, video, n)
             held.append(ctx.device_bytes())
             print("run", run, "NALs", n, "device_bytes", held[-1])
             assert got.keys() == want[n].keys()
@@ -264,6 +303,35 @@ def test_buffers_grow_under_a_live_context(video):
         ctx.close()
     assert held[1] > held[0], held
     assert held[2] >= held[1], held
+
+
+@pytest.mark.parametrize("call", S.CALLS)
+def test_scratch_relations_of_the_framing_calls(call):
+    """device_bytes() after the five newer calls, as relations between readings (see SCRATCH_BYTES): a plan in front of a run
+    adds nothing to what the run alone holds; a small call, or the same call again, leaves it as it is; a context that only
+    ever sees the small case holds strictly less.  Every call is held against the reference loop on the way."""
+    small, large = S.case(call, "small"), S.case(call, "large")
+    planned, alone, little = new_ctx(), new_ctx(), new_ctx()
+    try:
+        step(planned, large, plan=True)
+        after_plan = planned.device_bytes()
+        step(planned, large)
+        held = planned.device_bytes()
+        step(alone, large)
+        print("device_bytes of", call, ": plan", after_plan, "plan and run", held, "run alone", alone.device_bytes())
+        assert after_plan <= held == alone.device_bytes()
+        step(planned, small)
+        assert planned.device_bytes() == held, "a small call behind a large one"
+        step(planned, large)
+        step(planned, large)
+        assert planned.device_bytes() == held, "the same call again"
+        step(little, small)
+        step(little, small)
+        print("device_bytes of", call, ": the small case alone", little.device_bytes())
+        assert 0 < little.device_bytes() < held
+    finally:
+        for c in (planned, alone, little):
+            c.close()
 
 
 # ---- timing slots -------------------------------------------------------------------------------------------------------------
@@ -292,5 +360,25 @@ def test_every_timed_call_takes_a_slot(video):
         assert ctx.kernel_ms() == ms[0] and ctx.kernel_ms_back(0) == ms[0]
         with pytest.raises(Exception):
             ctx.kernel_ms_back(3)
+        # the five framing and transport calls take a slot each time, a plan and a call without input included: their
+        # launchers record both events around whatever they launch, be it the one-workgroup scan kernel alone
+        history = list(ms)                                   # the last call first
+
+        def timed(c, plan=False):
+            step(ctx, c, plan)
+            now = ctx.kernel_ms()
+            assert now >= 0 and ctx.kernel_ms_back(0) == now, (c, plan, now)
+            for back, m in enumerate(history):               # the earlier calls' values, one slot further back each
+                assert ctx.kernel_ms_back(back + 1) == m, (c, plan, back)
+            with pytest.raises(Exception):
+                ctx.kernel_ms_back(len(history) + 1)
+            history.insert(0, now)
+            return now
+        for call in S.CALLS:
+            assert timed(S.case(call, "small")) > 0, call
+        for call in S.CALLS:
+            timed(S.case(call, "small"), plan=True)
+            timed(S.empty(call))
+        print("framing and transport calls: ms", history[:-3])
     finally:
         ctx.close()
