@@ -489,7 +489,7 @@ hipError_t launch_access_units(const AuArgs& a, hipStream_t st)
 
 hipError_t launch_au_keep(const AuKeepArgs& a, hipStream_t st)
 {
-    hipError_t e = hipMemsetAsync(a.sets, 0, 16, st);
+    hipError_t e = clear_async(a.sets, 16, st);
     if (e != hipSuccess) return e;
     if (a.n_nals) {
         const unsigned g = (unsigned)((a.n_nals + 255) / 256);

@@ -53,8 +53,8 @@ struct hbs_ctx {
     int grid_env, spare_wgs;            /* HBS_GRID_BLOCKS (0: unset); workgroup slots left free for other streams' kernels */
     int exclusive;                      /* hbs_ctx_set_device_exclusive: no other persistent kernel shares the device */
     int variant;                  /* 0 = automatic */
-    int last_variant;             /* the kernel the last hbs_index_extract ran (automatic mode: once read back) */
-    int probe_pending;
+    int last_variant;             /* the kernel the last hbs_index_extract ran (automatic mode: as last read back) */
+    int probe_pending;            /* the last hbs_index_extract chose on the device: hbs_ctx_last_kernel reads the probe back, at every call of it */
     int last_index_only;          /* the last hbs_index_extract had no arena: its sparse kernel is the streaming one (5) */
     int parse_sequential;         /* hbs_ctx_set_sequential_parse */
     int count_ahead;              /* hbs_ctx_set_count_ahead: 0 never, 1 streams from 3 GiB up, 2 always */
@@ -439,7 +439,9 @@ int hbs_ctx_last_kernel(hbs_ctx* c)
     if (!c) return HBS_E_ARG;
     if (c->variant) return (c->variant == 5 && !c->last_index_only) ? 4 : c->variant;
     if (!c->probe_pending) return c->last_variant;
-    /* automatic mode: the choice was made on the device; read the probe's counts back */
+    /* automatic mode: the choice was made on the device; read the probe's counts back.  Every time: a call captured in a HIP graph
+     * runs again at each replay without the host side of hbs_index_extract, so a value kept from the first read-back would be the
+     * kernel of an earlier replay */
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::RunHeader h;
     hipError_t e = hipMemcpyAsync(&h, c->hdr, sizeof(h), hipMemcpyDeviceToHost, c->stream);
@@ -448,7 +450,6 @@ int hbs_ctx_last_kernel(hbs_ctx* c)
     uint64_t chunks = 0, flagged = 0;
     for (int i = 0; i < 64; ++i) { chunks += h.probe_slot[i][0]; flagged += h.probe_slot[i][1]; }
     c->last_variant = hbs::probe_variant((uint32_t)chunks, (uint32_t)flagged, c->last_index_only != 0);
-    c->probe_pending = 0;
     return c->last_variant;
 }
 

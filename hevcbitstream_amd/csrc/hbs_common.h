@@ -174,6 +174,35 @@ __device__ __forceinline__ bool gate_closed(int gate, const RunHeader* __restric
     const int want = gate == kGateIfSparse ? kProbeSparse : gate == kGateIfMid ? kProbeMid : kProbeDense;
     return c != want;
 }
+/* The counters and flags that hbs_emit_annexb, hbs_parse_headers and hbs_au_keep clear in front of their kernels are cleared by
+ * a kernel, not by hipMemsetAsync.  Captured in a HIP graph (stream capture on a side stream), those memsets left other bytes than
+ * zeros at a replay -- a repeating pattern: 80 80 80 80 in the parse's err word, an 8-byte value that grew by 0x500 from replay to
+ * replay over the emit's look-back words and counters -- while the same calls enqueued directly were right and every kernel of the
+ * same graphs ran as captured (tests/test_gpu_graphs.py fails on each of the three with the memsets back).  THE CAUSE IS NOT KNOWN:
+ * nobody traced it into the HIP runtime.  What the failing memsets had in common: value 0; destinations that are interior pointers
+ * of one of the context's grow-only scratch allocations (hipMalloc), 256-byte aligned; sizes of 4, 8 and 16 bytes and of a few KiB
+ * (the emit's), so not small sizes alone.  hbs_index_extract, whose clears were kernels already, always replayed right.  The
+ * hipMemsetAsync calls that remain (DESIGN.md section 8 lists them) are on paths no test replays.
+ * Stores [p, p + bytes) and nothing else.  (A template only so that the kernel can be defined in this header.) */
+template <int kUnused = 0> __global__ void k_clear(uint8_t* __restrict__ p, uint64_t bytes)
+{
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t head = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u;
+    if (head > bytes) head = bytes;
+    const uint64_t whole = (bytes - head) / 16u;
+    uint4* const q = reinterpret_cast<uint4*>(p + head);
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (uint64_t i = tid; i < whole; i += step) q[i] = z;
+    for (uint64_t i = tid; i < head; i += step) p[i] = 0;
+    for (uint64_t i = head + 16u * whole + tid; i < bytes; i += step) p[i] = 0;
+}
+inline hipError_t clear_async(void* p, uint64_t bytes, hipStream_t st)
+{
+    if (!bytes) return hipSuccess;
+    const uint64_t want = (bytes / 16u + 255u) / 256u;
+    k_clear<0><<<dim3((unsigned)(want < 1 ? 1 : want > 1024 ? 1024 : want)), dim3(256), 0, st>>>(static_cast<uint8_t*>(p), bytes);
+    return hipGetLastError();
+}
 #endif
 
 

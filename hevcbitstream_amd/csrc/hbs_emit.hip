@@ -2450,7 +2450,7 @@ hipError_t launch_emit_annexb(const EmitArgs& a, hipStream_t st)
         return hipGetLastError();
     }
     /* one clear: the look-back words and, behind them in the workspace, total / err / ticket / n_items / total_dense / probe */
-    hipError_t e = hipMemsetAsync(a.desc, 0, a.clear_bytes, st);
+    hipError_t e = clear_async(a.desc, a.clear_bytes, st);
     if (e != hipSuccess) return e;
     const unsigned grid = 256 * 16;
     if (emit_takes_tiny_path(a.n, a.rbsp_bytes, a.two_pass, a.tiles)) {

@@ -985,7 +985,7 @@ hipError_t launch_parse_headers(const ParseArgs& a, hipStream_t st)
      * raises div_flag.  Batches of up to 64 NALs are then walked again the reference's way, NAL after NAL with one set of
      * tables (k4_seq, gated on the flag: no host round trip; it returns at once on ordinary streams); larger ones walk
      * only the slices that need it (k4_fix, below). */
-    hipError_t e = hipMemsetAsync(a.div_flag, 0, sizeof(uint32_t), st);
+    hipError_t e = clear_async(a.total, 512, st);                          /* total, err, div_flag share 512 bytes of the workspace: one launch */
     if (e != hipSuccess) return e;
     RpsTables* const seq_tables_ws = reinterpret_cast<RpsTables*>(a.own_rows);
     auto exact_pass = [&]() {
@@ -1007,10 +1007,6 @@ hipError_t launch_parse_headers(const ParseArgs& a, hipStream_t st)
         exact_pass();
         return hipGetLastError();
     }
-    e = hipMemsetAsync(a.err, 0, sizeof(uint32_t), st);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(a.total, 0, sizeof(unsigned long long), st);
-    if (e != hipSuccess) return e;
     if (a.n && a.trace_count) {
         e = hipMemsetAsync(a.trace_count, 0, a.n * sizeof(uint32_t), st);      /* NALs that are not parsed have no trace */
         if (e != hipSuccess) return e;
@@ -1043,7 +1039,7 @@ hipError_t launch_parse_headers(const ParseArgs& a, hipStream_t st)
         c.rbsp = a.rbsp; c.idx = a.index; c.n = a.n; c.parsed = a.parsed; c.structs = a.structs; c.structs_cap = a.structs_cap;
         c.ctx_sps = a.ctx_sps; c.ctx_pps = a.ctx_pps; c.zeros = a.zeros; c.init_sps_slot = a.initial_sps_slot; c.init_pps = a.initial_pps;
         c.deps = a.deps; c.wmask = a.wmask; c.bsum = a.bsum;
-        e = hipMemsetAsync(a.fix_count, 0, 2 * sizeof(uint32_t), st);
+        e = clear_async(a.fix_count, 2 * sizeof(uint32_t), st);
         if (e != hipSuccess) return e;
         const unsigned mblocks = (unsigned)((a.n + kFixBlock - 1) / kFixBlock);
         k4_fix_masks<<<mblocks, kFixBlock, 0, st>>>(a.parsed, a.structs, a.deps, a.n, a.wmask, a.bsum, a.fix_count, a.state_sps_slot_out ? nullptr : a.div_flag);

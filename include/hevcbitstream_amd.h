@@ -105,7 +105,24 @@ typedef struct hbs_ctx hbs_ctx;
  *     (an event between the two streams): the scratch is shared by both.  hbs_index_extract_host uses two private streams
  *     and returns only when they are idle.
  * The legacy single-NAL symbols (find_nal_unit ... write_hevc_nal_unit) share one internal context behind a process-wide
- * lock: safe from any thread, serialised (hbs_legacy.c). */
+ * lock: safe from any thread, serialised (hbs_legacy.c).
+ *
+ * HIP graphs.  These calls only enqueue -- no host wait, no allocation once the scratch has its size, every choice that depends
+ * on the data made on the device -- and may be captured into a HIP graph (hipStreamBeginCapture on the bound stream) after ONE
+ * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
+ *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
+ *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep.
+ * The list is what tests/test_gpu_graphs.py and tests/test_gpu_scan.py replay, no more: hbs_parse_headers_compact,
+ * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
+ * of the calls above were wrong at a replay until one did -- capture them at your own risk.
+ * A replay is the captured call on what the buffers hold then: every argument the host passed (counts, byte sizes, capacities,
+ * flags, params, `initial` records) keeps the value it had at capture, so a graph serves inputs that agree in all of them, and a
+ * capture must not need the scratch to grow.  Timing stays off during a capture (hbs_ctx_enable_timing records events and keeps
+ * host state per call).
+ * The calls that wait for the device, and therefore are never captured: hbs_index_parse*, hbs_index_extract_host, hbs_gather_*,
+ * hbs_trim_part, hbs_read_summary, hbs_ctx_last_kernel, hbs_ctx_last_emit_by_tiles, hbs_ctx_kernel_ms*, hbs_ctx_synchronize
+ * and the synchronous copies (hbs_copy_to_device, hbs_copy_to_host).  After a replay hbs_ctx_last_kernel and
+ * hbs_ctx_last_emit_by_tiles speak of that replay: both read what the device left, at every call of them. */
 int  hbs_ctx_create(hbs_ctx** out, int device);
 void hbs_ctx_destroy(hbs_ctx* ctx);
 /* A new context enqueues on a non-blocking stream of its own.  set_stream

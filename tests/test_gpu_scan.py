@@ -459,7 +459,13 @@ def test_last_kernel_reports_what_ran_without_an_arena():
 def test_calls_capture_into_a_hip_graph(orc):
     """hbs_index_extract only enqueues (no allocation after a warm-up call of the same size, no host wait, the
     kernel choice made on the device): captured once in a HIP graph, it is replayed on other bytes in the same
-    buffers -- zero-heavy, then sparse again, so a replay takes the other kernel -- and stays exact."""
+    buffers -- with zeros, then sparse again, then zero-heavy, so every replay takes another kernel -- and stays exact.
+    hbs_ctx_last_kernel names the kernel of each replay, the one probe_variant (hbs_common.h) gives for that replay's bytes: no
+    host side of the call runs at a replay, so it reads the probe back each time it is asked.  4 for the sparse bytes (300 start
+    codes in 187 500 chunks of 16 bytes); 2 for the zero-heavy ones (4 bytes in 13 are zero: nearly every chunk ends a pattern
+    00 00 {<= 3}); and 6 for random bytes of which 12 % are zero: a chunk ends such a pattern with probability
+    16 x 0.12^2 x (0.12 + 0.88 x 3 / 255) = 0.03, one chunk in 33, which since round 6 lies between "one in 44" (kDenseOneIn) and
+    "two in 13" (kMidTwoIn) and belongs to the 24-row geometry."""
     import torch
     import hevcbitstream_amd as hbs
     from tests._orc import NAL_ENTRY
@@ -468,15 +474,16 @@ def test_calls_capture_into_a_hip_graph(orc):
     n = 3_000_000
     rng = np.random.RandomState(91)
 
-    def make(zero_heavy):
+    def make(zeros):
         s = rng.randint(1, 256, size=n).astype(np.uint8)
-        if zero_heavy:
+        if zeros:
             s[rng.rand(n) < 0.12] = 0
         for p in rng.randint(0, n - 8, size=300):
             s[p:p + 4] = (0, 0, 1, 0x42)
         return s
 
     first, second = make(False), make(True)
+    dense = ALPHA[rng.randint(0, len(ALPHA), size=n)]
     d_stream = torch.from_numpy(first).cuda()
     index, rbsp, summary, cap = ctx.alloc_outputs(n)
     side = torch.cuda.Stream()
@@ -486,10 +493,11 @@ def test_calls_capture_into_a_hip_graph(orc):
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=side):
             ctx.index_extract_async(d_stream, index, cap, rbsp, summary)
-    for data in (second, first):
+    for data, kernel in ((second, 6), (first, 4), (dense, 2), (first, 4), (second, 6)):
         d_stream.copy_(torch.from_numpy(data))
         g.replay()
         torch.cuda.synchronize()
+        assert ctx.last_kernel() == kernel, (ctx.last_kernel(), kernel)
         want_idx, want_arena, why = orc.index_extract(data)
         sm = np.frombuffer(summary.cpu().numpy().tobytes(), dtype=SUMMARY)[0]
         assert int(sm["error"]) == 0 and int(sm["nal_count"]) == len(want_idx) and int(sm["stop_reason"]) == why
@@ -555,6 +563,51 @@ def test_count_ahead_replayed_from_a_hip_graph(orc):
         tot = int(want_idx["rbsp_off"][-1] + want_idx["rbsp_len"][-1]) if len(want_idx) else 0
         assert np.array_equal(rbsp[:tot].cpu().numpy(), want_arena[:tot]), k
     ctx.close()
+
+
+def test_the_contexts_own_stream(orc):
+    """a caller from C gets a non-blocking stream of the context's own (every Python method rebinds to torch's current stream
+    first): hbs_ctx_get_stream, hbs_ctx_set_stream and hbs_ctx_use_own_stream say which stream is bound, and a scan and an emit
+    enqueued through the library itself on the own stream, waited for with hbs_ctx_synchronize, are the oracle's"""
+    import ctypes as C
+    import torch
+    import hevcbitstream_amd as hbs
+    from tests._orc import NAL_ENTRY
+    from hevcbitstream_amd.api import SUMMARY
+    lib = hbs.load_library()
+    h = C.c_void_p()
+    assert lib.hbs_ctx_create(C.byref(h), 0) == 0            # as a caller from C has it: never bound to torch's stream
+    try:
+        own = lib.hbs_ctx_get_stream(h)
+        assert own                                           # non-null: not the HIP null stream
+        side = torch.cuda.Stream()
+        assert side.cuda_stream and side.cuda_stream != own
+        assert lib.hbs_ctx_set_stream(h, C.c_void_p(side.cuda_stream)) == 0
+        assert lib.hbs_ctx_get_stream(h) == side.cuda_stream
+        assert lib.hbs_ctx_use_own_stream(h) == 0
+        assert lib.hbs_ctx_get_stream(h) == own
+        stream, want_idx, want_arena = orc.gen_stream(0x77, 300, 1)
+        n, cap = len(stream), len(want_idx) + 8
+        d_stream = torch.from_numpy(stream).cuda()
+        index = torch.zeros(cap * 32, dtype=torch.uint8, device="cuda")
+        rbsp = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
+        out = torch.zeros(n + 4096, dtype=torch.uint8, device="cuda")
+        summary, esum = (torch.zeros(SUMMARY.itemsize, dtype=torch.uint8, device="cuda") for _ in range(2))
+        torch.cuda.synchronize()                             # the inputs are there before the own stream reads them
+        p = lambda x: C.c_void_p(x.data_ptr())               # noqa: E731
+        assert lib.hbs_index_extract(h, p(d_stream), n, p(index), cap, p(rbsp), rbsp.numel(), p(summary)) == 0
+        assert lib.hbs_emit_annexb(h, p(rbsp), len(want_arena), p(index), len(want_idx), 0, p(out), n, None, p(esum)) == 0
+        assert lib.hbs_ctx_get_stream(h) == own
+        assert lib.hbs_ctx_synchronize(h) == 0
+        sm, es = (np.frombuffer(x.cpu().numpy().tobytes(), dtype=SUMMARY)[0] for x in (summary, esum))
+        assert int(sm["error"]) == 0 and int(sm["nal_count"]) == len(want_idx) and int(sm["rbsp_bytes"]) == len(want_arena)
+        assert np.array_equal(index[: len(want_idx) * 32].cpu().numpy().view(NAL_ENTRY), want_idx)
+        assert np.array_equal(rbsp[: len(want_arena)].cpu().numpy(), want_arena)
+        assert int(es["error"]) == 0 and int(es["stream_bytes"]) == n
+        assert np.array_equal(out[:n].cpu().numpy(), orc.emit_annexb(want_arena, want_idx))
+        assert np.array_equal(out[:n].cpu().numpy(), stream)
+    finally:
+        lib.hbs_ctx_destroy(h)
 
 
 def test_timing_ring_keeps_the_last_calls(ctx, orc):
