@@ -14,7 +14,9 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   TS_F_PTS, TS_F_DTS, TS_F_RANDOM_ACCESS, TS_F_DISCONTINUITY, TS_F_DATA_ALIGNED, TS_NO_TIME,
                   STREAM_TYPE_HEVC, ts_packet, ts_find_pid,
                   TS_MUX_PARAMS, TSMUX_PCR, TSMUX_PSI_AT_IRAP, TSMUX_NO_PSI, ts_mux_params, ts_mux_psi, ts_mux_au_packets,
-                  AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST, aud_nal)
+                  AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST, aud_nal,
+                  RTP_PARAMS, RTP_PACKET, RTP_OPEN_END, RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER,
+                  rtp_params, rtp_nal_packets, rtp_packet, rtp_packet_offsets)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
            "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
@@ -25,4 +27,6 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "TS_F_PTS", "TS_F_DTS", "TS_F_RANDOM_ACCESS", "TS_F_DISCONTINUITY", "TS_F_DATA_ALIGNED", "TS_NO_TIME",
            "STREAM_TYPE_HEVC", "ts_packet", "ts_find_pid",
            "TS_MUX_PARAMS", "TSMUX_PCR", "TSMUX_PSI_AT_IRAP", "TSMUX_NO_PSI", "ts_mux_params", "ts_mux_psi", "ts_mux_au_packets",
-           "AUINS_AUD", "AUINS_PARAM_SETS", "AUINS_PARAM_SETS_FIRST", "aud_nal"]
+           "AUINS_AUD", "AUINS_PARAM_SETS", "AUINS_PARAM_SETS_FIRST", "aud_nal",
+           "RTP_PARAMS", "RTP_PACKET", "RTP_OPEN_END", "RTP_SINGLE", "RTP_FU", "RTP_AP", "RTP_OTHER",
+           "rtp_params", "rtp_nal_packets", "rtp_packet", "rtp_packet_offsets"]

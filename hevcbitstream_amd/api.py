@@ -43,6 +43,14 @@ TS_MUX_PARAMS = np.dtype([("packet_bytes", "<i4"), ("pid", "<i4"), ("pmt_pid", "
                           ("transport_stream_id", "<i4"), ("flags", "<u4"), ("cc_es", "<u4"), ("cc_pat", "<u4"), ("cc_pmt", "<u4"),
                           ("reserved", "<u4"), ("pcr_lead", "<u8")])
 TSMUX_PCR, TSMUX_PSI_AT_IRAP, TSMUX_NO_PSI = 1, 2, 4
+# layout of hbs_rtp_params / hbs_rtp_packet, the flags of hbs_rtp_pack and the packet kinds of hbs_rtp_packet_host
+RTP_PARAMS = np.dtype([("max_payload", "<i4"), ("payload_type", "<i4"), ("framing", "<i4"), ("flags", "<u4"), ("ssrc", "<u4"),
+                       ("seq", "<u4"), ("ts_base", "<u4"), ("ts_step", "<u4")])
+RTP_PACKET = np.dtype([("payload_off", "<u8"), ("payload_len", "<u8"), ("nal_off", "<u8"), ("nal_len", "<u8"), ("kind", "<i4"),
+                       ("nal_type", "<i4"), ("marker", "<u4"), ("payload_type", "<u4"), ("seq", "<u4"), ("timestamp", "<u4"),
+                       ("ssrc", "<u4"), ("fu_start", "<u4"), ("fu_end", "<u4"), ("nal_header", "u1", (2,)), ("reserved", "u1", (2,))])
+RTP_OPEN_END = 1
+RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER = 0, 1, 2, 3
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -73,7 +81,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb",
            "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
-           "hbs_au_insert", "hbs_aud_nal_host"]
+           "hbs_au_insert", "hbs_aud_nal_host",
+           "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -219,6 +228,11 @@ def load_library():
                                   C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                   C.c_void_p, C.c_void_p]
     lib.hbs_aud_nal_host.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
+    lib.hbs_rtp_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hbs_rtp_nal_packets_host.argtypes = [C.c_uint64, C.c_int]
+    lib.hbs_rtp_nal_packets_host.restype = C.c_uint64
+    lib.hbs_rtp_packet_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
     _lib = lib
     return lib
 
@@ -278,6 +292,41 @@ def aud_nal(temporal_id_plus1, slice_types):
     if rc != 0:
         raise HbsError("hbs_aud_nal_host failed: %d" % rc)
     return out.tobytes()
+
+
+def rtp_params(max_payload=1188, payload_type=96, framing=0, flags=0, ssrc=0, seq=0, ts_base=0, ts_step=0):
+    """an hbs_rtp_params record (ndarray[RTP_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=RTP_PARAMS)
+    p[0] = (max_payload, payload_type, framing, flags, ssrc, seq, ts_base, ts_step)
+    return p
+
+
+def rtp_nal_packets(nal_bytes, max_payload):
+    """hbs_rtp_nal_packets_host: the RTP packets of a NAL of nal_bytes bytes (0: below 2 bytes, or a max_payload out of range).
+    No GPU involved."""
+    return int(load_library().hbs_rtp_nal_packets_host(int(nal_bytes), int(max_payload)))
+
+
+def rtp_packet(packet):
+    """hbs_rtp_packet_host: one RTP packet (bytes or a uint8 array, without a length field, host memory) as a receiver reads it
+    -> an RTP_PACKET record.  No GPU involved."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(packet), dtype=np.uint8) if isinstance(packet, (bytes, bytearray)) else packet, dtype=np.uint8)
+    out = np.zeros(1, dtype=RTP_PACKET)
+    rc = load_library().hbs_rtp_packet_host(a.ctypes.data if len(a) else None, len(a), out.ctypes.data)
+    if rc != 0:
+        raise HbsError("hbs_rtp_packet_host failed: %d" % rc)
+    return out[0]
+
+
+def rtp_packet_offsets(nal_off, nal_packet, max_payload, framing=0):
+    """the output offset of every packet of an hbs_rtp_pack call, and the total behind them (packets + 1 entries), from the two
+    per-NAL tables: all packets of a NAL but its last take framing + 12 + max_payload bytes"""
+    nal_off, nal_packet = np.asarray(nal_off, dtype=np.uint64), np.asarray(nal_packet, dtype=np.uint64)
+    count = np.diff(nal_packet).astype(np.int64)
+    first = np.repeat(nal_packet[:-1], count)
+    within = np.arange(int(nal_packet[-1]), dtype=np.uint64) - first
+    off = np.repeat(nal_off[:-1], count) + within * np.uint64(int(framing) + 12 + int(max_payload))
+    return np.concatenate([off, nal_off[-1:]]).astype(np.uint64)
 
 
 class Context:
@@ -942,6 +991,59 @@ class Context:
         if int(s["error"]) != 0:
             raise HbsError("hbs_ts_mux: error %d" % int(s["error"]))
         return out[:need], au_packet.cpu().numpy().view(np.uint32).copy(), s
+
+    # ---- RTP ------------------------------------------------------------------------------
+
+    def rtp_pack_async(self, stream, stream_bytes, index, n_nals, nal_au, n_aus, pts, params, out, nal_off, nal_packet, summary, out_cap=None):
+        """Enqueue hbs_rtp_pack on the current torch stream.  stream / index / nal_au / pts / out / nal_off / nal_packet / summary
+        are device tensors (nal_au, pts, nal_off, nal_packet may be None; out None: plan only); params is an
+        ndarray[RTP_PARAMS] of one in host memory.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=RTP_PARAMS)
+        return self.lib.hbs_rtp_pack(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None, int(n_nals),
+                                     p(nal_au), int(n_aus), p(pts), params.ctypes.data_as(C.c_void_p) if params is not None else None,
+                                     p(out), int(out_cap), p(nal_off), p(nal_packet), p(summary))
+
+    def rtp_pack(self, stream, index, n_nals=None, nal_au=None, n_aus=None, pts=None, stream_bytes=None, **params):
+        """Convenience: the NALs `index` (ndarray[NAL_ENTRY] or a device uint8 tensor of the records) of `stream` (device uint8
+        tensor) as RTP packets.  nal_au: None or one uint32 per NAL; pts: None or one uint64 per AU; host arrays or device
+        tensors; params: the keywords of rtp_params.  Plans first, allocates the exact output, runs.  Returns (out device
+        tensor, packet_off ndarray[uint64] of packets + 1: where every packet begins and the total, summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x, dtype):
+            if isinstance(x, np.ndarray):
+                b = np.ascontiguousarray(x, dtype=dtype).view(np.uint8).reshape(-1)
+                return t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
+            return x
+        n = n_nals if n_nals is not None else (len(index) if isinstance(index, np.ndarray) else index.numel() * index.element_size() // NAL_ENTRY.itemsize)
+        if n_aus is None:
+            n_aus = 0 if pts is None else (len(pts) if isinstance(pts, np.ndarray) else pts.numel() * pts.element_size() // 8)
+            if pts is None and nal_au is not None:
+                n_aus = 1 << 32
+        index, nal_au, pts = dv(index, NAL_ENTRY), dv(nal_au, np.uint32), dv(pts, np.uint64)
+        prm = rtp_params(**params)
+        nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        args = (stream, nbytes, index, n, nal_au, n_aus, pts, prm)
+        self._check(self.rtp_pack_async(*args, None, None, None, summary), "hbs_rtp_pack")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_rtp_pack: error %d (NAL %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        need = int(s["stream_bytes"])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        nal_off, nal_packet = (t.empty((n + 1) * 8, dtype=t.uint8, device=dev) for _ in range(2))
+        self._check(self.rtp_pack_async(*args, out, nal_off, nal_packet, summary, out_cap=need), "hbs_rtp_pack")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_rtp_pack: error %d" % int(s["error"]))
+        tabs = [x.cpu().numpy().view(np.uint64) for x in (nal_off, nal_packet)]
+        return out[:need], rtp_packet_offsets(tabs[0], tabs[1], int(prm["max_payload"][0]), int(prm["framing"][0])), s
 
     # ---- access units -----------------------------------------------------------------
 

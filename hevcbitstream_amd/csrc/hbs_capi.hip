@@ -23,6 +23,7 @@
 #include "hbs_ts.h"
 #include "hbs_tsmux.h"
 #include "hbs_auins.h"
+#include "hbs_rtp.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -39,8 +40,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kLws    the scratch of hbs_annexb_to_lenpref and hbs_lenpref_to_annexb
  * kTws    hbs_ts_demux's scratch
  * kMws    hbs_ts_mux's scratch
- * kIws    hbs_au_insert's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kBufs };
+ * kIws    hbs_au_insert's scratch
+ * kRws    hbs_rtp_pack's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -726,6 +728,41 @@ int hbs_ts_mux(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_ts_mux(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_ts_mux");
+}
+
+int hbs_rtp_pack(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                 const hbs_nal_entry* d_index, uint64_t n_nals, const uint32_t* d_nal_au, uint64_t n_aus, const uint64_t* d_pts,
+                 const hbs_rtp_params* params, uint8_t* d_out, uint64_t out_cap,
+                 uint64_t* d_nal_off, uint64_t* d_nal_packet, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_rtp_params) == 32 && sizeof(hbs_rtp_packet) == 72 && sizeof(hbs_nal_entry) == 32, "hbs_rtp_params / hbs_rtp_packet layout");
+    if (!c || !d_summary || !hbs::rtp_params_ok(params) || n_nals > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_nals && (!d_index || !d_stream)) return HBS_E_ARG;
+    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_index, 7) ||
+        misaligned(d_pts, 7) || misaligned(d_nal_off, 7) || misaligned(d_nal_packet, 7) || misaligned(d_nal_au, 3)) {
+        snprintf(c->err, sizeof(c->err), "stream/output/summary pointers must be 16-byte aligned, index, times and the two tables 8-byte, AU numbers 4-byte");
+        return HBS_E_ARG;
+    }
+    if (d_out && out_cap > hbs::kRtpOutCapMax) {
+        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::RtpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_stream; a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals;
+    a.nal_au = d_nal_au; a.n_aus = n_aus; a.pts = reinterpret_cast<const unsigned long long*>(d_pts);
+    a.q = hbs::rtp_rule(params); a.flags = params->flags; a.ts_base = params->ts_base; a.ts_step = params->ts_step;
+    a.out = d_out; a.out_cap = out_cap; a.summary = d_summary;
+    if (d_out) { a.nal_off = reinterpret_cast<unsigned long long*>(d_nal_off); a.nal_packet = reinterpret_cast<unsigned long long*>(d_nal_packet); }
+    /* the copy's grid: the tiles out_cap has room for, and no more than the call can make */
+    const uint64_t most = hbs::rtp_output_bound(n_nals, stream_bytes, a.q);
+    a.tiles = d_out && n_nals ? hbs::rtp_tiles(out_cap < most ? out_cap : most) : 0;
+    const int rc = carve(c, c->buf[kRws], "hipMalloc(RTP scratch)", [&](hbs::Carver& w) { hbs::lay_rtp(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_rtp_pack(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_pack");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,

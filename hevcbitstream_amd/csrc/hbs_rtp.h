@@ -1,0 +1,237 @@
+/*
+ * hbs_rtp.h -- hbs_rtp_pack (include/hevcbitstream_amd.h): the rule that turns one NAL unit into RFC 7798 RTP packets, as
+ * host/device inline functions -- rtp_nal lays a NAL out (single NAL unit packet or fragmentation units, packets, output
+ * bytes), rtp_packet_bytes gives packet p's length and rtp_head_byte every byte in front of its NAL bytes; the kernels of
+ * hbs_rtp.hip, the two host entry points and the tests all run them -- the receiver's view of one packet (rtp_packet_host),
+ * and the host-visible launcher.  Everything above the launcher compiles with plain g++.
+ */
+#ifndef HBS_RTP_H
+#define HBS_RTP_H
+
+#include "hbs_common.h"
+
+namespace hbs {
+
+constexpr int kRtpPlanLanes = 256;                  /* plan: a lane a NAL, 256 NALs a workgroup                     */
+constexpr int kRtpNalsPerBlock = kRtpPlanLanes;
+constexpr uint64_t kRtpTileBytes = 64 * 1024;       /* copy: output bytes of one workgroup                          */
+constexpr uint64_t kRtpOutCapMax = 1ull << 46;      /* out_cap sizes the copy's grid and scratch                    */
+constexpr uint32_t kRtpHeader = 12;                 /* the fixed RTP header                                         */
+constexpr uint32_t kRtpFuHeader = 3;                /* PayloadHdr (2) + FU header (1)                               */
+constexpr int kRtpMinPayload = 4, kRtpMaxPayload = 65535 - 12;
+constexpr uint64_t kRtpTimeLimit = 1ull << 33;      /* a d_pts value must be below this                             */
+
+/* what of hbs_rtp_params the rule reads */
+struct RtpRule {
+    uint32_t mp;                                     /* max_payload                                                  */
+    uint32_t fr;                                     /* framing: 0 or 2                                              */
+    uint32_t pt, ssrc, seq;
+};
+
+HBS_HD bool rtp_max_payload_ok(int64_t mp) { return mp >= kRtpMinPayload && mp <= kRtpMaxPayload; }
+
+/* NAL of L >= 2 bytes */
+struct RtpNal {
+    bool fu;                                         /* L > mp                                                       */
+    uint64_t packets;                                /* 1, or n = ceil((L - 2) / (mp - 3)) >= 2                      */
+    uint64_t out_bytes;                              /* framing, headers and NAL bytes of all its packets            */
+};
+
+HBS_HD RtpNal rtp_nal(uint64_t L, uint32_t mp, uint32_t fr)
+{
+    RtpNal r;
+    r.fu = L > mp;
+    if (!r.fu) { r.packets = 1; r.out_bytes = fr + kRtpHeader + L; return r; }
+    const uint64_t F = mp - 3u, B = L - 2u;
+    r.packets = (B + F - 1u) / F;
+    r.out_bytes = r.packets * (uint64_t)(fr + kRtpHeader + kRtpFuHeader) + B;
+    return r;
+}
+
+/* every packet of an FU NAL but its last takes this many output bytes */
+HBS_HD uint32_t rtp_full_packet_bytes(const RtpRule& q) { return q.fr + kRtpHeader + q.mp; }
+
+/* output bytes of packet p of the NAL (p < packets), the length field included */
+HBS_HD uint64_t rtp_packet_bytes(const RtpRule& q, uint64_t L, const RtpNal& u, uint64_t p)
+{
+    if (!u.fu) return u.out_bytes;
+    if (p + 1 < u.packets) return rtp_full_packet_bytes(q);
+    return (uint64_t)(q.fr + kRtpHeader + kRtpFuHeader) + (L - 2u) - p * (uint64_t)(q.mp - 3u);
+}
+
+/* bytes in front of the NAL bytes a packet carries */
+HBS_HD uint32_t rtp_head_bytes(const RtpRule& q, bool fu) { return q.fr + kRtpHeader + (fu ? kRtpFuHeader : 0u); }
+
+/* where in the NAL the bytes of packet p begin */
+HBS_HD uint64_t rtp_packet_src(const RtpRule& q, bool fu, uint64_t p) { return fu ? 2u + p * (uint64_t)(q.mp - 3u) : 0u; }
+
+/* byte i (i < rtp_head_bytes) of a packet of plen bytes (length field included): number j of the call, timestamp ts;
+ * last: the NAL's last packet; marker: the NAL ends its access unit; h0, h1: the NAL's header (read for an FU only) */
+HBS_HD uint32_t rtp_head_byte(const RtpRule& q, bool fu, bool first, bool last, bool marker, uint64_t plen, uint64_t j, uint32_t ts,
+                              uint32_t h0, uint32_t h1, uint32_t i)
+{
+    if (i < q.fr) {
+        const uint32_t len = (uint32_t)(plen - q.fr);
+        return (i == 0 ? len >> 8 : len) & 0xFFu;
+    }
+    i -= q.fr;
+    if (i < kRtpHeader) {
+        const uint32_t s = (q.seq + (uint32_t)j) & 0xFFFFu;
+        switch (i) {
+        case 0: return 0x80u;
+        case 1: return ((last && marker) ? 0x80u : 0u) | q.pt;
+        case 2: return s >> 8;
+        case 3: return s & 0xFFu;
+        case 4: case 5: case 6: case 7: return (ts >> (8u * (7u - i))) & 0xFFu;
+        default: return (q.ssrc >> (8u * (11u - i))) & 0xFFu;
+        }
+    }
+    i -= kRtpHeader;                                                 /* an FU's three bytes */
+    if (i == 0) return (h0 & 0x81u) | 0x62u;
+    if (i == 1) return h1;
+    return (first ? 0x80u : 0u) | (last ? 0x40u : 0u) | ((h0 >> 1) & 63u);
+}
+
+/* ---- host side: parameters, one NAL, one packet as a receiver reads it ------------------------------------------------- */
+
+inline bool rtp_params_ok(const hbs_rtp_params* p)
+{
+    if (!p || !rtp_max_payload_ok(p->max_payload)) return false;
+    if (p->payload_type < 0 || p->payload_type > 127 || (p->framing != 0 && p->framing != 2)) return false;
+    return (p->flags & ~HBS_RTP_OPEN_END) == 0u && p->seq <= 0xFFFFu;
+}
+
+inline RtpRule rtp_rule(const hbs_rtp_params* p)
+{
+    RtpRule q;
+    q.mp = (uint32_t)p->max_payload; q.fr = (uint32_t)p->framing; q.pt = (uint32_t)p->payload_type; q.ssrc = p->ssrc; q.seq = p->seq;
+    return q;
+}
+
+inline uint64_t rtp_nal_packets_host(uint64_t nal_bytes, int max_payload)
+{
+    if (nal_bytes < 2 || !rtp_max_payload_ok(max_payload)) return 0;
+    return rtp_nal(nal_bytes, (uint32_t)max_payload, 0).packets;
+}
+
+/* packet p of the NAL nal[0, L) into out[0, rtp_packet_bytes): the rule run byte by byte */
+inline void rtp_write_packet_host(const RtpRule& q, const uint8_t* nal, uint64_t L, uint64_t p, bool marker, uint64_t j, uint32_t ts, uint8_t* out)
+{
+    const RtpNal u = rtp_nal(L, q.mp, q.fr);
+    const uint64_t plen = rtp_packet_bytes(q, L, u, p);
+    const uint32_t head = rtp_head_bytes(q, u.fu);
+    const uint64_t src = rtp_packet_src(q, u.fu, p);
+    for (uint32_t i = 0; i < head; ++i)
+        out[i] = (uint8_t)rtp_head_byte(q, u.fu, p == 0, p + 1 == u.packets, marker, plen, j, ts, nal[0], nal[1], i);
+    for (uint64_t i = head; i < plen; ++i) out[i] = nal[src + (i - head)];
+}
+
+/* one RTP packet pkt[0, n) (no length field) as a receiver reads it: RFC 3550 5.1 / 5.3.1, RFC 7798 4.4 */
+inline int rtp_packet_host(const uint8_t* pkt, uint64_t n, hbs_rtp_packet* out)
+{
+    if (!pkt || !out || n < kRtpHeader || (pkt[0] >> 6) != 2u) return HBS_E_ARG;
+    uint64_t head = kRtpHeader + 4u * (pkt[0] & 15u);                /* the CSRC entries */
+    if (head > n) return HBS_E_ARG;
+    if (pkt[0] & 0x10u) {                                            /* a header extension: 16 bits of profile, 16 of length in words */
+        if (n - head < 4u) return HBS_E_ARG;
+        const uint64_t words = ((uint64_t)pkt[head + 2] << 8) | pkt[head + 3];
+        head += 4u;
+        if (n - head < 4u * words) return HBS_E_ARG;
+        head += 4u * words;
+    }
+    uint64_t pad = 0;
+    if (pkt[0] & 0x20u) {                                            /* padding: its last byte counts it, itself included */
+        pad = pkt[n - 1];
+        if (pad == 0 || pad > n - head) return HBS_E_ARG;
+    }
+    hbs_rtp_packet r;
+    r.payload_off = head; r.payload_len = n - head - pad;
+    r.marker = pkt[1] >> 7; r.payload_type = pkt[1] & 127u;
+    r.seq = ((uint32_t)pkt[2] << 8) | pkt[3];
+    r.timestamp = ((uint32_t)pkt[4] << 24) | ((uint32_t)pkt[5] << 16) | ((uint32_t)pkt[6] << 8) | pkt[7];
+    r.ssrc = ((uint32_t)pkt[8] << 24) | ((uint32_t)pkt[9] << 16) | ((uint32_t)pkt[10] << 8) | pkt[11];
+    r.kind = HBS_RTP_OTHER; r.nal_type = -1; r.fu_start = r.fu_end = 0;
+    r.nal_off = r.payload_off; r.nal_len = r.payload_len;
+    r.nal_header[0] = r.nal_header[1] = 0; r.reserved[0] = r.reserved[1] = 0;
+    if (r.payload_len >= 2) {
+        const uint8_t* p = pkt + head;
+        const uint32_t t = (p[0] >> 1) & 63u;
+        r.nal_type = (int32_t)t; r.nal_header[0] = p[0]; r.nal_header[1] = p[1];
+        if (t < 48u) {
+            r.kind = HBS_RTP_SINGLE;
+        } else if (t == 48u) {
+            r.kind = HBS_RTP_AP;
+        } else if (t == 49u) {
+            if (r.payload_len < kRtpFuHeader) return HBS_E_ARG;
+            r.kind = HBS_RTP_FU;
+            r.fu_start = p[2] >> 7; r.fu_end = (p[2] >> 6) & 1u;
+            r.nal_type = (int32_t)(p[2] & 63u);
+            r.nal_header[0] = (uint8_t)((p[0] & 0x81u) | ((p[2] & 63u) << 1));
+            r.nal_off = head + kRtpFuHeader; r.nal_len = r.payload_len - kRtpFuHeader;
+        }
+    }
+    *out = r;
+    return 0;
+}
+
+#ifdef __HIPCC__
+} // namespace hbs
+#include <hip/hip_runtime_api.h>
+namespace hbs {
+
+struct RtpArgs {
+    const uint8_t* src; uint64_t n;                   /* the stream                                                   */
+    const hbs_nal_entry* index; uint64_t n_nals;
+    const uint32_t* nal_au; uint64_t n_aus;           /* nal_au NULL: one access unit                                 */
+    const unsigned long long* pts;                    /* nullable                                                     */
+    RtpRule q;
+    uint32_t flags, ts_base, ts_step;
+    uint8_t* out; uint64_t out_cap;                   /* out NULL: plan only                                          */
+    unsigned long long* nal_off;                      /* nullable, n_nals + 1                                         */
+    unsigned long long* nal_packet;                   /* nullable, n_nals + 1                                         */
+    hbs_summary* summary;
+    /* scratch (lay_rtp) */
+    unsigned long long* part;      /* 8 per plan block: output bytes, packets, NAL bytes, FU NALs, 1 + the lowest bad NAL (0: none) */
+    unsigned long long* ctl;       /* 8: error, output bytes, packets                                                               */
+    unsigned long long* rec_out;   /* n_nals + 1: output offset of NAL k's first packet (then the total)                            */
+    unsigned long long* rec_pkt;   /* n_nals + 1: number of NAL k's first packet (then the total)                                   */
+    unsigned long long* rec_src;   /* n_nals: start_k                                                                                */
+    unsigned long long* rec_len;   /* n_nals: L                                                                                      */
+    unsigned long long* rec_tm;    /* n_nals: the timestamp, bit 32: the NAL ends its access unit                                   */
+    unsigned long long* tile_first;/* tiles + 1: the NAL the output tile's first byte lies in                                       */
+    uint64_t tiles;                /* output tiles the copy's grid covers                                                           */
+    hipEvent_t ev_begin, ev_end;
+};
+
+/* the most output bytes a call can make: L + 15 + framing for a single packet, a head of 15 + framing for every mp - 3 bytes
+ * of an FU and one more for its short last packet */
+inline uint64_t rtp_output_bound(uint64_t n_nals, uint64_t stream_bytes, const RtpRule& q)
+{
+    const uint64_t head = q.fr + kRtpHeader + kRtpFuHeader;
+    return stream_bytes + head * (2u * n_nals + stream_bytes / (q.mp - 3u));
+}
+
+inline uint64_t rtp_tiles(uint64_t reach)
+{
+    const uint64_t t = reach / kRtpTileBytes + (reach % kRtpTileBytes ? 1 : 0);
+    return t < 0x7FFFFFFFull ? t : 0x7FFFFFFFull;
+}
+
+inline void lay_rtp(Carver& w, RtpArgs& a)
+{
+    const uint64_t blocks = (a.n_nals + kRtpNalsPerBlock - 1) / kRtpNalsPerBlock;
+    a.part = w.take<unsigned long long>(blocks * 64);
+    a.ctl = w.take<unsigned long long>(64);
+    const uint64_t recs = a.out ? a.n_nals : 0;                      /* (a plan-only call places nothing) */
+    a.rec_out = w.take<unsigned long long>(a.out ? (recs + 1) * 8 : 0);
+    a.rec_pkt = w.take<unsigned long long>(a.out ? (recs + 1) * 8 : 0);
+    a.rec_src = w.take<unsigned long long>(recs * 8);
+    a.rec_len = w.take<unsigned long long>(recs * 8);
+    a.rec_tm = w.take<unsigned long long>(recs * 8);
+    a.tile_first = w.take<unsigned long long>(a.tiles ? (a.tiles + 1) * 8 : 0);
+}
+hipError_t launch_rtp_pack(const RtpArgs& a, hipStream_t st);
+#endif
+
+} // namespace hbs
+#endif

@@ -1,0 +1,376 @@
+/*
+ * hbs_rtp.hip -- hbs_rtp_pack: the NAL units of a stream -> RTP packets by RFC 7798, single NAL unit packets and fragmentation
+ * units, the marker bit on the last packet of an access unit (include/hevcbitstream_amd.h; the packet rule is rtp_nal /
+ * rtp_head_byte, hbs_rtp.h).  The filter's plan shape per NAL, then a copy that needs no per-packet table because all packets
+ * of a NAL but its last have one size.  Five launches, none of which waits for another workgroup:
+ *
+ *   k_rtp_count   one lane a NAL, 256 NALs a workgroup: checks the entry, reads the NAL's first byte, checks the AU number and
+ *                 the time; per workgroup the sums of output bytes, packets, NAL bytes and FU NALs, and 1 + its lowest bad NAL
+ *   k_rtp_scan    one workgroup: exclusive scan of those sums over the workgroups (scan_parts, hbs_plan.h); the totals, the
+ *                 error, the summary.  A plan-only call ends here
+ *   k_rtp_place   the entries once more, now with the offsets: per NAL its output offset, first packet number, source offset,
+ *                 length and timestamp with the marker (scratch), d_nal_off and d_nal_packet
+ *   k_rtp_tiles   one lane per 64 KiB output tile: binary search of the NAL its first byte lies in
+ *   k_rtp_copy    one workgroup per output tile: each lane takes 16-byte output chunks 4 KiB apart and finds the NAL of each
+ *                 (the tile's NALs are staged in LDS; more than 512 are read from memory); the packet of the chunk is a
+ *                 division by the full packet's size.  A chunk that lies wholly inside one packet's NAL bytes is one or two
+ *                 aligned 16-byte non-temporal loads, alignbyte and one aligned 16-byte non-temporal store, four chunks' loads
+ *                 in flight a lane; a chunk that holds length, RTP header or FU header bytes or spans packets or NALs -- two in
+ *                 75 at 1 200-byte packets -- goes to a list in LDS, and behind the batches the workgroup takes the list
+ *                 sixty-four chunks at a time, a lane a byte of four chunks from the rule, sixteen lanes' bytes put together into one aligned
+ *                 16-byte store; the output's last chunk is stored byte-exactly.
+ *
+ * Traffic: the NALs' bytes read once and the output written once; 32 B a NAL of the index read by each plan pass, 40 B a NAL of
+ * scratch written and read, 8 B a tile.
+ */
+#include <hip/hip_runtime.h>
+#include "hbs_rtp.h"
+#include "hbs_plan.h"
+#include "hbs_pieces.h"
+#include "hbs_wave.h"
+
+namespace hbs {
+namespace {
+
+constexpr int kRT = 256;                                              /* lanes of the copy workgroup             */
+constexpr uint32_t kTile = (uint32_t)kRtpTileBytes;
+constexpr int kChunks = (int)(kRtpTileBytes / 16 / kRT);              /* 16-byte output chunks a copy lane takes */
+constexpr int kBatch = 4;                                             /* ... loads of that many issued together  */
+constexpr int kSlowBatch = 4;                                         /* slow chunks a group of sixteen lanes takes together */
+constexpr uint32_t kLdsNals = 512;                                    /* NALs a tile stages in LDS; more: read from memory */
+constexpr unsigned long long kMarker = 1ull << 32;                    /* rec_tm: the NAL ends its access unit    */
+static_assert(kTile / 16 <= 0x1000 && kTile / 14 < (1u << 20), "a slow chunk and its NAL share a word");
+
+struct NalEval {
+    uint64_t start, L;
+    uint32_t ts;
+    bool bad, marker;
+    RtpNal u;
+};
+
+/* entry k: every check of the call that is about NAL k; each thing is checked before it is used */
+__device__ __forceinline__ NalEval eval_nal(const RtpArgs& a, uint64_t k)
+{
+    const hbs_nal_entry* e = a.index + k;
+    const uint64_t start = e->start, end = e->end, prev_end = k ? a.index[k - 1].end : 0;
+    NalEval r;
+    r.start = start; r.L = 0; r.ts = 0;
+    r.bad = start > end || end > a.n || start < prev_end;
+    if (!r.bad) {
+        r.L = end - start;
+        if (r.L < 2) r.bad = true;
+        else if (((a.src[start] >> 1) & 63u) >= 48u) r.bad = true;
+    }
+    uint32_t rel = 0;
+    bool au_ok = true;
+    r.marker = k + 1 == a.n_nals ? !(a.flags & HBS_RTP_OPEN_END) : false;
+    if (a.nal_au) {
+        const uint32_t au = a.nal_au[k], first = a.nal_au[0];
+        if (k) {
+            const uint32_t prev = a.nal_au[k - 1];
+            if (au != prev && (uint64_t)au != (uint64_t)prev + 1) au_ok = false;
+        }
+        rel = au - first;
+        if (au < first || (uint64_t)rel >= a.n_aus) au_ok = false;
+        if (k + 1 < a.n_nals) r.marker = a.nal_au[k + 1] != au;
+    }
+    if (!au_ok) { r.bad = true; rel = 0; }
+    if (a.pts) {
+        const uint64_t t = au_ok ? a.pts[rel] : 0;
+        if (t >= kRtpTimeLimit) r.bad = true;
+        r.ts = a.ts_base + (uint32_t)t;
+    } else {
+        r.ts = a.ts_base + rel * a.ts_step;
+    }
+    r.u = rtp_nal(r.bad ? 2 : r.L, a.q.mp, a.q.fr);
+    return r;
+}
+
+__global__ __launch_bounds__(kRtpPlanLanes) void k_rtp_count(RtpArgs a)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kRtpNalsPerBlock + threadIdx.x;
+    uint64_t v[4] = {0, 0, 0, 0};
+    uint64_t bad = 0;
+    if (k < a.n_nals) {
+        const NalEval x = eval_nal(a, k);
+        if (x.bad) bad = k + 1;
+        else { v[0] = x.u.out_bytes; v[1] = x.u.packets; v[2] = x.L; v[3] = x.u.fu ? 1 : 0; }
+    }
+    bad = block_min_nonzero(bad);
+    uint64_t ex[4], tot[4];
+    block_scan<4, kRtpPlanLanes>(v, ex, tot);
+    if (threadIdx.x == 0) {
+        unsigned long long* p = a.part + (uint64_t)blockIdx.x * 8;
+        p[0] = tot[0]; p[1] = tot[1]; p[2] = tot[2]; p[3] = tot[3]; p[4] = bad;
+    }
+}
+
+__global__ __launch_bounds__(kPlanLanes) void k_rtp_scan(RtpArgs a, uint64_t blocks)
+{
+    uint64_t carry[4];
+    const uint64_t bad = scan_parts<4>(a.part, blocks, carry);
+    if (threadIdx.x == 0) {
+        const uint64_t total = carry[0], packets = carry[1];
+        const int32_t err = bad ? HBS_E_ARG : (a.out && total > a.out_cap) ? HBS_E_CAPACITY : 0;
+        a.ctl[0] = (unsigned long long)(uint32_t)err;
+        a.ctl[1] = total; a.ctl[2] = packets;
+        if (!err && a.out) {
+            a.rec_out[a.n_nals] = total; a.rec_pkt[a.n_nals] = packets;
+            if (a.nal_off) a.nal_off[a.n_nals] = total;
+            if (a.nal_packet) a.nal_packet[a.n_nals] = packets;
+        }
+        hbs_summary s;
+        s.nal_count = packets; s.nal_found = a.n_nals; s.rbsp_bytes = carry[2]; s.stream_bytes = total;
+        s.stop_reason = 0; s.error = err;
+        s.reserved[0] = bad; s.reserved[1] = packets; s.reserved[2] = carry[3];
+        *a.summary = s;
+    }
+}
+
+__global__ __launch_bounds__(kRtpPlanLanes) void k_rtp_place(RtpArgs a)
+{
+    if (a.ctl[0] != 0) return;
+    const uint64_t k = (uint64_t)blockIdx.x * kRtpNalsPerBlock + threadIdx.x;
+    const bool in = k < a.n_nals;
+    uint64_t v[2] = {0, 0};
+    NalEval x;
+    x.start = 0; x.L = 0; x.ts = 0; x.marker = false;
+    if (in) {
+        x = eval_nal(a, k);
+        v[0] = x.u.out_bytes; v[1] = x.u.packets;
+    }
+    uint64_t off[2], tot[2];
+    block_scan<2, kRtpPlanLanes>(v, off, tot);
+    if (!in) return;
+    const unsigned long long* p = a.part + (uint64_t)blockIdx.x * 8;
+    off[0] += p[0]; off[1] += p[1];
+    a.rec_out[k] = off[0]; a.rec_pkt[k] = off[1];
+    a.rec_src[k] = x.start; a.rec_len[k] = x.L;
+    a.rec_tm[k] = (unsigned long long)x.ts | (x.marker ? kMarker : 0ull);
+    if (a.nal_off) a.nal_off[k] = off[0];
+    if (a.nal_packet) a.nal_packet[k] = off[1];
+}
+
+__global__ __launch_bounds__(256) void k_rtp_tiles(RtpArgs a)
+{
+    if (a.ctl[0] != 0) return;
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t total = a.ctl[1];
+    const uint64_t used = (total + kTile - 1) / kTile;
+    if (t > used || t > a.tiles || a.n_nals == 0) return;
+    if (t == used) { a.tile_first[t] = a.n_nals - 1; return; }
+    const uint64_t o = t * kTile;
+    uint64_t lo = 0, hi = a.n_nals - 1;               /* the last NAL whose packets begin at or before o */
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (a.rec_out[mid] <= o) lo = mid; else hi = mid - 1;
+    }
+    a.tile_first[t] = lo;
+}
+
+/* bytes [sh, sh + 16) of the 32 bytes a:b */
+__device__ __forceinline__ u32x4 realign(u32x4 a, u32x4 b, uint32_t sh)
+{
+    const uint32_t q = sh >> 2, r = sh & 3u;
+    uint32_t x0, x1, x2, x3, x4;
+    if (q == 0)      { x0 = a.x; x1 = a.y; x2 = a.z; x3 = a.w; x4 = b.x; }
+    else if (q == 1) { x0 = a.y; x1 = a.z; x2 = a.w; x3 = b.x; x4 = b.y; }
+    else if (q == 2) { x0 = a.z; x1 = a.w; x2 = b.x; x3 = b.y; x4 = b.z; }
+    else             { x0 = a.w; x1 = b.x; x2 = b.y; x3 = b.z; x4 = b.w; }
+    u32x4 v;
+    v.x = alignbyte(x1, x0, r); v.y = alignbyte(x2, x1, r); v.z = alignbyte(x3, x2, r); v.w = alignbyte(x4, x3, r);
+    return v;
+}
+
+__device__ __forceinline__ u32x4 zero4() { u32x4 z; z.x = z.y = z.z = z.w = 0; return z; }
+
+/* the tile's NALs [j0, j0 + cnt): out(i) = where the packets of NAL j0 + i begin in the output (i = cnt: where they end) */
+struct TileNals {
+    const unsigned long long* s_out; const unsigned long long* s_src; const unsigned long long* s_len;      /* staged: LDS */
+    const unsigned long long* rec_out; const unsigned long long* rec_src; const unsigned long long* rec_len;
+    uint64_t j0;
+    bool lds;
+    __device__ __forceinline__ uint64_t out(uint32_t i) const { return lds ? s_out[i] : rec_out[j0 + i]; }
+    __device__ __forceinline__ uint64_t src(uint32_t i) const { return lds ? s_src[i] : rec_src[j0 + i]; }
+    __device__ __forceinline__ uint64_t len(uint32_t i) const { return lds ? s_len[i] : rec_len[j0 + i]; }
+    /* the last NAL i in [lo, hi] with out(i) <= o (out(lo) <= o holds) */
+    __device__ __forceinline__ uint32_t find(uint32_t lo, uint32_t hi, uint64_t o) const
+    {
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (out(mid) <= o) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    }
+};
+
+/* the packet of byte q of an FU NAL's output: q / P */
+__device__ __forceinline__ uint64_t packet_of(uint64_t q, uint32_t P)
+{
+    return q <= 0xFFFFFFFFull ? (uint64_t)((uint32_t)q / P) : q / P;
+}
+
+/* output byte `cur` of a chunk that holds bytes in front of a packet's NAL bytes or spans packets or NALs (or ends the
+ * output), from the rule; ip: the NAL the chunk's first byte lies in (every NAL has at least 14 output bytes, so the byte lies
+ * in that NAL or in one of the two behind it).  Every load is issued whatever the byte turns out to be -- the NAL's two header
+ * bytes and its record exist for every NAL -- so that the loads of several bytes a lane are in flight together. */
+__device__ __forceinline__ uint32_t chunk_byte(const RtpArgs& a, const TileNals& tn, uint32_t ip, uint64_t cur)
+{
+    ip += cur >= tn.out(ip + 1) ? 1u : 0u;
+    ip += cur >= tn.out(ip + 1) ? 1u : 0u;
+    const uint32_t P = rtp_full_packet_bytes(a.q);
+    const uint64_t O = tn.out(ip), E = tn.out(ip + 1), S = tn.src(ip);
+    const bool fu = tn.len(ip) > a.q.mp;
+    const uint64_t q = cur - O;
+    const uint64_t p = fu ? packet_of(q, P) : 0;                     /* the packet of the NAL, where it begins, its bytes */
+    const uint64_t pstart = O + p * P;
+    const uint64_t plen = fu ? (E - pstart < P ? E - pstart : P) : E - O;
+    const uint32_t i = (uint32_t)(cur - pstart), head = rtp_head_bytes(a.q, fu);
+    const bool payload = i >= head;
+    const uint32_t pay = a.src[S + (payload ? rtp_packet_src(a.q, fu, p) + (i - head) : 0u)];
+    const uint32_t h0 = a.src[S], h1 = a.src[S + 1];
+    const unsigned long long tm = a.rec_tm[tn.j0 + ip], pkt0 = a.rec_pkt[tn.j0 + ip];
+    const uint32_t hb = rtp_head_byte(a.q, fu, p == 0, pstart + plen == E, (tm & kMarker) != 0, plen, pkt0 + p, (uint32_t)tm, h0, h1, payload ? 0u : i);
+    return payload ? pay : hb;
+}
+
+__global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
+{
+    __shared__ unsigned long long s_out[kLdsNals + 1];
+    __shared__ unsigned long long s_src[kLdsNals];
+    __shared__ unsigned long long s_len[kLdsNals];
+    __shared__ uint32_t s_slow[kTile / 16];           /* the chunks done byte by byte: chunk | its NAL's number in the tile << 12 */
+    __shared__ uint32_t s_nslow;
+    if (a.ctl[0] != 0) return;
+    const uint64_t total = a.ctl[1];
+    const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
+    if (t0 >= total) return;
+    const uint32_t tlen = total - t0 < kTile ? (uint32_t)(total - t0) : kTile;
+    const uint64_t j0 = a.tile_first[blockIdx.x], j1 = a.tile_first[blockIdx.x + 1];
+    const uint32_t cnt = (uint32_t)(j1 - j0 + 1);     /* NALs [j0, j1]; rec_out[j1 + 1] exists (the total at the end) */
+    TileNals tn;
+    tn.s_out = s_out; tn.s_src = s_src; tn.s_len = s_len;
+    tn.rec_out = a.rec_out; tn.rec_src = a.rec_src; tn.rec_len = a.rec_len;
+    tn.j0 = j0; tn.lds = false;
+    if (cnt <= kLdsNals) {
+        for (uint32_t i = threadIdx.x; i <= cnt; i += kRT) {
+            s_out[i] = a.rec_out[j0 + i];
+            if (i < cnt) { s_src[i] = a.rec_src[j0 + i]; s_len[i] = a.rec_len[j0 + i]; }
+        }
+        tn.lds = true;
+    }
+    if (threadIdx.x == 0) s_nslow = 0;
+    __syncthreads();
+    const uint32_t P = rtp_full_packet_bytes(a.q), F = a.q.mp - 3u, mp = a.q.mp;
+    const uint32_t head_single = rtp_head_bytes(a.q, false), head_fu = rtp_head_bytes(a.q, true);
+    uint32_t lo = 0;
+#pragma unroll 1
+    for (int b = 0; b < kChunks; b += kBatch) {
+        u32x4 va[kBatch], vb[kBatch];
+        uint32_t sh[kBatch], ip[kBatch];
+        bool simple[kBatch];
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) {
+            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kRT * (uint32_t)(b + u));
+            simple[u] = false; sh[u] = 0; ip[u] = lo;
+            va[u] = zero4(); vb[u] = zero4();
+            if (r < tlen) {
+                const uint64_t o = t0 + r;
+                lo = tn.find(lo, cnt - 1, o);
+                ip[u] = lo;
+                if (o + 16 <= tn.out(lo + 1)) {                       /* the chunk ends inside the NAL's packets */
+                    const uint64_t q = o - tn.out(lo), S = tn.src(lo);
+                    uint64_t s;
+                    bool ok;
+                    if (tn.len(lo) <= mp) {
+                        ok = q >= head_single;
+                        s = S + (q - head_single);
+                    } else {
+                        const uint64_t p = packet_of(q, P);
+                        const uint32_t i = (uint32_t)(q - p * P);
+                        ok = i >= head_fu && i + 16u <= P;
+                        s = S + 2u + p * F + (i - head_fu);
+                    }
+                    if (ok) {
+                        const uint64_t g = s & ~15ull;
+                        sh[u] = (uint32_t)(s & 15u);
+                        simple[u] = true;
+                        va[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g));
+                        if (sh[u]) vb[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g + 16));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) {
+            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kRT * (uint32_t)(b + u));
+            if (simple[u]) arena_store16(a.out + t0 + r, realign(va[u], vb[u], sh[u]));
+            else if (r < tlen) s_slow[atomicAdd(&s_nslow, 1u)] = (r >> 4) | (ip[u] << 12);
+        }
+    }
+    /* behind the batches: the tile's slow chunks, sixty-four at a time, a lane a byte of four of them; the sixteen lanes of a chunk put their
+     * bytes together and the first stores them */
+    __syncthreads();
+    const uint32_t nslow = s_nslow;
+#pragma unroll 1
+    for (uint32_t base = 0; base < nslow; base += kSlowBatch * (kRT / 16)) {
+        const uint32_t b = threadIdx.x & 15u;
+        uint32_t v[kSlowBatch], r[kSlowBatch], len[kSlowBatch];
+#pragma unroll
+        for (int u = 0; u < kSlowBatch; ++u) {
+            const uint32_t c = base + (uint32_t)u * (kRT / 16) + (threadIdx.x >> 4);
+            v[u] = 0; r[u] = 0; len[u] = 0;
+            if (c < nslow) {
+                const uint32_t e = s_slow[c];
+                r[u] = (e & 0xFFFu) << 4;
+                len[u] = tlen - r[u] < 16 ? tlen - r[u] : 16u;
+                if (b < len[u]) v[u] = chunk_byte(a, tn, e >> 12, t0 + r[u] + b);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kSlowBatch; ++u) {
+            if (!len[u]) continue;                                    /* (the sixteen lanes of a chunk agree) */
+            uint32_t w = v[u] << (8u * (b & 3u));
+            w |= __shfl_xor(w, 1, 16);
+            w |= __shfl_xor(w, 2, 16);
+            u32x4 x;
+            x.x = __shfl(w, 0, 16); x.y = __shfl(w, 4, 16); x.z = __shfl(w, 8, 16); x.w = __shfl(w, 12, 16);
+            if (len[u] == 16) { if (b == 0) arena_store16(a.out + t0 + r[u], x); }
+            else if (b < len[u]) a.out[t0 + r[u] + b] = (uint8_t)v[u];  /* the output's end: these bytes and no others */
+        }
+    }
+}
+
+} // namespace
+
+hipError_t launch_rtp_pack(const RtpArgs& a, hipStream_t st)
+{
+    const uint64_t blocks = (a.n_nals + kRtpNalsPerBlock - 1) / kRtpNalsPerBlock;
+    if (a.ev_begin) { const hipError_t e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    if (blocks) hipLaunchKernelGGL(k_rtp_count, dim3((unsigned)blocks), dim3(kRtpPlanLanes), 0, st, a);
+    hipLaunchKernelGGL(k_rtp_scan, dim3(1), dim3(kPlanLanes), 0, st, a, blocks);
+    if (a.out && blocks) {
+        hipLaunchKernelGGL(k_rtp_place, dim3((unsigned)blocks), dim3(kRtpPlanLanes), 0, st, a);
+        if (a.tiles) {
+            hipLaunchKernelGGL(k_rtp_tiles, dim3((unsigned)((a.tiles + 1 + 255) / 256)), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_rtp_copy, dim3((unsigned)a.tiles), dim3(kRT), 0, st, a);
+        }
+    }
+    return end_launches(a.ev_end, st);
+}
+
+} // namespace hbs
+
+extern "C" {
+
+uint64_t hbs_rtp_nal_packets_host(uint64_t nal_bytes, int max_payload)
+{
+    return hbs::rtp_nal_packets_host(nal_bytes, max_payload);
+}
+
+int hbs_rtp_packet_host(const uint8_t* pkt, uint64_t n, hbs_rtp_packet* out)
+{
+    return hbs::rtp_packet_host(pkt, n, out);
+}
+
+}

@@ -111,8 +111,8 @@ typedef struct hbs_ctx hbs_ctx;
  * on the data made on the device -- and may be captured into a HIP graph (hipStreamBeginCapture on the bound stream) after ONE
  * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
- *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep.
- * The list is what tests/test_gpu_graphs.py and tests/test_gpu_scan.py replay, no more: hbs_parse_headers_compact,
+ *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack.
+ * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py and tests/test_gpu_rtp.py replay, no more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
  * A replay is the captured call on what the buffers hold then: every argument the host passed (counts, byte sizes, capacities,
@@ -596,6 +596,103 @@ int hbs_ts_mux(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
                uint32_t* d_au_packet /* optional, n_aus + 1 */, hbs_summary* d_summary);
 int hbs_ts_mux_psi_host(const hbs_ts_mux_params* params, uint8_t pat188[188], uint8_t pmt188[188]);
 uint64_t hbs_ts_mux_au_packets_host(uint64_t es_bytes, int time_fields /* 0, 1, 2 */, int pcr);
+
+/*
+ * ---- NAL units -> RTP packets (RFC 7798): single NAL unit packets, fragmentation units, the marker bit ------------------
+ * hbs_rtp_pack is the third transport: every NAL of a stream in device memory becomes one RTP packet, or a run of
+ * fragmentation units (FUs) when it is larger than a packet may be.  It needs the stream, its index and, for the marker bit and
+ * the timestamps, the AU number of every NAL (hbs_access_units' d_nal_au, hbs_au_insert's d_nal_au_out) and the AUs' times
+ * (hbs_ts_demux's PES table).
+ *
+ * NAL k.  Bytes stream[start_k, end_k), L = end - start; h0 = stream[start], h1 = stream[start + 1], type t = (h0 >> 1) & 63;
+ * mp = max_payload, F = mp - 3.
+ * SINGLE NAL UNIT PACKET, when L <= mp: one packet whose payload is the L bytes verbatim.
+ * FRAGMENTATION UNITS, when L > mp: the body is the B = L - 2 bytes stream[start + 2, end); n = ceil(B / F) packets (always
+ * >= 2, so no FU carries both S and E).  Packet i carries the 2-byte PayloadHdr (h0 & 0x81) | 0x62, h1 (type 49, the NAL's F
+ * bit, layer id and TID), then the FU header (i == 0) << 7 | (i == n - 1) << 6 | t, then the body bytes
+ * [i F, min((i + 1) F, B)): only the last fragment is short.  No DONL fields (sprop-max-don-diff = 0), no aggregation packets.
+ * RTP HEADER, 12 bytes.  0x80, M << 7 | payload_type, the sequence number (seq + j) & 0xFFFF of the call's j-th packet
+ * big-endian, the timestamp big-endian, the ssrc big-endian.  M = 1 exactly on the last packet of the last NAL of an access
+ * unit: NAL k with k == n_nals - 1 or d_nal_au[k + 1] != d_nal_au[k]; with HBS_RTP_OPEN_END the call's last NAL is exempt.
+ * ACCESS UNITS AND TIMES.  a_k = d_nal_au[k] - d_nal_au[0]; every step d_nal_au[k] - d_nal_au[k - 1] must be 0 or 1 and
+ * a_k < n_aus, so a range is passed by pointer offset into the tables, like a GOP cut to hbs_ts_mux.  d_nal_au == NULL: the
+ * whole batch is AU 0 and n_aus is ignored.  The timestamp of AU a, modulo 2^32, is ts_base + (uint32_t)d_pts[a] when d_pts is
+ * given and ts_base + a * ts_step when it is not.  A d_pts[a] of 2^33 or more is an error, the ~0 "absent" of hbs_ts_demux
+ * included: RTP has no packet without a time.
+ *
+ * THE CALL.  The output is the packets of NAL 0, 1, ... in that order, each as `framing` bytes of length (12 + payload bytes,
+ * big-endian; RFC 4571) when framing is 2, the header, the payload.  Nothing between NALs is copied.  d_nal_off[k] (optional,
+ * n_nals + 1 entries) = the output offset where NAL k's first packet begins, its length field included, entry n_nals the
+ * total; d_nal_packet[k] (optional, n_nals + 1) = the number of NAL k's first packet, entry n_nals the packet count.  All
+ * packets of a NAL but its last take framing + 12 + mp bytes, so the two tables and the rule give every packet's offset
+ * without a table per packet.  d_out == NULL: plan only, the summary alone is written.  n_nals == 0 is valid: an empty output,
+ * entry 0 of both tables 0.
+ *   d_summary   nal_count = packets, nal_found = n_nals, rbsp_bytes = NAL bytes carried (the sum of L), stream_bytes = output
+ *               bytes, stop_reason = 0, reserved[1] = packets (the next call's seq is (seq + reserved[1]) & 0xFFFF),
+ *               reserved[2] = NALs sent as FUs.
+ *               error = HBS_E_ARG with reserved[0] = 1 + the lowest offending NAL when a NAL has L < 2, has t >= 48 (48 to 50
+ *               mean AP / FU / PACI to a receiver: filter such NALs out first with hbs_filter_annexb), has an index entry that
+ *               is inconsistent by the filter's definition (start > end, end > stream_bytes, start_k < end_{k-1}), breaks an
+ *               AU-number rule or belongs to an AU whose time is out of range; every record is checked before it is used;
+ *               the other counts mean nothing then.  Else HBS_E_CAPACITY when out_cap is below the output; the counts are
+ *               right.  On either error nothing is written but the summary.
+ * Refused with HBS_E_ARG at once, before anything is written: params NULL or out of range (max_payload outside 4..65523,
+ * payload_type outside 0..127, framing not 0 or 2, unknown flags, seq above 65535), n_nals above 2^32 - 1, out_cap above 2^46
+ * with a d_out, missing or misaligned pointers.
+ * Nothing outside [d_out, d_out + output bytes), the n_nals + 1 entries of the two tables and the summary is stored; no load
+ * touches a 16-byte granule that holds no byte of the stream, and a NAL's first byte is read only after its entry has been
+ * checked; no host synchronisation; scratch comes from the context's workspace (40 bytes a NAL, and 8 bytes per 64 KiB output
+ * tile of what out_cap and the stream can hold).
+ * Alignment: d_stream, d_out, d_summary 16 bytes; d_index, d_pts, d_nal_off, d_nal_packet 8 bytes; d_nal_au 4 bytes.
+ * STATED LIMITS: no aggregation packets (every NAL has a packet of its own); no DONL fields, no interleaving; no PACI; no
+ * header extension and no CSRC entries on the sending side; no RTCP; no SRTP; no depacketizer on the device --
+ * hbs_rtp_packet_host reads one packet on the host.
+ *
+ * Host side, plain C, no GPU involved.
+ * hbs_rtp_nal_packets_host: the packets of a NAL of nal_bytes bytes; 0 for nal_bytes < 2 or a max_payload out of range.
+ * hbs_rtp_packet_host: one RTP packet pkt[0, n) (without a length field) as a receiver reads it -- CSRC entries, a header
+ * extension and padding are accounted for by RFC 3550, so payload_off / payload_len are right for packets this library did not
+ * write.  kind by the payload's type: below 48 a single NAL unit (nal_off / nal_len = the payload), 49 an FU (fu_start,
+ * fu_end, nal_type from the FU header, nal_header = the two reconstructed header bytes of the NAL, nal_off / nal_len = the
+ * fragment behind the three bytes), 48 an AP, anything else HBS_RTP_OTHER (a payload below 2 bytes: nal_type -1).  0, or
+ * HBS_E_ARG for a version other than 2, NULL pointers or a packet shorter than its own fields say.
+ */
+typedef struct hbs_rtp_params {   /* HOST memory, 32 bytes */
+    int32_t  max_payload;   /* most RTP payload bytes in a packet (behind the 12-byte header): 4 .. 65523 */
+    int32_t  payload_type;  /* 0 .. 127 */
+    int32_t  framing;       /* 0: packets back to back; 2: a big-endian 16-bit packet length in front of each (RFC 4571) */
+    uint32_t flags;         /* HBS_RTP_* */
+    uint32_t ssrc;
+    uint32_t seq;           /* sequence number of the call's first packet, 0 .. 65535 */
+    uint32_t ts_base;       /* added to every timestamp, modulo 2^32 */
+    uint32_t ts_step;       /* with d_pts == NULL: the timestamp of AU a is ts_base + a * ts_step */
+} hbs_rtp_params;
+#define HBS_RTP_OPEN_END 1u  /* the call's last NAL does not end its access unit: no marker bit on its last packet */
+
+#define HBS_RTP_SINGLE 0     /* hbs_rtp_packet.kind */
+#define HBS_RTP_FU     1
+#define HBS_RTP_AP     2
+#define HBS_RTP_OTHER  3
+typedef struct hbs_rtp_packet {   /* 72 bytes */
+    uint64_t payload_off, payload_len;   /* the RTP payload: behind header, CSRC entries and extension, in front of the padding */
+    uint64_t nal_off, nal_len;           /* where the NAL's bytes lie (an FU: the fragment)                                     */
+    int32_t  kind;                       /* HBS_RTP_SINGLE / FU / AP / OTHER                                                    */
+    int32_t  nal_type;                   /* the NAL's type (an FU: from the FU header); -1: no payload header                   */
+    uint32_t marker, payload_type, seq, timestamp, ssrc;
+    uint32_t fu_start, fu_end;           /* an FU's S and E bits                                                                */
+    uint8_t  nal_header[2];              /* the NAL's two header bytes (an FU: reconstructed)                                   */
+    uint8_t  reserved[2];
+} hbs_rtp_packet;
+
+int hbs_rtp_pack(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
+                 const hbs_nal_entry* d_index, uint64_t n_nals,
+                 const uint32_t* d_nal_au /* nullable */, uint64_t n_aus, const uint64_t* d_pts /* nullable */,
+                 const hbs_rtp_params* params,
+                 uint8_t* d_out, uint64_t out_cap,
+                 uint64_t* d_nal_off /* optional, n_nals + 1 */, uint64_t* d_nal_packet /* optional, n_nals + 1 */,
+                 hbs_summary* d_summary);
+uint64_t hbs_rtp_nal_packets_host(uint64_t nal_bytes, int max_payload);
+int hbs_rtp_packet_host(const uint8_t* pkt, uint64_t n, hbs_rtp_packet* out);
 
 /*
  * K4: header parse, one NAL per lane (64 per wavefront), over the RBSP arena and index that
