@@ -51,6 +51,9 @@ RTP_PACKET = np.dtype([("payload_off", "<u8"), ("payload_len", "<u8"), ("nal_off
                        ("ssrc", "<u4"), ("fu_start", "<u4"), ("fu_end", "<u4"), ("nal_header", "u1", (2,)), ("reserved", "u1", (2,))])
 RTP_OPEN_END = 1
 RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER = 0, 1, 2, 3
+# layout of hbs_rtp_unpack_params and the flags of hbs_rtp_unpack
+RTP_UNPACK_PARAMS = np.dtype([("payload_type", "<i4"), ("startcode_bytes", "<i4"), ("flags", "<u4"), ("ssrc", "<u4")])
+RTPU_MATCH_SSRC = 1
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -82,7 +85,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
            "hbs_au_insert", "hbs_aud_nal_host",
-           "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host"]
+           "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host",
+           "hbs_rtp_unpack", "hbs_rtp_frames_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -233,6 +237,10 @@ def load_library():
     lib.hbs_rtp_nal_packets_host.argtypes = [C.c_uint64, C.c_int]
     lib.hbs_rtp_nal_packets_host.restype = C.c_uint64
     lib.hbs_rtp_packet_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.hbs_rtp_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                   C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.hbs_rtp_frames_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.hbs_rtp_frames_host.restype = C.c_uint64
     _lib = lib
     return lib
 
@@ -327,6 +335,30 @@ def rtp_packet_offsets(nal_off, nal_packet, max_payload, framing=0):
     within = np.arange(int(nal_packet[-1]), dtype=np.uint64) - first
     off = np.repeat(nal_off[:-1], count) + within * np.uint64(int(framing) + 12 + int(max_payload))
     return np.concatenate([off, nal_off[-1:]]).astype(np.uint64)
+
+
+def rtp_unpack_params(payload_type=96, startcode_bytes=4, flags=0, ssrc=0):
+    """an hbs_rtp_unpack_params record (ndarray[RTP_UNPACK_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=RTP_UNPACK_PARAMS)
+    p[0] = (payload_type, startcode_bytes, flags, ssrc)
+    return p
+
+
+def rtp_frames(data, cap=None):
+    """hbs_rtp_frames_host: the packets of an RFC 4571 byte stream (bytes or a uint8 array, host memory) -> (packet offsets,
+    packet sizes, bytes the whole frames take); the tables are what hbs_rtp_unpack takes.  cap: fill no more than that many
+    entries (the frames are still counted: see the fourth value).  -> (off ndarray[uint64], size ndarray[uint64], used, frames).
+    No GPU involved."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
+    lib = load_library()
+    used = C.c_uint64(0)
+    ptr = a.ctypes.data if len(a) else None
+    if cap is None:
+        cap = int(lib.hbs_rtp_frames_host(ptr, len(a), None, None, 0, C.byref(used)))
+    off, size = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+    frames = int(lib.hbs_rtp_frames_host(ptr, len(a), off.ctypes.data if cap else None, size.ctypes.data if cap else None, cap, C.byref(used)))
+    filled = min(frames, cap)
+    return off[:filled], size[:filled], int(used.value), frames
 
 
 class Context:
@@ -1044,6 +1076,65 @@ class Context:
             raise HbsError("hbs_rtp_pack: error %d" % int(s["error"]))
         tabs = [x.cpu().numpy().view(np.uint64) for x in (nal_off, nal_packet)]
         return out[:need], rtp_packet_offsets(tabs[0], tabs[1], int(prm["max_payload"][0]), int(prm["framing"][0])), s
+
+    def rtp_unpack_async(self, data, in_bytes, pkt_off, pkt_size, n_packets, params, out, index_out, nal_au_out, au_ts_out, summary,
+                         out_cap=None, nal_cap=None, au_cap=None):
+        """Enqueue hbs_rtp_unpack on the current torch stream.  data / pkt_off / pkt_size / out / index_out / nal_au_out /
+        au_ts_out / summary are device tensors (index_out, nal_au_out, au_ts_out may be None; out None: plan only); params is
+        an ndarray[RTP_UNPACK_PARAMS] of one in host memory.  nal_cap / au_cap default to what the tensors hold.  Returns the
+        call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        if nal_cap is None:
+            caps = [x.numel() * x.element_size() // w for x, w in ((index_out, NAL_ENTRY.itemsize), (nal_au_out, 4)) if x is not None]
+            nal_cap = min(caps) if caps else (1 << 64) - 1
+        if au_cap is None:
+            au_cap = au_ts_out.numel() * au_ts_out.element_size() // 8 if au_ts_out is not None else 0
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=RTP_UNPACK_PARAMS)
+        return self.lib.hbs_rtp_unpack(self.h, p(data) if in_bytes else None, int(in_bytes), p(pkt_off) if n_packets else None,
+                                       p(pkt_size) if n_packets else None, int(n_packets),
+                                       params.ctypes.data_as(C.c_void_p) if params is not None else None, p(out), int(out_cap),
+                                       p(index_out), p(nal_au_out), int(nal_cap), p(au_ts_out), int(au_cap), p(summary))
+
+    def rtp_unpack(self, data, pkt_off, pkt_size, in_bytes=None, **params):
+        """Convenience: the RTP packets data[off_p, off_p + size_p) (data: device uint8 tensor; pkt_off / pkt_size: uint64 arrays,
+        host or device tensors of their bytes) as one Annex-B stream; params: the keywords of rtp_unpack_params.  Plans first,
+        allocates the exact outputs, runs.  Returns (out device tensor, index device tensor of NAL_ENTRY records, nal_au
+        ndarray[uint32], au_ts ndarray[uint64], summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x):
+            if isinstance(x, np.ndarray):
+                a = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8)
+                return (t.from_numpy(a.copy()).to(dev) if a.size else t.zeros(16, dtype=t.uint8, device=dev)), len(x)
+            return x, x.numel() * x.element_size() // 8
+        d_off, n = dv(pkt_off)
+        d_size, n2 = dv(pkt_size)
+        if n != n2:
+            raise HbsError("hbs_rtp_unpack: %d packet offsets, %d sizes" % (n, n2))
+        prm = rtp_unpack_params(**params)
+        nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        args = (data, nbytes, d_off, d_size, n, prm)
+        self._check(self.rtp_unpack_async(*args, None, None, None, None, summary), "hbs_rtp_unpack")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_rtp_unpack: error %d (packet %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        need, nals, aus = int(s["stream_bytes"]), int(s["nal_count"]), int(s["reserved"][1])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        index = t.empty(max(nals, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
+        nal_au = t.empty(max(nals, 1) * 4, dtype=t.uint8, device=dev)
+        au_ts = t.empty(max(aus, 1) * 8, dtype=t.uint8, device=dev)
+        self._check(self.rtp_unpack_async(*args, out, index, nal_au, au_ts, summary, out_cap=need, nal_cap=nals, au_cap=aus), "hbs_rtp_unpack")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_rtp_unpack: error %d" % int(s["error"]))
+        return (out[:need], index[: nals * NAL_ENTRY.itemsize], nal_au[: nals * 4].cpu().numpy().view(np.uint32).copy(),
+                au_ts[: aus * 8].cpu().numpy().view(np.uint64).copy(), s)
 
     # ---- access units -----------------------------------------------------------------
 

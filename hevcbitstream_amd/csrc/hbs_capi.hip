@@ -24,6 +24,7 @@
 #include "hbs_tsmux.h"
 #include "hbs_auins.h"
 #include "hbs_rtp.h"
+#include "hbs_rtpun.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -41,8 +42,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kTws    hbs_ts_demux's scratch
  * kMws    hbs_ts_mux's scratch
  * kIws    hbs_au_insert's scratch
- * kRws    hbs_rtp_pack's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kBufs };
+ * kRws    hbs_rtp_pack's scratch
+ * kUws    hbs_rtp_unpack's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -763,6 +765,42 @@ int hbs_rtp_pack(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_rtp_pack(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_pack");
+}
+
+int hbs_rtp_unpack(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
+                   const uint64_t* d_pkt_off, const uint64_t* d_pkt_size, uint64_t n_packets,
+                   const hbs_rtp_unpack_params* params, uint8_t* d_out, uint64_t out_cap,
+                   hbs_nal_entry* d_index_out, uint32_t* d_nal_au_out, uint64_t nal_cap,
+                   uint64_t* d_au_ts_out, uint64_t au_cap, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_rtp_unpack_params) == 16, "hbs_rtp_unpack_params layout");
+    if (!c || !d_summary || !hbs::rtpu_params_ok(params) || n_packets > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_packets && (!d_pkt_off || !d_pkt_size || (in_bytes && !d_in))) return HBS_E_ARG;
+    if (misaligned(d_in, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_pkt_off, 7) || misaligned(d_pkt_size, 7) ||
+        misaligned(d_index_out, 7) || misaligned(d_au_ts_out, 7) || misaligned(d_nal_au_out, 3)) {
+        snprintf(c->err, sizeof(c->err), "input/output/summary pointers must be 16-byte aligned, packet tables, output index and AU times 8-byte, AU numbers 4-byte");
+        return HBS_E_ARG;
+    }
+    if (d_out && out_cap > hbs::kRtpuOutCapMax) {
+        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::RtpuArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = in_bytes;
+    a.pkt_off = reinterpret_cast<const unsigned long long*>(d_pkt_off);
+    a.pkt_size = reinterpret_cast<const unsigned long long*>(d_pkt_size); a.n_packets = n_packets;
+    a.q = hbs::rtpu_rule(params);
+    a.out_cap = out_cap; a.nal_cap = nal_cap; a.au_cap = au_cap; a.summary = d_summary;
+    if (d_out) { a.index_out = d_index_out; a.nal_au_out = d_nal_au_out; a.au_ts_out = reinterpret_cast<unsigned long long*>(d_au_ts_out); }
+    a.t.src = d_in; a.t.out = d_out;
+    a.t.tiles = d_out ? hbs::piece_tiles(out_cap) : 0;              /* (packets may overlap: the input's size bounds nothing; out_cap is bounded above) */
+    const int rc = carve(c, c->buf[kUws], "hipMalloc(RTP unpack scratch)", [&](hbs::Carver& w) { hbs::lay_rtpu(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_rtp_unpack(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_unpack");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,

@@ -2,8 +2,9 @@
  * hbs_rtp.h -- hbs_rtp_pack (include/hevcbitstream_amd.h): the rule that turns one NAL unit into RFC 7798 RTP packets, as
  * host/device inline functions -- rtp_nal lays a NAL out (single NAL unit packet or fragmentation units, packets, output
  * bytes), rtp_packet_bytes gives packet p's length and rtp_head_byte every byte in front of its NAL bytes; the kernels of
- * hbs_rtp.hip, the two host entry points and the tests all run them -- the receiver's view of one packet (rtp_packet_host),
- * and the host-visible launcher.  Everything above the launcher compiles with plain g++.
+ * hbs_rtp.hip, the two host entry points and the tests all run them -- the receiver's view of one packet (rtp_packet_rule: a
+ * host/device function too, behind rtp_packet_host and in the kernels of hbs_rtp_unpack, hbs_rtpun.hip), and the host-visible
+ * launcher.  Everything above the launcher compiles with plain g++.
  */
 #ifndef HBS_RTP_H
 #define HBS_RTP_H
@@ -126,52 +127,69 @@ inline void rtp_write_packet_host(const RtpRule& q, const uint8_t* nal, uint64_t
     for (uint64_t i = head; i < plen; ++i) out[i] = nal[src + (i - head)];
 }
 
-/* one RTP packet pkt[0, n) (no length field) as a receiver reads it: RFC 3550 5.1 / 5.3.1, RFC 7798 4.4 */
-inline int rtp_packet_host(const uint8_t* pkt, uint64_t n, hbs_rtp_packet* out)
+/* one RTP packet of n bytes (no length field) as a receiver reads it: RFC 3550 5.1 / 5.3.1, RFC 7798 4.4.  byte(i) is byte i of
+ * the packet; none at or beyond n is asked for.  The one rule of hbs_rtp_packet_host and of the kernels of hbs_rtp_unpack
+ * (hbs_rtpun.hip), which keep a packet's first bytes in registers */
+template <class B> HBS_HD int rtp_packet_rule(B byte, uint64_t n, hbs_rtp_packet* out)
 {
-    if (!pkt || !out || n < kRtpHeader || (pkt[0] >> 6) != 2u) return HBS_E_ARG;
-    uint64_t head = kRtpHeader + 4u * (pkt[0] & 15u);                /* the CSRC entries */
+    if (n < kRtpHeader) return HBS_E_ARG;
+    const uint32_t b0 = byte(0), b1 = byte(1);
+    if ((b0 >> 6) != 2u) return HBS_E_ARG;
+    uint64_t head = kRtpHeader + 4u * (b0 & 15u);                    /* the CSRC entries */
     if (head > n) return HBS_E_ARG;
-    if (pkt[0] & 0x10u) {                                            /* a header extension: 16 bits of profile, 16 of length in words */
+    if (b0 & 0x10u) {                                                /* a header extension: 16 bits of profile, 16 of length in words */
         if (n - head < 4u) return HBS_E_ARG;
-        const uint64_t words = ((uint64_t)pkt[head + 2] << 8) | pkt[head + 3];
+        const uint64_t words = ((uint64_t)byte(head + 2) << 8) | byte(head + 3);
         head += 4u;
         if (n - head < 4u * words) return HBS_E_ARG;
         head += 4u * words;
     }
     uint64_t pad = 0;
-    if (pkt[0] & 0x20u) {                                            /* padding: its last byte counts it, itself included */
-        pad = pkt[n - 1];
+    if (b0 & 0x20u) {                                                /* padding: its last byte counts it, itself included */
+        pad = byte(n - 1);
         if (pad == 0 || pad > n - head) return HBS_E_ARG;
     }
     hbs_rtp_packet r;
     r.payload_off = head; r.payload_len = n - head - pad;
-    r.marker = pkt[1] >> 7; r.payload_type = pkt[1] & 127u;
-    r.seq = ((uint32_t)pkt[2] << 8) | pkt[3];
-    r.timestamp = ((uint32_t)pkt[4] << 24) | ((uint32_t)pkt[5] << 16) | ((uint32_t)pkt[6] << 8) | pkt[7];
-    r.ssrc = ((uint32_t)pkt[8] << 24) | ((uint32_t)pkt[9] << 16) | ((uint32_t)pkt[10] << 8) | pkt[11];
+    r.marker = b1 >> 7; r.payload_type = b1 & 127u;
+    r.seq = (byte(2) << 8) | byte(3);
+    r.timestamp = (byte(4) << 24) | (byte(5) << 16) | (byte(6) << 8) | byte(7);
+    r.ssrc = (byte(8) << 24) | (byte(9) << 16) | (byte(10) << 8) | byte(11);
     r.kind = HBS_RTP_OTHER; r.nal_type = -1; r.fu_start = r.fu_end = 0;
     r.nal_off = r.payload_off; r.nal_len = r.payload_len;
     r.nal_header[0] = r.nal_header[1] = 0; r.reserved[0] = r.reserved[1] = 0;
     if (r.payload_len >= 2) {
-        const uint8_t* p = pkt + head;
-        const uint32_t t = (p[0] >> 1) & 63u;
-        r.nal_type = (int32_t)t; r.nal_header[0] = p[0]; r.nal_header[1] = p[1];
+        const uint32_t p0 = byte(head), p1 = byte(head + 1);
+        const uint32_t t = (p0 >> 1) & 63u;
+        r.nal_type = (int32_t)t; r.nal_header[0] = (uint8_t)p0; r.nal_header[1] = (uint8_t)p1;
         if (t < 48u) {
             r.kind = HBS_RTP_SINGLE;
         } else if (t == 48u) {
             r.kind = HBS_RTP_AP;
         } else if (t == 49u) {
             if (r.payload_len < kRtpFuHeader) return HBS_E_ARG;
+            const uint32_t p2 = byte(head + 2);
             r.kind = HBS_RTP_FU;
-            r.fu_start = p[2] >> 7; r.fu_end = (p[2] >> 6) & 1u;
-            r.nal_type = (int32_t)(p[2] & 63u);
-            r.nal_header[0] = (uint8_t)((p[0] & 0x81u) | ((p[2] & 63u) << 1));
+            r.fu_start = p2 >> 7; r.fu_end = (p2 >> 6) & 1u;
+            r.nal_type = (int32_t)(p2 & 63u);
+            r.nal_header[0] = (uint8_t)((p0 & 0x81u) | ((p2 & 63u) << 1));
             r.nal_off = head + kRtpFuHeader; r.nal_len = r.payload_len - kRtpFuHeader;
         }
     }
     *out = r;
     return 0;
+}
+
+/* bytes in memory: byte i of the packet at p */
+struct RtpBytesAt {
+    const uint8_t* p;
+    HBS_M uint32_t operator()(uint64_t i) const { return p[i]; }
+};
+
+inline int rtp_packet_host(const uint8_t* pkt, uint64_t n, hbs_rtp_packet* out)
+{
+    if (!pkt || !out) return HBS_E_ARG;
+    return rtp_packet_rule(RtpBytesAt{pkt}, n, out);
 }
 
 #ifdef __HIPCC__

@@ -111,8 +111,9 @@ typedef struct hbs_ctx hbs_ctx;
  * on the data made on the device -- and may be captured into a HIP graph (hipStreamBeginCapture on the bound stream) after ONE
  * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
- *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack.
- * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py and tests/test_gpu_rtp.py replay, no more: hbs_parse_headers_compact,
+ *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack, hbs_rtp_unpack.
+ * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py and tests/test_gpu_rtp_unpack.py replay, no
+ * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
  * A replay is the captured call on what the buffers hold then: every argument the host passed (counts, byte sizes, capacities,
@@ -645,7 +646,7 @@ uint64_t hbs_ts_mux_au_packets_host(uint64_t es_bytes, int time_fields /* 0, 1, 
  * tile of what out_cap and the stream can hold).
  * Alignment: d_stream, d_out, d_summary 16 bytes; d_index, d_pts, d_nal_off, d_nal_packet 8 bytes; d_nal_au 4 bytes.
  * STATED LIMITS: no aggregation packets (every NAL has a packet of its own); no DONL fields, no interleaving; no PACI; no
- * header extension and no CSRC entries on the sending side; no RTCP; no SRTP; no depacketizer on the device --
+ * header extension and no CSRC entries on the sending side; no RTCP; no SRTP.  The way back is hbs_rtp_unpack (below);
  * hbs_rtp_packet_host reads one packet on the host.
  *
  * Host side, plain C, no GPU involved.
@@ -693,6 +694,96 @@ int hbs_rtp_pack(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
                  hbs_summary* d_summary);
 uint64_t hbs_rtp_nal_packets_host(uint64_t nal_bytes, int max_payload);
 int hbs_rtp_packet_host(const uint8_t* pkt, uint64_t n, hbs_rtp_packet* out);
+
+/*
+ * ---- RTP packets (RFC 7798) -> Annex-B: single NAL unit packets, aggregation packets, fragmentation units ---------------
+ * hbs_rtp_unpack is the receiver's side of the third transport: a table of RTP packets in device memory becomes the Annex-B
+ * stream of their NAL units, with the index hbs_parse_headers* and hbs_filter_annexb take, the AU number of every NAL and the
+ * timestamp of every AU.  hbs_rtp_pack never makes aggregation packets; a receiver meets them, and this call reads them.
+ *
+ * PACKETS.  Packet p is d_in[d_pkt_off[p], d_pkt_off[p] + d_pkt_size[p]), a raw RTP packet without a length field.  Packets may
+ * lie anywhere in the buffer, in any order, and may overlap, like the samples of hbs_lenpref_to_annexb; the output follows the
+ * order of the TABLE, so a caller reorders late packets by permuting the table.  The framed output of hbs_rtp_pack (framing 2)
+ * is passed by adding 2 to each packet offset; hbs_rtp_frames_host makes the table of any RFC 4571 byte stream.
+ *
+ * THE PACKET RULE, in this order.
+ * 1. ENTRY FAULT: off + size wraps or exceeds in_bytes.  Every entry is checked before a byte of its packet is read.
+ * 2. HEADER FAULT: what hbs_rtp_packet_host refuses -- fewer than 12 bytes, a version other than 2, shorter than its own CSRC /
+ *    extension / padding fields say, a fragmentation unit's payload below 3 bytes.  (One function, rtp_packet_rule, runs in the
+ *    kernels and behind hbs_rtp_packet_host.)
+ * 3. OTHER: the payload type differs from params->payload_type, or, with HBS_RTPU_MATCH_SSRC, the ssrc differs from
+ *    params->ssrc.  Such a packet is not this stream's and plays no further part, but it still stands between its table
+ *    neighbours: it ends a chain (below) and no sequence break is counted across it.
+ * 4. ACCEPTED, by the type t = (payload[0] >> 1) & 63 of the payload's first two bytes (the PayloadHdr):
+ *    a payload below 2 bytes, or t in 50..63 (PACI, reserved): unsupported -- dropped and counted;
+ *    t < 48: a single NAL unit, the payload verbatim;
+ *    t == 48: an aggregation packet without DONL fields.  Behind the PayloadHdr come units of a big-endian 16-bit size s and
+ *      then s bytes, until the payload's end; each unit is one NAL.  A FAULT when there is no unit, when fewer than 2 bytes are
+ *      left for a size, when s < 2 or s exceeds what is left, or when a unit's NAL type is 48 or above.  Every size is bounded
+ *      before it is used;
+ *    t == 49: a fragmentation unit (FU): PayloadHdr, the FU header S << 7 | E << 6 | type, the fragment.  A FAULT when the FU
+ *      header's type is 48 or above.  An empty fragment is accepted; S and E both set is a NAL of one fragment.
+ * CHAINS.  An accepted FU p CONTINUES packet p - 1 of the table when p has no S, p - 1 is an accepted FU without E, both have
+ * the same FU type, the same two PayloadHdr bytes, the same timestamp and the same ssrc, and seq_p == (seq_{p-1} + 1) & 0xFFFF.
+ * A chain is a maximal run of FUs in which every packet but the first continues the one in front of it; it is WHOLE when its
+ * first packet has S and its last has E.  A whole chain is one NAL: the two header bytes (payload[0] & 0x81) | type << 1,
+ * payload[1] rebuilt from its first packet, then the fragments in order; its timestamp is its first packet's and its marker its
+ * last packet's.  Every FU of a chain that is not whole is dropped and counted: ONLY WHOLE NALS EVER REACH THE OUTPUT.
+ *
+ * THE OUTPUT.  For every NAL in table order `startcode_bytes` bytes of start code (00 00 01 or 00 00 00 01) and then its bytes.
+ * d_index_out[k] (optional): start / end = NAL k's bytes in the output (behind its start code), rbsp_off = rbsp_len = 0,
+ * status = 0 and HBS_ST_UNTERMINATED on the last entry only -- what hbs_index_extract says of the same stream.
+ * ACCESS UNITS.  NAL k begins an access unit when k == 0, when its timestamp differs from NAL k - 1's, or when NAL k - 1
+ * carried the marker; the marker of an aggregation packet belongs to its last unit.  d_nal_au_out[k] (optional) = the AU's
+ * number from 0; d_au_ts_out[a] (optional) = the timestamp of AU a's first NAL as a uint64_t.  The two tables go straight into
+ * hbs_rtp_pack, hbs_ts_mux (as its times) and hbs_annexb_to_lenpref.
+ * d_out == NULL: plan only -- the summary alone is written and no capacity is looked at.  n_packets == 0 is valid.
+ *   d_summary   nal_count = NALs, nal_found = accepted packets, stream_bytes = output bytes, rbsp_bytes = NAL bytes (the output
+ *               without its start codes), stop_reason = -1 when a NAL came out, else 0; reserved[1] = access units;
+ *               reserved[2] = sequence breaks << 32 | dropped packets.  A sequence break is a pair of table neighbours, both
+ *               accepted, with seq_p != (seq_{p-1} + 1) & 0xFFFF.  A dropped packet is an accepted packet of which no byte
+ *               reaches the output: an unsupported one, or an FU of a chain that is not whole (an empty fragment of a whole
+ *               chain is part of its NAL and is not counted).
+ *               On any fault error = HBS_E_ARG and reserved[0] = 1 + the lowest faulty packet; the other counts mean nothing
+ *               (they are 0).  Else HBS_E_CAPACITY when, with a d_out, the output exceeds out_cap, the NALs exceed nal_cap or,
+ *               with a d_au_ts_out, the access units exceed au_cap; the counts are right then.  On either error nothing but
+ *               the summary is written.
+ * Refused with HBS_E_ARG at once, before anything is written: params NULL or out of range (payload_type outside 0..127,
+ * startcode_bytes not 3 or 4, unknown flags), n_packets above 2^32 - 1, out_cap above 2^46 with a d_out, missing or misaligned
+ * pointers (with packets: the two tables, and d_in when in_bytes is not 0).
+ * Nothing outside [d_out, d_out + output bytes), the first nal_count entries of d_index_out and d_nal_au_out, the first
+ * reserved[1] entries of d_au_ts_out and the summary is stored; no load touches a 16-byte granule that holds no byte of
+ * d_in[0, in_bytes); no host synchronisation; scratch comes from the context's workspace and is sized by n_packets, nal_cap
+ * and out_cap alone (44 bytes a packet, 24 bytes a piece of at most n_packets + min(nal_cap, out_cap / (startcode_bytes + 2))
+ * pieces, 8 bytes per 64 KiB of out_cap).
+ * Alignment: d_in, d_out, d_summary 16 bytes; d_pkt_off, d_pkt_size, d_index_out, d_au_ts_out 8 bytes; d_nal_au_out 4 bytes.
+ * STATED LIMITS: no reordering and no duplicate removal beyond the table's order (a duplicate comes out twice and counts as a
+ * break); no DONL fields, no interleaving; no PACI; a packet that is not this stream's and lies inside a chain breaks the
+ * chain; no RTCP; no SRTP.
+ *
+ * Host side, plain C, no GPU involved.
+ * hbs_rtp_frames_host walks an RFC 4571 byte stream bytes[0, n): a big-endian 16-bit length, then a packet of that many bytes,
+ * and so on.  It stops in front of the first incomplete frame; no length is trusted before it is bounded.  Returns the number
+ * of whole frames and fills the offset / size (of the packets, the length fields left out) of the first `cap` of them;
+ * *used_out = the bytes the whole frames take, where the next read continues.  off_out, size_out and used_out may be NULL.
+ */
+typedef struct hbs_rtp_unpack_params {   /* HOST memory, 16 bytes */
+    int32_t  payload_type;      /* 0 .. 127: packets of another type are not this stream's */
+    int32_t  startcode_bytes;   /* 3: 00 00 01, 4: 00 00 00 01 in front of every NAL */
+    uint32_t flags;             /* HBS_RTPU_* */
+    uint32_t ssrc;              /* read with HBS_RTPU_MATCH_SSRC */
+} hbs_rtp_unpack_params;
+#define HBS_RTPU_MATCH_SSRC 1u  /* packets whose ssrc differs from params->ssrc are not this stream's */
+
+int hbs_rtp_unpack(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
+                   const uint64_t* d_pkt_off, const uint64_t* d_pkt_size, uint64_t n_packets,
+                   const hbs_rtp_unpack_params* params,
+                   uint8_t* d_out, uint64_t out_cap,
+                   hbs_nal_entry* d_index_out /* optional */, uint32_t* d_nal_au_out /* optional */, uint64_t nal_cap,
+                   uint64_t* d_au_ts_out /* optional */, uint64_t au_cap,
+                   hbs_summary* d_summary);
+uint64_t hbs_rtp_frames_host(const uint8_t* bytes, uint64_t n, uint64_t* off_out, uint64_t* size_out, uint64_t cap,
+                             uint64_t* used_out);
 
 /*
  * K4: header parse, one NAL per lane (64 per wavefront), over the RBSP arena and index that
