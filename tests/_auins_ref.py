@@ -6,6 +6,7 @@ import numpy as np
 from hevcbitstream_amd.api import ACCESS_UNIT, COMPACT, NAL_ENTRY, PARSED
 from tests import _au_ref as A
 from tests import _filter_ref as F
+from tests._segments import materialise
 
 AUD, PARAM_SETS, PARAM_SETS_FIRST = 1, 2, 4
 E_ARG, E_CAPACITY = -3, -4
@@ -61,16 +62,25 @@ def empty(n_nals, error=0, aus=0):
 
 def au_insert(stream, index, parsed, au, nal_au, first_au, au_count, flags, out_cap=None, index_cap=None):
     """-> (out, index_out, nal_src, nal_au_out, au_out, summary).  out_cap None: a plan (no capacity is looked at); index_cap
-    None: no per-NAL table is given.  On an error the outputs are empty."""
+    None: no per-NAL table is given.  On an error the outputs are empty.  The plan below and the bytes of its segments."""
     stream = np.asarray(stream, dtype=np.uint8)
+    segs, index_out, nal_src, nal_au_out, au_out, s = plan(len(stream), index, parsed, au, nal_au, first_au, au_count, flags, out_cap, index_cap)
+    if s["error"] or not segs:
+        return (np.zeros(0, dtype=np.uint8), index_out, nal_src, nal_au_out, au_out, s)
+    return materialise(segs, s["stream_bytes"], stream), index_out, nal_src, nal_au_out, au_out, s
+
+
+def plan(stream_bytes, index, parsed, au, nal_au, first_au, au_count, flags, out_cap=None, index_cap=None):
+    """au_insert without the stream's bytes -> (segments of tests/_segments.py: verbatim ranges and literals, index_out, nal_src,
+    nal_au_out, au_out, summary)"""
     n, m = len(index), len(au)
     if n == 0 or m == 0:
-        return empty(n)
-    if not F.consistent(index, len(stream)) or not tables_tile(index, au, nal_au):
-        return empty(n, E_ARG)
+        return ([],) + empty(n)[1:]
+    if not F.consistent(index, stream_bytes) or not tables_tile(index, au, nal_au):
+        return ([],) + empty(n, E_ARG)[1:]
     a0, cnt = clip(m, first_au, au_count)
     if cnt == 0:
-        return empty(n)
+        return ([],) + empty(n)[1:]
     typ, rc = parsed["nal_unit_type"].tolist(), parsed["rc"].tolist()
     start, end = index["start"].tolist(), index["end"].tolist()
     rlen, status = index["rbsp_len"].tolist(), index["status"].tolist()
@@ -87,7 +97,14 @@ def au_insert(stream, index, parsed, au, nal_au, first_au, au_count, flags, out_
     k0, ub0 = A_first[a0], A_begin[a0]
     kend = A_first[a0 + cnt - 1] + A_count[a0 + cnt - 1]
 
-    segs, cursor = [], ub0                     # the output: verbatim runs and what is inserted between them
+    segs, cursor, at = [], ub0, 0              # the output: verbatim runs and what is inserted between them; bytes laid out
+
+    def put(seg):
+        nonlocal at
+        length = seg[2] if seg[0] == "copy" else len(seg[1])          # ("copy", src, length) or ("lit", bytes) -> with the offset
+        if length:
+            segs.append((seg[0], at) + seg[1:])
+        at += length
     pos = nals = rbsp = 0                      # bytes, NALs, rbsp_len inserted so far
     auds = sets = 0
     ins = []                                   # inserted entries: (j, start, end, rbsp_off, rbsp_len, status, src, au)
@@ -110,7 +127,7 @@ def au_insert(stream, index, parsed, au, nal_au, first_au, au_count, flags, out_
                 if 0 <= q < f:
                     items.append(q)
         if items:
-            segs.append(stream[cursor:point])
+            put(("copy", cursor, point - cursor))
             cursor = point
             j = f - k0 + nals + (1 if has_aud else 0)
             o = point - ub0 + pos
@@ -118,13 +135,13 @@ def au_insert(stream, index, parsed, au, nal_au, first_au, au_count, flags, out_
             for q in items:
                 if q is None:
                     lit = aud_nal(A_tid[a], A_st[a])
-                    segs.append(np.frombuffer(lit, dtype=np.uint8))
+                    put(("lit", lit))
                     ins.append((j, o + 4, o + 7, r, 3, 0, NONE, i))
                     size, rl = 7, 3
                     auds += 1
                 else:
-                    segs.append(np.frombuffer(b"\x00\x00\x00\x01", dtype=np.uint8))
-                    segs.append(stream[start[q]:end[q]])
+                    put(("lit", b"\x00\x00\x00\x01"))
+                    put(("copy", start[q], end[q] - start[q]))
                     size, rl = 4 + end[q] - start[q], rlen[q]
                     ins.append((j, o + 4, o + size, r, rl, status[q] & ~ST_UNTERMINATED, q, i))
                     sets += 1
@@ -134,15 +151,14 @@ def au_insert(stream, index, parsed, au, nal_au, first_au, au_count, flags, out_
                 in_n[i] += 1
                 in_r[i] += rl
             pos, nals, rbsp = pos + in_b[i], nals + in_n[i], rbsp + in_r[i]
-    segs.append(stream[cursor:A_end[a0 + cnt - 1]])
-    out = np.concatenate(segs)
+    put(("copy", cursor, A_end[a0 + cnt - 1] - cursor))
     M = kend - k0 + nals
     total_rbsp = rsum[kend] - rsum[k0] + rbsp
-    s = dict(nal_count=M, nal_found=n, rbsp_bytes=total_rbsp, stream_bytes=len(out), stop_reason=-1 if M else 0, error=0,
+    s = dict(nal_count=M, nal_found=n, rbsp_bytes=total_rbsp, stream_bytes=at, stop_reason=-1 if M else 0, error=0,
              reserved=[auds, sets, cnt])
-    if (out_cap is not None and len(out) > out_cap) or (out_cap is not None and index_cap is not None and M > index_cap):
+    if (out_cap is not None and at > out_cap) or (out_cap is not None and index_cap is not None and M > index_cap):
         e = empty(n)
-        return e[:5] + (dict(s, error=E_CAPACITY),)
+        return ([],) + e[1:5] + (dict(s, error=E_CAPACITY),)
 
     ex_b, ex_n, ex_r, own = (np.array(x, dtype=np.int64) for x in (ex_b, ex_n, ex_r, own))
     in_b, in_n, in_r = (np.array(x, dtype=np.int64) for x in (in_b, in_n, in_r))
@@ -177,7 +193,7 @@ def au_insert(stream, index, parsed, au, nal_au, first_au, au_count, flags, out_
         nal_src[jj], nal_au_out[jj] = t[:, 6], t[:, 7]
     if M:
         index_out["status"][-1] |= ST_UNTERMINATED
-    return out, index_out, nal_src, nal_au_out, au_out, s
+    return segs, index_out, nal_src, nal_au_out, au_out, s
 
 
 def gather_records(parsed, compact, nal_src, au_out, nal_au_out):
@@ -219,32 +235,22 @@ def nal(type, size=None, layer=0, tid1=1, rc=None, first=0, stype=1, lsb=0, dep=
                 lsb=lsb, dep=dep, sc=sc, zeros=zeros, junk=junk)
 
 
-def build(rng, nals, lead_junk=0, tail=b""):
-    """nals: a list of nal() dicts in stream order -> (stream, index, parsed, compact, au, nal_au): the bytes (payloads without
-    a zero byte, so rbsp_len = the size and the end is where the next unit begins), the index a scan of them gives, the records a
-    parse would give, and the AUs of tests/_au_ref.py over them."""
+def gap_bytes(d, k):
+    """bytes in front of NAL k's payload: zeros, junk behind a 00 00 00 (not in front of NAL 0), the start code"""
+    return d["zeros"] + (3 + d["junk"] if d["junk"] and k else 0) + (4 if d["sc"] == 4 else 3)
+
+
+def tables(nals, lead_junk=0, tail=False):
+    """nals: nal() dicts with an explicit size -> (stream bytes, index, parsed, compact, au, nal_au): what build() returns
+    behind the bytes, from the sizes alone"""
     n = len(nals)
-    parts, at = [], 0
     index, parsed, compact = np.zeros(n, dtype=NAL_ENTRY), np.zeros(n, dtype=PARSED), np.zeros(n, dtype=COMPACT)
     parsed["struct_off"] = A.NO_SLOT
-    if lead_junk:
-        parts.append(rng.integers(1, 256, size=lead_junk, dtype=np.uint8).tobytes())
-        at += lead_junk
-    roff = 0
+    at, roff = lead_junk, 0
     for k, d in enumerate(nals):
-        gap = b"\x00" * d["zeros"]
-        if d["junk"] and k:                  # junk belongs to the next unit when it follows the 00 00 00 that ended the NAL in front
-            gap += b"\x00\x00\x00" + rng.integers(4, 256, size=d["junk"], dtype=np.uint8).tobytes()
-        gap += b"\x00\x00\x00\x01" if d["sc"] == 4 else b"\x00\x00\x01"
-        size = int(rng.integers(3, 40)) if d["size"] is None else d["size"]
-        pay = rng.integers(1, 256, size=size, dtype=np.uint8)
-        hdr = [(d["type"] << 1) | (d["layer"] >> 5), ((d["layer"] & 31) << 3) | d["tid1"]]
-        pay[:min(size, 2)] = hdr[:min(size, 2)]
-        if size >= 2 and pay[1] == 0:
-            pay[1] = 1
-        parts += [gap, pay.tobytes()]
-        index[k] = (at + len(gap), at + len(gap) + size, roff, size, 0)
-        at += len(gap) + size
+        gap, size = gap_bytes(d, k), d["size"]
+        index[k] = (at + gap, at + gap + size, roff, size, 0)
+        at += gap + size
         roff += size
         parsed[k] = (d["rc"], d["type"], d["layer"], d["tid1"], A.NO_SLOT, 0, 0)
         compact["first_slice_segment_in_pic_flag"][k] = d["first"]
@@ -253,8 +259,39 @@ def build(rng, nals, lead_junk=0, tail=b""):
         compact["slice_pic_order_cnt_lsb"][k] = d["lsb"]
     if n:
         index["status"][-1] = ST_UNTERMINATED if not tail else 0
-    stream = np.frombuffer(b"".join(parts) + tail, dtype=np.uint8).copy()
     au, nal_au, _, _ = A.access_units(index, parsed, compact, None, SPS_OFF)
+    return at, index, parsed, compact, au, nal_au
+
+
+def header_bytes(d):
+    """the two bytes of a NAL unit header"""
+    return [(d["type"] << 1) | (d["layer"] >> 5), ((d["layer"] & 31) << 3) | d["tid1"]]
+
+
+def build(rng, nals, lead_junk=0, tail=b""):
+    """nals: a list of nal() dicts in stream order -> (stream, index, parsed, compact, au, nal_au): the bytes (payloads without
+    a zero byte, so rbsp_len = the size and the end is where the next unit begins), the index a scan of them gives, the records a
+    parse would give, and the AUs of tests/_au_ref.py over them (tables(), once the sizes are drawn)."""
+    parts, sized = [], []
+    if lead_junk:
+        parts.append(rng.integers(1, 256, size=lead_junk, dtype=np.uint8).tobytes())
+    for k, d in enumerate(nals):
+        gap = b"\x00" * d["zeros"]
+        if d["junk"] and k:                  # junk belongs to the next unit when it follows the 00 00 00 that ended the NAL in front
+            gap += b"\x00\x00\x00" + rng.integers(4, 256, size=d["junk"], dtype=np.uint8).tobytes()
+        gap += b"\x00\x00\x00\x01" if d["sc"] == 4 else b"\x00\x00\x01"
+        size = int(rng.integers(3, 40)) if d["size"] is None else d["size"]
+        pay = rng.integers(1, 256, size=size, dtype=np.uint8)
+        hdr = header_bytes(d)
+        pay[:min(size, 2)] = hdr[:min(size, 2)]
+        if size >= 2 and pay[1] == 0:
+            pay[1] = 1
+        assert len(gap) == gap_bytes(d, k)
+        parts += [gap, pay.tobytes()]
+        sized.append(dict(d, size=size))
+    total, index, parsed, compact, au, nal_au = tables(sized, lead_junk, bool(tail))
+    stream = np.frombuffer(b"".join(parts) + tail, dtype=np.uint8).copy()
+    assert len(stream) == total + len(tail)
     return stream, index, parsed, compact, au, nal_au
 
 

@@ -3,6 +3,8 @@ a receiver that turns packets back into NALs, and a vectorised restatement for b
 infrastructure: numpy only, no GPU, nothing of the library."""
 import numpy as np
 
+from tests._segments import materialise, run_of
+
 NAL_ENTRY = np.dtype([("start", "<u8"), ("end", "<u8"), ("rbsp_off", "<u8"), ("rbsp_len", "<u4"), ("status", "<i4")])
 PARAMS = np.dtype([("max_payload", "<i4"), ("payload_type", "<i4"), ("framing", "<i4"), ("flags", "<u4"), ("ssrc", "<u4"),
                    ("seq", "<u4"), ("ts_base", "<u4"), ("ts_step", "<u4")])
@@ -67,11 +69,17 @@ def nal_to_packets(nal, prm, marker, j, ts):
 
 def offending(stream, index, nal_au, n_aus, pts, k):
     """is NAL k malformed?  -> (bad, its AU number relative to the first NAL's)"""
+    s = int(index["start"][k])
+    return offending_of(len(stream), int(stream[s]) if s < len(stream) else 0, index, nal_au, n_aus, pts, k)
+
+
+def offending_of(stream_bytes, first_byte, index, nal_au, n_aus, pts, k):
+    """offending() from the stream's size and the NAL's first byte"""
     s, e = int(index["start"][k]), int(index["end"][k])
     prev_end = int(index["end"][k - 1]) if k else 0
-    bad = s > e or e > len(stream) or s < prev_end
+    bad = s > e or e > stream_bytes or s < prev_end
     if not bad:
-        bad = e - s < 2 or ((int(stream[s]) >> 1) & 63) >= 48
+        bad = e - s < 2 or ((first_byte >> 1) & 63) >= 48
     a = 0
     if nal_au is not None:
         au = int(nal_au[k])
@@ -83,21 +91,54 @@ def offending(stream, index, nal_au, n_aus, pts, k):
     return bad, a
 
 
-def pack(stream, index, nal_au, n_aus, pts, prm, out_cap=None):
-    """-> (out uint8 array, nal_off uint64[n + 1], nal_packet uint64[n + 1], summary dict); on an error out is empty and the
-    tables are None"""
+def nal_headers(stream, index):
+    """the first two bytes of every NAL, (n, 2) uint8: all of the stream's contents that plan() needs (0 where the stream ends)"""
+    stream = np.asarray(stream, dtype=np.uint8)
+    s = index["start"].astype(np.int64)
+    padded = np.concatenate([stream, np.zeros(2, dtype=np.uint8)])
+    at = np.clip(s, 0, len(stream))
+    return np.stack([padded[at], padded[at + 1]], axis=1) if len(index) else np.zeros((0, 2), dtype=np.uint8)
+
+
+def fu_run_heads(prm, j, ts, hdr2):
+    """the headers of the FU packets of a NAL that are neither its first nor its last, without a loop: packet i of the run is
+    the call's (j + i)-th packet -> a function (lo, hi) -> (hi - lo, framing + 15) uint8"""
+    fr = prm["framing"]
+    fixed = header(prm, False, 0, ts) + bytes([(hdr2[0] & 0x81) | 0x62, hdr2[1], (hdr2[0] >> 1) & 63])
+    if fr:
+        fixed = (12 + prm["max_payload"]).to_bytes(fr, "big") + fixed
+
+    def heads(lo, hi):
+        h = np.tile(np.frombuffer(fixed, dtype=np.uint8), (hi - lo, 1))
+        seq = (prm["seq"] + j + np.arange(lo, hi, dtype=np.int64)) & 0xFFFF
+        h[:, fr + 2], h[:, fr + 3] = seq >> 8, seq & 0xFF
+        return h
+    return heads
+
+
+def plan(stream_bytes, hdr, index, nal_au, n_aus, pts, prm, out_cap=None):
+    """pack() without the stream's bytes; hdr: nal_headers() -> (segments of tests/_segments.py, nal_off uint64[n + 1],
+    nal_packet uint64[n + 1], summary dict); on an error there are no segments and the tables are None.  A NAL of one packet is
+    a literal header and a verbatim range; a fragmented NAL is its first and its last packet in that form (their headers from
+    nal_to_packets on a NAL of two or three fragments with the same header bytes, the same last fragment and the same packet numbers)
+    and, between them, one strided run of full packets."""
     n, mp, fr = len(index), prm["max_payload"], prm["framing"]
     summary = dict(nal_count=0, nal_found=n, rbsp_bytes=0, stream_bytes=0, stop_reason=0, error=0, reserved=[0, 0, 0])
     rel = []
     for k in range(n):
-        bad, a = offending(stream, index, nal_au, n_aus, pts, k)
+        bad, a = offending_of(stream_bytes, int(hdr[k][0]), index, nal_au, n_aus, pts, k)
         if bad:
             summary["error"], summary["reserved"] = E_ARG, [k + 1, 0, 0]
-            return np.zeros(0, dtype=np.uint8), None, None, summary
+            return [], None, None, summary
         rel.append(a)
-    parts, nal_off, nal_packet, at, j, carried, fus = [], [], [], 0, 0, 0, 0
+    segs, nal_off, nal_packet, at, j, carried, fus = [], [], [], 0, 0, 0, 0
+    F, P = mp - 3, fr + 12 + mp
+
+    def framed(p, head):
+        return (len(p).to_bytes(fr, "big") if fr else b"") + p[:head]
     for k in range(n):
-        nal = stream[int(index["start"][k]):int(index["end"][k])].tobytes()
+        S, L = int(index["start"][k]), int(index["end"][k]) - int(index["start"][k])
+        h2 = bytes([int(hdr[k][0]), int(hdr[k][1])])
         if k == n - 1:
             marker = not prm["flags"] & OPEN_END
         else:
@@ -105,30 +146,54 @@ def pack(stream, index, nal_au, n_aus, pts, prm, out_cap=None):
         ts = prm["ts_base"] + (int(pts[rel[k]]) if pts is not None else rel[k] * prm["ts_step"])
         nal_off.append(at)
         nal_packet.append(j)
-        packets = nal_to_packets(nal, prm, marker, j, ts)
-        assert len(packets) == nal_packets(len(nal), mp)
-        for p in packets:
-            assert len(p) - 12 <= mp
-            parts.append(len(p).to_bytes(fr, "big") + p if fr else p)
-            at += fr + len(p)
-        j += len(packets)
-        carried += len(nal)
-        fus += len(nal) > mp
+        count = nal_packets(L, mp)
+        if count == 1:
+            (p,) = nal_to_packets(h2 + bytes(L - 2), prm, marker, j, ts)
+            segs += [("lit", at, framed(p, 12)), ("copy", at + fr + 12, S, L)]
+            at += fr + 12 + L
+        else:
+            last = L - 2 - (count - 1) * F
+            assert 1 <= last <= F
+            mid = min(count, 3) - 2                            # (a body of F + 1 bytes is one packet: three fragments where the NAL has three or more)
+            packets = nal_to_packets(h2 + bytes((1 + mid) * F + last), prm, marker, j, ts)
+            first_p = packets[0]
+            last_p = nal_to_packets(h2 + bytes((1 + mid) * F + last), prm, marker, j + count - 2 - mid, ts)[-1]
+            assert len(packets) == 2 + mid
+            assert len(first_p) == 12 + mp and len(last_p) == 15 + last
+            segs += [("lit", at, framed(first_p, 15)), ("copy", at + fr + 15, S + 2, F)]
+            if count > 2:
+                segs.append(("run", at + P, run_of(count - 2, P, fr + 15, F, S + 2 + F, fu_run_heads(prm, j + 1, ts, h2))))
+            o = at + (count - 1) * P
+            segs += [("lit", o, framed(last_p, 15)), ("copy", o + fr + 15, S + 2 + (count - 1) * F, last)]
+            at = o + fr + 15 + last
+        j += count
+        carried += L
+        fus += L > mp
     summary.update(nal_count=j, rbsp_bytes=carried, stream_bytes=at, reserved=[0, j, fus])
     tabs = np.array(nal_off + [at], dtype=np.uint64), np.array(nal_packet + [j], dtype=np.uint64)
     if out_cap is not None and at > out_cap:
         summary["error"] = E_CAPACITY
+        return [], None, None, summary
+    return segs, tabs[0], tabs[1], summary
+
+
+def pack(stream, index, nal_au, n_aus, pts, prm, out_cap=None):
+    """-> (out uint8 array, nal_off uint64[n + 1], nal_packet uint64[n + 1], summary dict); on an error out is empty and the
+    tables are None.  plan() and the bytes of its segments."""
+    segs, nal_off, nal_packet, summary = plan(len(stream), nal_headers(stream, index), index, nal_au, n_aus, pts, prm, out_cap)
+    if summary["error"]:
         return np.zeros(0, dtype=np.uint8), None, None, summary
-    return np.frombuffer(b"".join(parts), dtype=np.uint8), tabs[0], tabs[1], summary
+    return materialise(segs, summary["stream_bytes"], stream), nal_off, nal_packet, summary
 
 
 def packet_offsets(nal_off, nal_packet, prm):
-    """where every packet begins, and the total: all packets of a NAL but its last take framing + 12 + max_payload bytes"""
-    out = []
-    for k in range(len(nal_off) - 1):
-        for i in range(int(nal_packet[k + 1] - nal_packet[k])):
-            out.append(int(nal_off[k]) + i * (prm["framing"] + 12 + prm["max_payload"]))
-    return np.array(out + [int(nal_off[-1])], dtype=np.uint64)
+    """where every packet begins, and the total: all packets of a NAL but its last take framing + 12 + max_payload bytes
+    (np.repeat arithmetic; tests/test_big_checks.py holds it against the loop over the NALs and their packets)"""
+    nal_off, nal_packet = np.asarray(nal_off, dtype=np.uint64), np.asarray(nal_packet, dtype=np.uint64)
+    count = np.diff(nal_packet).astype(np.int64)
+    within = np.arange(int(nal_packet[-1]), dtype=np.uint64) - np.repeat(nal_packet[:-1], count)
+    off = np.repeat(nal_off[:-1], count) + within * np.uint64(prm["framing"] + 12 + prm["max_payload"])
+    return np.concatenate([off, nal_off[-1:]]).astype(np.uint64)
 
 
 def read_packet(pkt):

@@ -2,6 +2,8 @@
 specification), with a bitwise CRC.  Test infrastructure: numpy only, no GPU, nothing of the library."""
 import numpy as np
 
+from tests._segments import materialise, run_of
+
 ACCESS_UNIT = np.dtype([("first_nal", "<u8"), ("unit_begin", "<u8"), ("unit_end", "<u8"), ("nal_count", "<u4"), ("vcl_count", "<u4"),
                         ("first_vcl", "<u4"), ("nal_unit_type", "<i4"), ("temporal_id_plus1", "<i4"), ("pic_order_cnt", "<i4"),
                         ("poc_lsb", "<i4"), ("slice_types", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
@@ -146,41 +148,95 @@ def frame(p188, B):
     return (b"\x00" * 4 if B == 192 else b"") + p188 + (b"\x00" * 16 if B == 204 else b"")
 
 
-def mux(stream, au, pts, dts, prm, out_cap=None):
-    """-> (out uint8 array, au_packet uint32 array of n + 1, summary dict).  stream: bytes-like; au: a table with unit_begin,
-    unit_end, flags; pts / dts: None or one value per AU; out_cap None: large enough (and the plan's summary)."""
-    data = bytes(stream)
+def es_run_heads(prm, cc):
+    """the headers of the packets of an AU that are neither its first nor its last (184 ES bytes each, no adaptation field),
+    without a loop: packet i of the run has the continuity counter (cc + i) & 15 -> a function (lo, hi) -> (hi - lo, 4 or 8) uint8"""
+    B, pid = prm["packet_bytes"], prm["pid"]
+    lead = 4 if B == 192 else 0
+    fixed = np.frombuffer(bytes(lead) + bytes([0x47, pid >> 8, pid & 0xFF, 0x10]), dtype=np.uint8)
+
+    def heads(lo, hi):
+        h = np.tile(fixed, (hi - lo, 1))
+        h[:, lead + 3] = 0x10 | ((cc + np.arange(lo, hi, dtype=np.int64)) & 15)
+        return h
+    return heads
+
+
+def plan(stream_bytes, au, pts, dts, prm, out_cap=None):
+    """mux() without the stream's bytes -> (segments of tests/_segments.py, au_packet uint32 array of n + 1, summary dict).  A PSI
+    packet is a literal; an AU is its first and its last packet, each a literal front (from au_to_packets on an ES of zeros
+    with the same length modulo 16 full packets, so the same stuffing and the same continuity counters) and a verbatim range,
+    and between them one strided run of full packets."""
     n, B, flags = len(au), prm["packet_bytes"], prm["flags"]
-    packets, au_packet = [], []
-    es_packets = pairs = es_bytes = 0
+    lead, trail = bytes(4 if B == 192 else 0), bytes(16 if B == 204 else 0)
+    segs, au_packet = [], []
+    total = es_packets = pairs = es_bytes = 0
     prev_end, bad = 0, 0
+
+    def one(k, p188, es_off, es_len):
+        """packet k: its front as a literal, its last es_len bytes from the stream"""
+        o = k * B
+        if es_len == 0:
+            segs.append(("lit", o, lead + p188 + trail))
+            return
+        segs.append(("lit", o, lead + p188[:188 - es_len]))
+        segs.append(("copy", o + len(lead) + 188 - es_len, es_off, es_len))
+        if trail:
+            segs.append(("lit", o + 188, trail))
     for a in range(n):
         b, e, irap = int(au["unit_begin"][a]), int(au["unit_end"][a]), bool(int(au["flags"][a]) & AU_IRAP)
         p = int(pts[a]) if pts is not None else NO_TIME
         d = int(dts[a]) if dts is not None else NO_TIME
-        ok = b <= e <= len(data) and b >= prev_end
+        ok = b <= e <= stream_bytes and b >= prev_end
         ok = ok and (p == NO_TIME or p <= MASK33) and (d == NO_TIME or (d <= MASK33 and p != NO_TIME))
         prev_end = e
         if not ok:
             bad = bad or a + 1
             continue
         if not flags & NO_PSI and (a == 0 or (flags & PSI_AT_IRAP and irap)):
-            packets += list(psi(prm, pairs))
+            for q in psi(prm, pairs):
+                segs.append(("lit", total * B, frame(q, B)))
+                total += 1
             pairs += 1
-        au_packet.append(len(packets))
-        mine = au_to_packets(data[b:e], p, d, irap, prm, prm["cc_es"] + es_packets)
-        packets += mine
-        es_packets += len(mine)
-        es_bytes += e - b
-    total = len(packets)
+        au_packet.append(total)
+        E, f = e - b, time_fields(p, d)
+        pcr = bool(flags & PCR) and f != 0
+        N = au_packets(E, f, pcr)
+        cc = prm["cc_es"] + es_packets
+        mine = au_to_packets(bytes(E - 184 * 16 * ((N - 2) // 16) if N > 2 else E), p, d, irap, prm, cc)
+        assert (N - len(mine)) % 16 == 0 and len(mine) <= 18
+        if N == 1:
+            one(total, mine[0], b, E)
+        else:
+            e1 = 184 - (8 if pcr else 2) - {0: 9, 2: 14, 3: 19}[f]
+            r = E - e1 - (N - 2) * 184
+            assert 1 <= r <= 184
+            one(total, mine[0], b, e1)
+            if N > 2:
+                segs.append(("run", (total + 1) * B, run_of(N - 2, B, len(lead) + 4, 184, b + e1, es_run_heads(prm, cc + 1), trail)))
+            one(total + N - 1, mine[-1], e - r, r)
+        total += N
+        es_packets += N
+        es_bytes += E
     s = dict(nal_count=total, nal_found=n, rbsp_bytes=es_bytes, stream_bytes=total * B, stop_reason=0, error=0, reserved=[0, es_packets, pairs])
     if bad:
         s.update(error=E_ARG, reserved=[bad, None, None], nal_count=None, rbsp_bytes=None, stream_bytes=None)
     elif out_cap is not None and out_cap < total * B:
         s["error"] = E_CAPACITY
     if s["error"]:
-        return np.zeros(0, np.uint8), np.zeros(0, np.uint32), s
-    return (np.frombuffer(b"".join(frame(p, B) for p in packets), dtype=np.uint8), np.array(au_packet + [total], dtype=np.uint32), s)
+        return [], np.zeros(0, np.uint32), s
+    return segs, np.array(au_packet + [total], dtype=np.uint32), s
+
+
+def mux(stream, au, pts, dts, prm, out_cap=None):
+    """-> (out uint8 array, au_packet uint32 array of n + 1, summary dict).  stream: bytes-like; au: a table with unit_begin,
+    unit_end, flags; pts / dts: None or one value per AU; out_cap None: large enough (and the plan's summary).  plan() and the
+    bytes of its segments."""
+    data = bytes(stream)
+    segs, au_packet, s = plan(len(data), au, pts, dts, prm, out_cap)
+    if s["error"]:
+        return np.zeros(0, np.uint8), au_packet, s
+    return materialise(segs, s["stream_bytes"], data), au_packet, s
 
 
 def mux_one_packet_aus(stream, au, prm):
