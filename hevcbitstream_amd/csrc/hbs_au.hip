@@ -467,8 +467,8 @@ __global__ __launch_bounds__(256) void k_aukeep_mask(AuKeepArgs a)
 hipError_t launch_access_units(const AuArgs& a, hipStream_t st)
 {
     const uint64_t blocks = (a.n_nals + kAuNalsPerBlock - 1) / kAuNalsPerBlock;
-    hipError_t e = hipSuccess;
-    if (a.ev_begin) { e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) {
         hipLaunchKernelGGL(k_au_digest, dim3((unsigned)blocks), dim3(kT), 0, st, a);
         hipLaunchKernelGGL(k_au_scan1, dim3(1), dim3(kT), 0, st, a, blocks);
@@ -481,10 +481,7 @@ hipError_t launch_access_units(const AuArgs& a, hipStream_t st)
         hipLaunchKernelGGL(k_au_write, dim3((unsigned)blocks), dim3(kT), 0, st, a);
         if (blocks > 1) hipLaunchKernelGGL(k_au_fix, dim3((unsigned)((blocks - 1 + 255) / 256)), dim3(256), 0, st, a, blocks);
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (a.ev_end) e = hipEventRecord(a.ev_end, st);
-    return e;
+    return end_launches(a.ev_end, st);
 }
 
 hipError_t launch_au_keep(const AuKeepArgs& a, hipStream_t st)

@@ -17,7 +17,6 @@ constexpr int kAuinsNalsPerBlock = 2048;            /* NAL side: 256 lanes x 8 c
 constexpr int kAuinsAusPerBlock = 256;              /* AU side: one AU a lane                                        */
 constexpr uint32_t kAuinsAudBytes = 7;
 constexpr uint32_t kAuinsFlags = HBS_AUINS_AUD | HBS_AUINS_PARAM_SETS | HBS_AUINS_PARAM_SETS_FIRST;
-constexpr uint64_t kAuinsOutCapMax = 1ull << 46;    /* out_cap sizes the copy's grid and 8 bytes a tile of scratch   */
 
 /* primary_pic_type of the AUD in front of an AU whose independent slices have the types in slice_types (bit t: type t) */
 HBS_HD uint32_t auins_pic_type(uint32_t slice_types)

@@ -6,7 +6,7 @@
  * of NALs costs its lane the same.
  *
  *   k_auins_nals        NAL side, positions 0 .. n_nals: checks the index entry and d_nal_au[k]; "the last VPS / SPS / PPS in
- *                       front of position p" is an exclusive max-scan of `number + 1` (DPP wave scans), of which the workgroup
+ *                       front of position p" is an exclusive max-scan of `number + 1` (block_excl_max, hbs_plan.h), of which the workgroup
  *                       leaves its aggregate and, for every p that is an AU's picture NAL (or its end, without a picture), the
  *                       in-workgroup value with that AU; the sum of rbsp_len over the range's NALs
  *   k_auins_nal_scan    one workgroup: the aggregates become what lies in front of each NAL workgroup
@@ -27,7 +27,6 @@
 #include <hip/hip_runtime.h>
 #include "hbs_auins.h"
 #include "hbs_plan.h"
-#include "hbs_wave.h"
 
 namespace hbs {
 namespace {
@@ -35,49 +34,6 @@ namespace {
 constexpr int kT = kPlanLanes;
 constexpr int kPer = kAuinsNalsPerBlock / kT;        /* NALs a lane of the NAL side takes */
 static_assert(kAuinsAusPerBlock == kT, "one AU a lane");
-
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-
-/* inclusive max-scan over the wavefront, with the DPP moves of wave_incl_scan32 (a lane without a source reads 0, the
- * identity: the values are numbers + 1) */
-__device__ __forceinline__ uint32_t wave_incl_max32(uint32_t v)
-{
-    v = umax(v, dpp_or_zero<kDppRowShr1, 0xF>(v));
-    v = umax(v, dpp_or_zero<kDppRowShr2, 0xF>(v));
-    v = umax(v, dpp_or_zero<kDppRowShr4, 0xF>(v));
-    v = umax(v, dpp_or_zero<kDppRowShr8, 0xF>(v));
-    v = umax(v, dpp_or_zero<kDppBcast15, 0xA>(v));
-    v = umax(v, dpp_or_zero<kDppBcast31, 0xC>(v));
-    return v;
-}
-
-/* exclusive max-scan of three fields over the kT lanes of the workgroup; tot: over all of them */
-__device__ __forceinline__ void block_excl_max3(const uint32_t v[3], uint32_t ex[3], uint32_t tot[3])
-{
-    __shared__ uint32_t s_w[kT / 64][3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t e[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const uint32_t inc = wave_incl_max32(v[q]);
-        e[q] = from_prev_lane(inc, 0u);
-        if (lane == 63) s_w[wave][q] = inc;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        uint32_t pre = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < kT / 64; ++w) {
-            const uint32_t x = s_w[w][q];
-            if (w < wave) pre = umax(pre, x);
-            all = umax(all, x);
-        }
-        ex[q] = umax(pre, e[q]);
-        tot[q] = all;
-    }
-    __syncthreads();
-}
 
 /* the NALs of the range as the AU table names them: compared with, never used as an index before k_auins_aus has checked it */
 __device__ __forceinline__ void range_nals(const AuinsArgs& a, uint64_t& k0, uint64_t& k1)
@@ -122,7 +78,7 @@ __global__ __launch_bounds__(kT) void k_auins_nals(AuinsArgs a)
     }
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
     uint32_t cur[3], tot[3];
-    block_excl_max3(m, cur, tot);
+    block_excl_max<uint32_t, 3, kT>(m, cur, tot);
     uint64_t rex[1], rtot[1];
     block_scan<1, kT>(rb, rex, rtot);
     if (threadIdx.x == 0) {
@@ -162,20 +118,20 @@ __global__ __launch_bounds__(kT) void k_auins_nal_scan(AuinsArgs a, uint64_t blo
         uint32_t acc[3] = {0, 0, 0};
         for (int i = 0; i < kPlanPer && i0 + i < blocks; ++i)
 #pragma unroll
-            for (int q = 0; q < 3; ++q) acc[q] = umax(acc[q], a.last_n[(i0 + i) * 4 + q]);
+            for (int q = 0; q < 3; ++q) acc[q] = max(acc[q], a.last_n[(i0 + i) * 4 + q]);
         uint32_t cur[3], tot[3];
-        block_excl_max3(acc, cur, tot);
+        block_excl_max<uint32_t, 3, kT>(acc, cur, tot);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) cur[q] = umax(cur[q], run[q]);
+        for (int q = 0; q < 3; ++q) cur[q] = max(cur[q], run[q]);
         for (int i = 0; i < kPlanPer && i0 + i < blocks; ++i)
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const uint32_t x = a.last_n[(i0 + i) * 4 + q];
                 a.last_n[(i0 + i) * 4 + q] = cur[q];
-                cur[q] = umax(cur[q], x);
+                cur[q] = max(cur[q], x);
             }
 #pragma unroll
-        for (int q = 0; q < 3; ++q) run[q] = umax(run[q], tot[q]);
+        for (int q = 0; q < 3; ++q) run[q] = max(run[q], tot[q]);
     }
     if (threadIdx.x == 0) { a.ctl2[4] = carry[0]; a.ctl2[5] = bad; }
 }
@@ -209,7 +165,7 @@ __global__ __launch_bounds__(kT) void k_auins_aus(AuinsArgs a)
                 const uint32_t* before = a.last_n + p / kAuinsNalsPerBlock * 4;
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
-                    const uint32_t qv = umax(before[t], a.au_q[i * 4 + t]);
+                    const uint32_t qv = max(before[t], a.au_q[i * 4 + t]);
                     if ((uint64_t)qv > p) { bad = true; continue; }          /* (never with tables that tile: nobody wrote au_q) */
                     if (qv == 0 || (uint64_t)qv - 1 >= f) continue;             /* none, or the AU brings its own */
                     const hbs_nal_entry e = a.index[qv - 1];
@@ -383,8 +339,8 @@ hipError_t launch_au_insert(const AuinsArgs& a, hipStream_t st)
 {
     const bool any = a.n_nals && a.n_aus;
     const uint64_t blocks_n = auins_nal_blocks(a.n_nals), blocks_a = auins_au_blocks(a.n_aus);
-    hipError_t e = hipSuccess;
-    if (a.ev_begin) { e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (any) {
         hipLaunchKernelGGL(k_auins_nals, dim3((unsigned)blocks_n), dim3(kT), 0, st, a);
         hipLaunchKernelGGL(k_auins_nal_scan, dim3(1), dim3(kT), 0, st, a, blocks_n);

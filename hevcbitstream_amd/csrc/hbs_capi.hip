@@ -93,6 +93,14 @@ int fail(hbs_ctx* c, hipError_t e, const char* what)
 
 bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
+/* a call whose out_cap sizes its scratch and grid: true, with the error's text, when it asks for more than kOutCapMax */
+bool out_cap_refused(hbs_ctx* c, const void* d_out, uint64_t out_cap)
+{
+    if (!d_out || out_cap <= hbs::kOutCapMax) return false;
+    snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
+    return true;
+}
+
 /* makes `b` hold `bytes` at least.  1: it grew (what it held is gone), 0: it was large enough, < 0: the call's return code */
 int grow(hbs_ctx* c, Buf& b, uint64_t bytes, const char* what)
 {
@@ -651,10 +659,7 @@ int hbs_lenpref_to_annexb(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, in
         snprintf(c->err, sizeof(c->err), "input/output/summary pointers must be 16-byte aligned, sample tables 8-byte aligned");
         return HBS_E_ARG;
     }
-    if (d_out && out_cap > hbs::kLenprefOutCapMax) {
-        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
-        return HBS_E_ARG;
-    }
+    if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::L2aArgs a;
     memset(&a, 0, sizeof(a));
@@ -745,10 +750,7 @@ int hbs_rtp_pack(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
         snprintf(c->err, sizeof(c->err), "stream/output/summary pointers must be 16-byte aligned, index, times and the two tables 8-byte, AU numbers 4-byte");
         return HBS_E_ARG;
     }
-    if (d_out && out_cap > hbs::kRtpOutCapMax) {
-        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
-        return HBS_E_ARG;
-    }
+    if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::RtpArgs a;
     memset(&a, 0, sizeof(a));
@@ -781,10 +783,7 @@ int hbs_rtp_unpack(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
         snprintf(c->err, sizeof(c->err), "input/output/summary pointers must be 16-byte aligned, packet tables, output index and AU times 8-byte, AU numbers 4-byte");
         return HBS_E_ARG;
     }
-    if (d_out && out_cap > hbs::kRtpuOutCapMax) {
-        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
-        return HBS_E_ARG;
-    }
+    if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::RtpuArgs a;
     memset(&a, 0, sizeof(a));
@@ -820,10 +819,7 @@ int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
         snprintf(c->err, sizeof(c->err), "stream/output/index/parsed/AU table/summary pointers must be 16-byte aligned, the output index 8-byte, the per-NAL numbers 4-byte");
         return HBS_E_ARG;
     }
-    if (d_out && out_cap > hbs::kAuinsOutCapMax) {
-        snprintf(c->err, sizeof(c->err), "out_cap sizes the call's scratch and grid: at most 2^46");
-        return HBS_E_ARG;
-    }
+    if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::AuinsArgs a;
     memset(&a, 0, sizeof(a));

@@ -115,6 +115,10 @@ struct Carver {
     }
 };
 
+/* The most a call whose out_cap sizes its scratch and its copy's grid accepts for it (hbs_lenpref_to_annexb, hbs_rtp_pack,
+ * hbs_rtp_unpack, hbs_au_insert): 2^30 tiles of 64 KiB, fewer than 2^45 pieces, so no size wraps */
+constexpr uint64_t kOutCapMax = 1ull << 46;
+
 /* The kernel-choice rule of the automatic mode (hbs_scan.hip launch_scan_extract): the event-sparse
  * kernel handles flagged chunks 64 at a time on one wavefront, so once more than one chunk in
  * kDenseOneIn may hold a zero pair the LDS-image kernel, whose cost does not depend on the data,
@@ -202,6 +206,17 @@ inline hipError_t clear_async(void* p, uint64_t bytes, hipStream_t st)
     const uint64_t want = (bytes / 16u + 255u) / 256u;
     k_clear<0><<<dim3((unsigned)(want < 1 ? 1 : want > 1024 ? 1024 : want)), dim3(256), 0, st>>>(static_cast<uint8_t*>(p), bytes);
     return hipGetLastError();
+}
+/* the two ends of a launcher: the begin event (when non-null) in front of its launches; behind them what they left, then the
+ * end event (when non-null) */
+inline hipError_t begin_launches(hipEvent_t ev_begin, hipStream_t st)
+{
+    return ev_begin ? hipEventRecord(ev_begin, st) : hipSuccess;
+}
+inline hipError_t end_launches(hipEvent_t ev_end, hipStream_t st)
+{
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess || !ev_end ? e : hipEventRecord(ev_end, st);
 }
 #endif
 

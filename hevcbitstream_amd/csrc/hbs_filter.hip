@@ -155,8 +155,8 @@ __global__ __launch_bounds__(kFT) void k_filter_place(FilterArgs a)
 hipError_t launch_filter_annexb(const FilterArgs& a, hipStream_t st)
 {
     const uint64_t blocks = (a.n_nals + kFilterNalsPerBlock - 1) / kFilterNalsPerBlock;
-    hipError_t e = hipSuccess;
-    if (a.ev_begin) { e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_filter_count, dim3((unsigned)blocks), dim3(kFT), 0, st, a);
     hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(kFT), 0, st, a, blocks);
     if (a.t.out && blocks) {

@@ -9,7 +9,6 @@ namespace hbs {
 
 constexpr int kLenprefNalsPerBlock = 2048;           /* forward plan: 256 lanes x 8 consecutive NALs        */
 constexpr int kLenprefSamplesPerBlock = 256;         /* reverse plan: one lane per sample                   */
-constexpr uint64_t kLenprefOutCapMax = 1ull << 46;   /* reverse: out_cap sizes scratch and grid (2^30 tiles, < 2^45 pieces: no size wraps) */
 
 struct A2lArgs {
     uint64_t n;                                       /* stream bytes                                          */

@@ -240,8 +240,8 @@ __global__ __launch_bounds__(kLT) void k_l2a_place(L2aArgs a)
 hipError_t launch_annexb_to_lenpref(const A2lArgs& a, hipStream_t st)
 {
     const uint64_t blocks = (a.n_nals + kLenprefNalsPerBlock - 1) / kLenprefNalsPerBlock;
-    hipError_t e = hipSuccess;
-    if (a.ev_begin) { e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_a2l_count, dim3((unsigned)blocks), dim3(kLT), 0, st, a);
     hipLaunchKernelGGL(k_a2l_scan, dim3(1), dim3(kLT), 0, st, a, blocks);
     if (a.t.out && blocks) {
@@ -254,8 +254,8 @@ hipError_t launch_annexb_to_lenpref(const A2lArgs& a, hipStream_t st)
 hipError_t launch_lenpref_to_annexb(const L2aArgs& a, hipStream_t st)
 {
     const uint64_t blocks = (a.n_samples + kLenprefSamplesPerBlock - 1) / kLenprefSamplesPerBlock;
-    hipError_t e = hipSuccess;
-    if (a.ev_begin) { e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_l2a_count, dim3((unsigned)blocks), dim3(kLT), 0, st, a);
     hipLaunchKernelGGL(k_l2a_scan, dim3(1), dim3(kLT), 0, st, a, blocks);
     if (a.t.out && blocks) {

@@ -47,12 +47,5 @@ inline uint64_t piece_tiles(uint64_t reach)
 /* behind the plan, on its stream: the tile kernel and the copy kernel (nothing when t.tiles is 0) */
 hipError_t copy_pieces(const PieceTable& t, hipStream_t st);
 
-/* the end of a launcher: what its launches left, then the end event (when non-null) */
-inline hipError_t end_launches(hipEvent_t ev_end, hipStream_t st)
-{
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess || !ev_end ? e : hipEventRecord(ev_end, st);
-}
-
 } // namespace hbs
 #endif

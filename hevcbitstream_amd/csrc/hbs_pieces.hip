@@ -15,11 +15,13 @@
  *                    away; kPiecePrefix for one prefix form a table; kPieceLiteral for a literal a piece (piece_lit), whose
  *                    length is staged next to the piece and whose bytes are read where a chunk holds some.
  *
+ * The chunk's loads, realignment and searches are hbs_copy16.h, which the other copies share.
+ *
  * Traffic: the payloads read once and written once, 16 B a piece and 8 B a tile of scratch read.
  */
 #include <hip/hip_runtime.h>
 #include "hbs_pieces.h"
-#include "hbs_wave.h"
+#include "hbs_copy16.h"
 
 namespace hbs {
 namespace {
@@ -37,34 +39,8 @@ __global__ __launch_bounds__(256) void k_piece_tiles(PieceTable a)
 {
     if (a.ctl[0] != 0) return;
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t total = a.ctl[1], pieces = a.ctl[2];
-    const uint64_t used = (total + kTile - 1) / kTile;
-    if (t > used || pieces == 0) return;
-    if (t == used) { a.tile_first[t] = pieces - 1; return; }
-    const uint64_t o = t * kTile;
-    uint64_t lo = 0, hi = pieces - 1;                /* the last piece that begins at or before o */
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (a.piece_out[mid] <= o) lo = mid; else hi = mid - 1;
-    }
-    a.tile_first[t] = lo;
+    tile_first_of<kTile>(a.piece_out, a.ctl[2], a.ctl[1], t, a.tile_first);
 }
-
-/* bytes [sh, sh + 16) of the 32 bytes a:b */
-__device__ __forceinline__ u32x4 realign(u32x4 a, u32x4 b, uint32_t sh)
-{
-    const uint32_t q = sh >> 2, r = sh & 3u;
-    uint32_t x0, x1, x2, x3, x4;
-    if (q == 0)      { x0 = a.x; x1 = a.y; x2 = a.z; x3 = a.w; x4 = b.x; }
-    else if (q == 1) { x0 = a.y; x1 = a.z; x2 = a.w; x3 = b.x; x4 = b.y; }
-    else if (q == 2) { x0 = a.z; x1 = a.w; x2 = b.x; x3 = b.y; x4 = b.z; }
-    else             { x0 = a.w; x1 = b.x; x2 = b.y; x3 = b.z; x4 = b.w; }
-    u32x4 v;
-    v.x = alignbyte(x1, x0, r); v.y = alignbyte(x2, x1, r); v.z = alignbyte(x3, x2, r); v.w = alignbyte(x4, x3, r);
-    return v;
-}
-
-__device__ __forceinline__ u32x4 zero4() { u32x4 z; z.x = z.y = z.z = z.w = 0; return z; }
 
 /* the tile's pieces [j0, j0 + cnt): rel(i) = where piece j0 + i begins, relative to the tile, clamped to [kFar, kTile] (without
  * prefixes to [0, kTile]: where a piece begins in front of the tile says nothing then) */
@@ -89,11 +65,7 @@ struct TilePieces {
     /* the last piece i in [lo, hi] with rel(i) <= r (rel(lo) <= r holds) */
     __device__ __forceinline__ uint32_t find(uint32_t lo, uint32_t hi, uint32_t r) const
     {
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1) >> 1;
-            if (rel(mid) <= (int32_t)r) lo = mid; else hi = mid - 1;
-        }
-        return lo;
+        return last_le(lo, hi, (int32_t)r, [&](uint32_t i) { return rel(i); });
     }
 };
 
@@ -134,6 +106,8 @@ __device__ __forceinline__ void copy_chunk_bytes(const PieceTable& a, const Tile
         }
         if (q < 8) clo |= v << (8 * q); else chi |= v << (8 * (q - 8));
     }
+    /* pack_byte and store_chunk (hbs_copy16.h), written out: with the two calls this path compiles to other code, and the
+     * filter and length-prefix calls then ran 0.4 to 0.9 % longer (profiles/r16/shared_time.txt) */
     uint8_t* dst = a.out + tp.t0 + r;
     if (len == 16) {
         u32x4 c;
@@ -190,12 +164,8 @@ __global__ __launch_bounds__(kCT) void k_piece_copy(PieceTable a)
                 ip[u] = lo;
                 if (tlen - r >= 16 && tp.rel(lo + 1) - (int32_t)r >= 16 &&
                     (!kPrefix || (int32_t)r - tp.rel(lo) >= (kMode == kPieceLiteral ? tp.lit_bytes(lo) : P))) {
-                    const uint64_t s = tp.delta(lo) + t0 + r;
-                    const uint64_t g = s & ~15ull;
-                    sh[u] = (uint32_t)(s & 15u);
                     simple[u] = true;
-                    va[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g));
-                    if (sh[u]) vb[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g + 16));
+                    load16_pair(a.src, tp.delta(lo) + t0 + r, va[u], vb[u], sh[u]);
                 }
             }
         }

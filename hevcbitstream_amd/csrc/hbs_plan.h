@@ -1,6 +1,7 @@
-/* hbs_plan.h -- device-only: the scans of a "count, scan, place" plan (hbs_filter.hip, hbs_lenpref.hip).  A count
- * kernel leaves 8 words a workgroup -- N sums, then a word that says what was wrong -- and one workgroup of kPlanLanes lanes
- * turns the sums into offsets (scan_parts). */
+/* hbs_plan.h -- device-only: the scans of a "count, scan, place" plan (hbs_filter.hip, hbs_lenpref.hip, hbs_ts.hip,
+ * hbs_tsmux.hip, hbs_rtp.hip, hbs_rtpun.hip, hbs_auins.hip): over the lanes of a workgroup the exclusive sums (block_scan) and
+ * the exclusive maxima (block_excl_max).  A count kernel leaves 8 words a workgroup -- N sums, then a word that says what was
+ * wrong -- and one workgroup of kPlanLanes lanes turns the sums into offsets (scan_parts). */
 #ifndef HBS_PLAN_H
 #define HBS_PLAN_H
 
@@ -40,6 +41,41 @@ __device__ __forceinline__ void block_scan(const uint64_t v[N], uint64_t ex[N], 
             all += x;
         }
         ex[q] = pre + inc[q] - v[q];
+        tot[q] = all;
+    }
+    __syncthreads();
+}
+
+/* exclusive maximum of N fields over the NT lanes of a workgroup (0, the identity, for lane 0); tot = the maximum of all */
+template <class T, int N, int NT>
+__device__ __forceinline__ void block_excl_max(const T v[N], T ex[N], T tot[N])
+{
+    __shared__ T s_w[NT / 64][N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T before[N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        T x = v[q];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const T y = __shfl_up(x, (unsigned)d, 64);
+            if (lane >= d && y > x) x = y;
+        }
+        const T y = __shfl_up(x, 1u, 64);
+        before[q] = lane ? y : 0;
+        if (lane == 63) s_w[wave][q] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        T pre = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < NT / 64; ++w) {
+            const T x = s_w[w][q];
+            if (w < wave && x > pre) pre = x;
+            if (x > all) all = x;
+        }
+        ex[q] = before[q] > pre ? before[q] : pre;
         tot[q] = all;
     }
     __syncthreads();

@@ -16,7 +16,6 @@ namespace hbs {
 constexpr int kRtpPlanLanes = 256;                  /* plan: a lane a NAL, 256 NALs a workgroup                     */
 constexpr int kRtpNalsPerBlock = kRtpPlanLanes;
 constexpr uint64_t kRtpTileBytes = 64 * 1024;       /* copy: output bytes of one workgroup                          */
-constexpr uint64_t kRtpOutCapMax = 1ull << 46;      /* out_cap sizes the copy's grid and scratch                    */
 constexpr uint32_t kRtpHeader = 12;                 /* the fixed RTP header                                         */
 constexpr uint32_t kRtpFuHeader = 3;                /* PayloadHdr (2) + FU header (1)                               */
 constexpr int kRtpMinPayload = 4, kRtpMaxPayload = 65535 - 12;

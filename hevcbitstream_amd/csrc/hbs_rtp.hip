@@ -26,8 +26,7 @@
 #include <hip/hip_runtime.h>
 #include "hbs_rtp.h"
 #include "hbs_plan.h"
-#include "hbs_pieces.h"
-#include "hbs_wave.h"
+#include "hbs_copy16.h"
 
 namespace hbs {
 namespace {
@@ -155,34 +154,9 @@ __global__ __launch_bounds__(256) void k_rtp_tiles(RtpArgs a)
 {
     if (a.ctl[0] != 0) return;
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t total = a.ctl[1];
-    const uint64_t used = (total + kTile - 1) / kTile;
-    if (t > used || t > a.tiles || a.n_nals == 0) return;
-    if (t == used) { a.tile_first[t] = a.n_nals - 1; return; }
-    const uint64_t o = t * kTile;
-    uint64_t lo = 0, hi = a.n_nals - 1;               /* the last NAL whose packets begin at or before o */
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (a.rec_out[mid] <= o) lo = mid; else hi = mid - 1;
-    }
-    a.tile_first[t] = lo;
+    if (t > a.tiles) return;
+    tile_first_of<kTile>(a.rec_out, a.n_nals, a.ctl[1], t, a.tile_first);
 }
-
-/* bytes [sh, sh + 16) of the 32 bytes a:b */
-__device__ __forceinline__ u32x4 realign(u32x4 a, u32x4 b, uint32_t sh)
-{
-    const uint32_t q = sh >> 2, r = sh & 3u;
-    uint32_t x0, x1, x2, x3, x4;
-    if (q == 0)      { x0 = a.x; x1 = a.y; x2 = a.z; x3 = a.w; x4 = b.x; }
-    else if (q == 1) { x0 = a.y; x1 = a.z; x2 = a.w; x3 = b.x; x4 = b.y; }
-    else if (q == 2) { x0 = a.z; x1 = a.w; x2 = b.x; x3 = b.y; x4 = b.z; }
-    else             { x0 = a.w; x1 = b.x; x2 = b.y; x3 = b.z; x4 = b.w; }
-    u32x4 v;
-    v.x = alignbyte(x1, x0, r); v.y = alignbyte(x2, x1, r); v.z = alignbyte(x3, x2, r); v.w = alignbyte(x4, x3, r);
-    return v;
-}
-
-__device__ __forceinline__ u32x4 zero4() { u32x4 z; z.x = z.y = z.z = z.w = 0; return z; }
 
 /* the tile's NALs [j0, j0 + cnt): out(i) = where the packets of NAL j0 + i begin in the output (i = cnt: where they end) */
 struct TileNals {
@@ -196,11 +170,7 @@ struct TileNals {
     /* the last NAL i in [lo, hi] with out(i) <= o (out(lo) <= o holds) */
     __device__ __forceinline__ uint32_t find(uint32_t lo, uint32_t hi, uint64_t o) const
     {
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1) >> 1;
-            if (out(mid) <= o) lo = mid; else hi = mid - 1;
-        }
-        return lo;
+        return last_le(lo, hi, o, [&](uint32_t i) { return out(i); });
     }
 };
 
@@ -292,11 +262,8 @@ __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
                         s = S + 2u + p * F + (i - head_fu);
                     }
                     if (ok) {
-                        const uint64_t g = s & ~15ull;
-                        sh[u] = (uint32_t)(s & 15u);
                         simple[u] = true;
-                        va[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g));
-                        if (sh[u]) vb[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g + 16));
+                        load16_pair(a.src, s, va[u], vb[u], sh[u]);
                     }
                 }
             }
@@ -346,7 +313,8 @@ __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
 hipError_t launch_rtp_pack(const RtpArgs& a, hipStream_t st)
 {
     const uint64_t blocks = (a.n_nals + kRtpNalsPerBlock - 1) / kRtpNalsPerBlock;
-    if (a.ev_begin) { const hipError_t e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_rtp_count, dim3((unsigned)blocks), dim3(kRtpPlanLanes), 0, st, a);
     hipLaunchKernelGGL(k_rtp_scan, dim3(1), dim3(kPlanLanes), 0, st, a, blocks);
     if (a.out && blocks) {

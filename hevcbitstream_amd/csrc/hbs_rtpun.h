@@ -16,7 +16,6 @@
 namespace hbs {
 
 constexpr int kRtpuPacketsPerBlock = 256;           /* a lane a packet, 256 packets a workgroup                       */
-constexpr uint64_t kRtpuOutCapMax = 1ull << 46;     /* out_cap sizes the copy's grid and the piece table              */
 constexpr uint32_t kRtpuFlags = HBS_RTPU_MATCH_SSRC;
 
 /* the classes of a packet, in the order of the packet rule */

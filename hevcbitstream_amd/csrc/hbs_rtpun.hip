@@ -95,32 +95,6 @@ __device__ __forceinline__ RtpuPacket read_entry(const RtpuArgs& a, uint64_t p, 
     return rtpu_read(pb, size, a.q);
 }
 
-/* exclusive max-scan over the kT lanes of the workgroup; tot: over all of them */
-__device__ __forceinline__ void block_excl_max(uint64_t v, uint64_t& ex, uint64_t& tot)
-{
-    __shared__ unsigned long long s_m[kT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long y = __shfl_up(x, (unsigned)d, 64);
-        if (lane >= d && y > x) x = y;
-    }
-    const unsigned long long before = __shfl_up(x, 1u, 64);
-    if (lane == 63) s_m[wave] = x;
-    __syncthreads();
-    uint64_t pre = 0, all = 0;
-    for (int w = 0; w < kT / 64; ++w) {
-        const uint64_t m = s_m[w];
-        if (w < wave && m > pre) pre = m;
-        if (m > all) all = m;
-    }
-    const uint64_t e = lane ? (uint64_t)before : 0;
-    ex = e > pre ? e : pre;
-    tot = all;
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kT) void k_rtpu_class(RtpuArgs a)
 {
     const uint64_t p = (uint64_t)blockIdx.x * kT + threadIdx.x;
@@ -255,7 +229,7 @@ __global__ __launch_bounds__(kT) void k_rtpu_count(RtpuArgs a)
     uint64_t ex[5], tot[5];
     block_scan<5, kT>(v, ex, tot);
     uint64_t mex, mtot;
-    block_excl_max(gives_at, mex, mtot);
+    block_excl_max<uint64_t, 1, kT>(&gives_at, &mex, &mtot);
     if (threadIdx.x == 0) {
         unsigned long long* q = a.part_n + (uint64_t)blockIdx.x * 8;
         q[0] = tot[0]; q[1] = tot[1]; q[2] = tot[2]; q[3] = tot[3]; q[4] = tot[4]; q[5] = 0;
@@ -274,7 +248,7 @@ __global__ __launch_bounds__(kT) void k_rtpu_scan_n(RtpuArgs a, uint64_t blocks)
         uint64_t acc = 0;
         for (int i = 0; i < kPlanPer && i0 + i < blocks; ++i) { const uint64_t x = a.last_n[i0 + i]; if (x > acc) acc = x; }
         uint64_t cur, tot;
-        block_excl_max(acc, cur, tot);
+        block_excl_max<uint64_t, 1, kT>(&acc, &cur, &tot);
         if (run > cur) cur = run;
         for (int i = 0; i < kPlanPer && i0 + i < blocks; ++i) {
             const uint64_t x = a.last_n[i0 + i];
@@ -293,8 +267,9 @@ __global__ __launch_bounds__(kT) void k_rtpu_au(RtpuArgs a)
     const bool in = p < a.n_packets;
     const uint32_t st = in ? a.state[p] : 0u;
     const bool gives_nals = (st & kGives) != 0;
+    const uint64_t gives_at = gives_nals ? p + 1 : 0;
     uint64_t before, all;
-    block_excl_max(gives_nals ? p + 1 : 0, before, all);
+    block_excl_max<uint64_t, 1, kT>(&gives_at, &before, &all);
     uint64_t v[1] = {0};
     if (gives_nals) {
         const uint64_t far = a.last_n[blockIdx.x];
@@ -402,7 +377,8 @@ hipError_t launch_rtp_unpack(const RtpuArgs& a, hipStream_t st)
 {
     const uint64_t blocks = rtpu_blocks(a.n_packets);
     const dim3 grid((unsigned)blocks), lanes(kT);
-    if (a.ev_begin) { const hipError_t e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_rtpu_class, grid, lanes, 0, st, a);
     hipLaunchKernelGGL(k_rtpu_scan_c, dim3(1), lanes, 0, st, a, blocks);
     if (blocks) {

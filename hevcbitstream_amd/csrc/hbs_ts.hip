@@ -17,15 +17,16 @@
  *                lengths scanned; every aligned 16-byte chunk of the round's output range is then put together from the image
  *                -- the packet by binary search of the in-LDS offsets; a chunk inside one packet's run as five dwords and
  *                alignbyte, one that spans packets byte by byte -- and stored whole; the partial chunks at the two ends of
- *                the range are stored byte-exactly (store_pieces), so neighbouring rounds and workgroups never write the
- *                same byte.
+ *                the range are stored byte-exactly (store_chunk), so neighbouring rounds and workgroups never write the
+ *                same byte.  The chunk helpers are hbs_copy16.h, the workgroup scans hbs_plan.h.
  *
  * Traffic: the stream read once by the copy; the plan passes read header bytes only (a cache line in front of each 188 bytes,
  * twice, three times with d_pes); 64 B a block of scratch.
  */
 #include <hip/hip_runtime.h>
 #include "hbs_ts.h"
-#include "hbs_wave.h"
+#include "hbs_plan.h"
+#include "hbs_copy16.h"
 
 namespace hbs {
 namespace {
@@ -48,48 +49,6 @@ enum : int {
     kPPesBase,        /* PES starts in front of the block                                                                   */
     kPLiveEs          /* ES bytes of the block that are output                                                              */
 };
-
-/* exclusive sum over the workgroup's lanes; tot = the sum of all */
-__device__ __forceinline__ uint64_t block_excl_sum(uint64_t v, uint64_t& tot)
-{
-    __shared__ unsigned long long s_w[kTT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long y = __shfl_up(x, (unsigned)d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_w[wave] = x;
-    __syncthreads();
-    uint64_t pre = 0, all = 0;
-    for (int w = 0; w < kTT / 64; ++w) { if (w < wave) pre += s_w[w]; all += s_w[w]; }
-    __syncthreads();
-    tot = all;
-    return pre + x - v;
-}
-
-/* exclusive maximum over the workgroup's lanes (0 for lane 0); tot = the maximum of all */
-__device__ __forceinline__ uint32_t block_excl_max(uint32_t v, uint32_t& tot)
-{
-    __shared__ uint32_t s_w[kTT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, (unsigned)d, 64);
-        if (lane >= d && y > x) x = y;
-    }
-    if (lane == 63) s_w[wave] = x;
-    __syncthreads();
-    uint32_t pre = 0, all = 0;
-    for (int w = 0; w < kTT / 64; ++w) { if (w < wave && s_w[w] > pre) pre = s_w[w]; if (s_w[w] > all) all = s_w[w]; }
-    __syncthreads();
-    uint32_t prev = __shfl_up(x, 1u, 64);
-    if (lane == 0) prev = 0;
-    tot = all;
-    return prev > pre ? prev : pre;
-}
 
 /* a packet's bytes in device memory: plain byte loads, every one of them inside the packet */
 __device__ __forceinline__ void classify_packet(const TsArgs& a, uint64_t p, hbs_ts_packet& r)
@@ -130,8 +89,8 @@ __global__ __launch_bounds__(kTT) void k_ts_count(TsArgs a)
     __syncthreads();
     if (my_pes != kNone) atomicMin(&s_first_pes, my_pes);
     if (my_fault != kNone) atomicMin(&s_fault, my_fault);
-    uint32_t any;
-    uint32_t prev = block_excl_max(last_key, any);                    /* the last packet with ES bytes in front of the lane */
+    uint32_t prev, any;                                               /* the last packet with ES bytes in front of the lane */
+    block_excl_max<uint32_t, 1, kTT>(&last_key, &prev, &any);
     const uint32_t F = s_first_pes;
     uint32_t sum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -216,11 +175,13 @@ __global__ __launch_bounds__(kTT) void k_ts_scan(TsArgs a, uint32_t blocks)
                 joins = (cc & 1u) != 0;
             }
         }
-        uint64_t tot_es, tot_pes;
-        const uint64_t ex_es = block_excl_sum(es, tot_es), ex_pes = block_excl_sum(pes, tot_pes);
-        uint32_t last_all;
+        uint64_t ex_es, tot_es, ex_pes, tot_pes;
+        block_scan<1, kTT>(&es, &ex_es, &tot_es);
+        block_scan<1, kTT>(&pes, &ex_pes, &tot_pes);
+        uint32_t before, last_all;
         const uint32_t key = (cc & 1u) ? (((threadIdx.x + 1u) << 5) | 16u | ((cc >> 12) & 15u)) : 0u;
-        uint32_t prev = block_excl_max(key, last_all) & 31u;
+        block_excl_max<uint32_t, 1, kTT>(&key, &before, &last_all);
+        uint32_t prev = before & 31u;
         if (!prev) prev = carry_cc;
         if (joins && prev && cc_breaks(prev & 15u, (cc >> 4) & 15u, ((cc >> 8) & 1u) != 0)) breaks += 1;
         if (in) {
@@ -266,9 +227,11 @@ __global__ __launch_bounds__(kTT) void k_ts_place(TsArgs a)
         classify_packet(a, p, r);
         if (ts_has_es(r.cls)) { es += r.es_len; pes += r.cls == HBS_TS_PES_START ? 1 : 0; }
     }
-    uint64_t tot;
-    uint64_t o = block_excl_sum(es, tot) + (((uint64_t)w[kPOutHi] << 32) | w[kPOutLo]);
-    uint64_t k = block_excl_sum(pes, tot) + w[kPPesBase];
+    uint64_t o, k, tot;
+    block_scan<1, kTT>(&es, &o, &tot);
+    block_scan<1, kTT>(&pes, &k, &tot);
+    o += ((uint64_t)w[kPOutHi] << 32) | w[kPOutLo];
+    k += w[kPPesBase];
     if (!pes) return;
 #pragma unroll 1
     for (int i = 0; i < kTPer; ++i) {
@@ -318,9 +281,10 @@ __global__ __launch_bounds__(kTT) void k_ts_copy(TsArgs a)
             ts_classify(TsByteReader{img + at}, a.pid, r);
             if (ts_has_es(r.cls)) { len = r.es_len; src = at + r.es_off; }
         }
-        uint64_t tot64;
-        const uint32_t off = (uint32_t)block_excl_sum(len, tot64);
-        const uint32_t total = (uint32_t)tot64;
+        const uint64_t len64 = len;
+        uint64_t off64, tot64;
+        block_scan<1, kTT>(&len64, &off64, &tot64);
+        const uint32_t off = (uint32_t)off64, total = (uint32_t)tot64;
         s_off[threadIdx.x] = off; s_src[threadIdx.x] = src;
         if (threadIdx.x == 0) s_off[kTsRoundPackets] = total;
         __syncthreads();
@@ -330,20 +294,14 @@ __global__ __launch_bounds__(kTT) void k_ts_copy(TsArgs a)
         for (uint32_t c = threadIdx.x; c < chunks && total; c += kTT) {
             const uint32_t lo = c ? 16u * c - head : 0u;
             const uint32_t hi = 16u * c + 16u - head < total ? 16u * c + 16u - head : total;
-            /* the packet the chunk's first byte comes from: the first j with s_off[j + 1] > lo */
-            uint32_t j = 0, jh = kTsRoundPackets - 1;
-            while (j < jh) {
-                const uint32_t mid = (j + jh) >> 1;
-                if (s_off[mid + 1] > lo) jh = mid; else j = mid + 1;
-            }
+            /* the packet the chunk's first byte comes from: the last j with s_off[j] <= lo.  That is the first j with
+             * s_off[j + 1] > lo, the packet whose run holds byte lo, runs of no bytes in front of it included: s_off does
+             * not decrease and lo < total = s_off[256], so the offsets <= lo are s_off[0 .. j] and no others */
+            uint32_t j = last_le(0u, (uint32_t)kTsRoundPackets - 1u, lo, [&](uint32_t i) { return s_off[i]; });
             uint8_t* dst = a.out + obase + lo;
             if (hi - lo == 16u && s_off[j + 1] - lo >= 16u) {
-                const uint32_t at = s_src[j] + (lo - s_off[j]), r = at & 3u;
-                const uint32_t* d = img32 + (at >> 2);
-                const uint32_t x0 = d[0], x1 = d[1], x2 = d[2], x3 = d[3], x4 = d[4];
-                u32x4 v;
-                v.x = alignbyte(x1, x0, r); v.y = alignbyte(x2, x1, r); v.z = alignbyte(x3, x2, r); v.w = alignbyte(x4, x3, r);
-                arena_store16(dst, v);
+                const uint32_t at = s_src[j] + (lo - s_off[j]);
+                arena_store16(dst, realign(img32 + (at >> 2), at & 3u));
                 continue;
             }
             uint64_t clo = 0, chi = 0;
@@ -351,17 +309,9 @@ __global__ __launch_bounds__(kTT) void k_ts_copy(TsArgs a)
 #pragma unroll 1
             for (uint32_t q = lo; q < hi; ++q) {
                 while (q >= end) { j += 1; end = s_off[j + 1]; at = s_src[j]; }     /* (runs of no bytes are passed over) */
-                const uint64_t v = img[at++];
-                const uint32_t k = q - lo;
-                if (k < 8) clo |= v << (8 * k); else chi |= v << (8 * (k - 8));
+                pack_byte(clo, chi, q - lo, img[at++]);
             }
-            if (hi - lo == 16u) {
-                u32x4 v;
-                v.x = (uint32_t)clo; v.y = (uint32_t)(clo >> 32); v.z = (uint32_t)chi; v.w = (uint32_t)(chi >> 32);
-                arena_store16(dst, v);
-            } else {
-                store_pieces(dst, clo, chi, hi - lo);                 /* an end of the round's range: these bytes and no others */
-            }
+            store_chunk(dst, clo, chi, hi - lo);
         }
         obase += total;
         __syncthreads();                                              /* the image and the offsets are the next round's */
@@ -373,18 +323,15 @@ __global__ __launch_bounds__(kTT) void k_ts_copy(TsArgs a)
 hipError_t launch_ts_demux(const TsArgs& a, hipStream_t st)
 {
     const uint32_t blocks = (uint32_t)((a.packets + kTsPacketsPerBlock - 1) / kTsPacketsPerBlock);
-    hipError_t e = hipSuccess;
-    if (a.ev_begin) { e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_ts_count, dim3(blocks), dim3(kTT), 0, st, a);
     hipLaunchKernelGGL(k_ts_scan, dim3(1), dim3(kTT), 0, st, a, blocks);
     if (a.out && blocks) {
         if (a.pes) hipLaunchKernelGGL(k_ts_place, dim3(blocks), dim3(kTT), 0, st, a);
         hipLaunchKernelGGL(k_ts_copy, dim3(blocks), dim3(kTT), 0, st, a);
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (a.ev_end) e = hipEventRecord(a.ev_end, st);
-    return e;
+    return end_launches(a.ev_end, st);
 }
 
 } // namespace hbs

@@ -27,8 +27,7 @@
 #include <hip/hip_runtime.h>
 #include "hbs_tsmux.h"
 #include "hbs_plan.h"
-#include "hbs_pieces.h"
-#include "hbs_wave.h"
+#include "hbs_copy16.h"
 
 namespace hbs {
 namespace {
@@ -146,26 +145,8 @@ __global__ __launch_bounds__(256) void k_tsm_blocks(TsmArgs a)
     const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint64_t P = b * kTsmPacketsPerBlock;
     if (b >= a.copy_blocks || P >= a.ctl[1]) return;
-    uint64_t lo = 0, hi = a.n_aus - 1;                /* the last AU whose PES begins at or in front of P (0 when none does) */
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (a.au_pkt[mid] <= P) lo = mid; else hi = mid - 1;
-    }
-    a.blk_first[b] = (uint32_t)lo;
-}
-
-/* bytes [sh, sh + 16) of the 32 bytes a:b */
-__device__ __forceinline__ u32x4 realign(u32x4 a, u32x4 b, uint32_t sh)
-{
-    const uint32_t q = sh >> 2, r = sh & 3u;
-    uint32_t x0, x1, x2, x3, x4;
-    if (q == 0)      { x0 = a.x; x1 = a.y; x2 = a.z; x3 = a.w; x4 = b.x; }
-    else if (q == 1) { x0 = a.y; x1 = a.z; x2 = a.w; x3 = b.x; x4 = b.y; }
-    else if (q == 2) { x0 = a.z; x1 = a.w; x2 = b.x; x3 = b.y; x4 = b.z; }
-    else             { x0 = a.w; x1 = b.x; x2 = b.y; x3 = b.z; x4 = b.w; }
-    u32x4 v;
-    v.x = alignbyte(x1, x0, r); v.y = alignbyte(x2, x1, r); v.z = alignbyte(x3, x2, r); v.w = alignbyte(x4, x3, r);
-    return v;
+    /* the last AU whose PES begins at or in front of P (0 when none does) */
+    a.blk_first[b] = (uint32_t)last_le((uint64_t)0, a.n_aus - 1, P, [&](uint64_t k) { return (uint64_t)a.au_pkt[k]; });
 }
 
 /* what the bytes in front of a packet's ES bytes are made from */
@@ -229,14 +210,8 @@ __global__ __launch_bounds__(kMT) void k_tsm_copy(TsmArgs a)
             uint32_t head = kTsBytes, r = kNone;
             uint64_t delta = 0;
             if (P < P1) {
-                if (s_pkt[0] <= P) {
-                    uint32_t lo = 0, hi = cnt - 1;                     /* the last staged AU whose PES begins at or in front of P */
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi + 1) >> 1;
-                        if (s_pkt[mid] <= P) lo = mid; else hi = mid - 1;
-                    }
-                    r = lo;
-                }
+                /* the last staged AU whose PES begins at or in front of P */
+                if (s_pkt[0] <= P) r = last_le(0u, cnt - 1, P, [&](uint32_t i) { return (uint64_t)s_pkt[i]; });
                 PacketCtx c;
                 packet_ctx(a, s_pkt, a0, r, P, c);
                 if (!c.psi) { head = c.p.head; delta = c.begin + c.p.src_off - (P * kB + kLead + head); }
@@ -256,16 +231,12 @@ __global__ __launch_bounds__(kMT) void k_tsm_copy(TsmArgs a)
             for (int u = 0; u < kBatch; ++u) {
                 const uint32_t o = 16u * (threadIdx.x + (uint32_t)kMT * (uint32_t)(b + u));
                 simple[u] = false; sh[u] = 0;
-                va[u] = (u32x4)(0u); vb[u] = (u32x4)(0u);
+                va[u] = zero4(); vb[u] = zero4();
                 if (b + u < kPerLane && o < rbytes) {
                     const uint32_t p = o / kB, i = o - p * kB;
                     if (i >= kLead + s_head[p] && i + 16u <= kLead + kTsBytes) {
-                        const uint64_t s = obase + o + s_delta[p];
-                        const uint64_t g = s & ~15ull;
-                        sh[u] = (uint32_t)(s & 15u);
                         simple[u] = true;
-                        va[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g));
-                        if (sh[u]) vb[u] = stream_load16(reinterpret_cast<const u32x4*>(a.src + g + 16));
+                        load16_pair(a.src, obase + o + s_delta[p], va[u], vb[u], sh[u]);
                     } else {
                         slow |= 1u << (b + u);
                     }
@@ -305,16 +276,9 @@ __global__ __launch_bounds__(kMT) void k_tsm_copy(TsmArgs a)
                         }
                     }
                 }
-                if (q < 8) clo |= v << (8 * q); else chi |= v << (8 * (q - 8));
+                pack_byte(clo, chi, q, v);
             }
-            uint8_t* dst = a.out + obase + o;
-            if (len == 16u) {
-                u32x4 x;
-                x.x = (uint32_t)clo; x.y = (uint32_t)(clo >> 32); x.z = (uint32_t)chi; x.w = (uint32_t)(chi >> 32);
-                arena_store16(dst, x);
-            } else {
-                store_pieces(dst, clo, chi, len);                     /* the output's end: these bytes and no others */
-            }
+            store_chunk(a.out + obase + o, clo, chi, len);
         }
         __syncthreads();                                              /* the packets' layout is the next round's */
     }
@@ -325,7 +289,8 @@ __global__ __launch_bounds__(kMT) void k_tsm_copy(TsmArgs a)
 hipError_t launch_ts_mux(const TsmArgs& a, hipStream_t st)
 {
     const uint64_t blocks = (a.n_aus + kTsmAusPerBlock - 1) / kTsmAusPerBlock;
-    if (a.ev_begin) { const hipError_t e = hipEventRecord(a.ev_begin, st); if (e != hipSuccess) return e; }
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_tsm_count, dim3((unsigned)blocks), dim3(kTsmPlanLanes), 0, st, a);
     hipLaunchKernelGGL(k_tsm_scan, dim3(1), dim3(kPlanLanes), 0, st, a, blocks);
     if (a.out && blocks) {
