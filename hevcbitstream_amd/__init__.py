@@ -15,8 +15,8 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   STREAM_TYPE_HEVC, ts_packet, ts_find_pid,
                   TS_MUX_PARAMS, TSMUX_PCR, TSMUX_PSI_AT_IRAP, TSMUX_NO_PSI, ts_mux_params, ts_mux_psi, ts_mux_au_packets,
                   AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST, aud_nal,
-                  RTP_PARAMS, RTP_PACKET, RTP_OPEN_END, RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER,
-                  rtp_params, rtp_nal_packets, rtp_packet, rtp_packet_offsets,
+                  RTP_PARAMS, RTP_PACKET, RTP_OPEN_END, RTP_AGGREGATE, RTP_AP_SPAN, RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER,
+                  rtp_params, rtp_nal_packets, rtp_packet, rtp_ap_units, rtp_packet_offsets,
                   RTP_UNPACK_PARAMS, RTPU_MATCH_SSRC, rtp_unpack_params, rtp_frames)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
@@ -29,6 +29,6 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "STREAM_TYPE_HEVC", "ts_packet", "ts_find_pid",
            "TS_MUX_PARAMS", "TSMUX_PCR", "TSMUX_PSI_AT_IRAP", "TSMUX_NO_PSI", "ts_mux_params", "ts_mux_psi", "ts_mux_au_packets",
            "AUINS_AUD", "AUINS_PARAM_SETS", "AUINS_PARAM_SETS_FIRST", "aud_nal",
-           "RTP_PARAMS", "RTP_PACKET", "RTP_OPEN_END", "RTP_SINGLE", "RTP_FU", "RTP_AP", "RTP_OTHER",
-           "rtp_params", "rtp_nal_packets", "rtp_packet", "rtp_packet_offsets",
+           "RTP_PARAMS", "RTP_PACKET", "RTP_OPEN_END", "RTP_AGGREGATE", "RTP_AP_SPAN", "RTP_SINGLE", "RTP_FU", "RTP_AP", "RTP_OTHER",
+           "rtp_params", "rtp_nal_packets", "rtp_packet", "rtp_ap_units", "rtp_packet_offsets",
            "RTP_UNPACK_PARAMS", "RTPU_MATCH_SSRC", "rtp_unpack_params", "rtp_frames"]

@@ -50,6 +50,8 @@ RTP_PACKET = np.dtype([("payload_off", "<u8"), ("payload_len", "<u8"), ("nal_off
                        ("nal_type", "<i4"), ("marker", "<u4"), ("payload_type", "<u4"), ("seq", "<u4"), ("timestamp", "<u4"),
                        ("ssrc", "<u4"), ("fu_start", "<u4"), ("fu_end", "<u4"), ("nal_header", "u1", (2,)), ("reserved", "u1", (2,))])
 RTP_OPEN_END = 1
+RTP_AGGREGATE = 4         # consecutive small NALs of an access unit share an aggregation packet ...
+RTP_AP_SPAN = 256         # ... which never reaches across a multiple of this in the call's NAL numbering
 RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER = 0, 1, 2, 3
 # layout of hbs_rtp_unpack_params and the flags of hbs_rtp_unpack
 RTP_UNPACK_PARAMS = np.dtype([("payload_type", "<i4"), ("startcode_bytes", "<i4"), ("flags", "<u4"), ("ssrc", "<u4")])
@@ -85,7 +87,7 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
            "hbs_au_insert", "hbs_aud_nal_host",
-           "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host",
+           "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host", "hbs_rtp_ap_units_host",
            "hbs_rtp_unpack", "hbs_rtp_frames_host"]
 
 
@@ -237,6 +239,8 @@ def load_library():
     lib.hbs_rtp_nal_packets_host.argtypes = [C.c_uint64, C.c_int]
     lib.hbs_rtp_nal_packets_host.restype = C.c_uint64
     lib.hbs_rtp_packet_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.hbs_rtp_ap_units_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.hbs_rtp_ap_units_host.restype = C.c_int64
     lib.hbs_rtp_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                    C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.hbs_rtp_frames_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -326,14 +330,32 @@ def rtp_packet(packet):
     return out[0]
 
 
+def rtp_ap_units(packet):
+    """hbs_rtp_ap_units_host: the NAL units of one aggregation packet (bytes or a uint8 array, without a length field, host
+    memory) -> (offsets within the packet ndarray[uint64], sizes ndarray[uint64]).  Raises HbsError for a packet that is no
+    well-formed aggregation packet.  No GPU involved."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(packet), dtype=np.uint8) if isinstance(packet, (bytes, bytearray)) else packet, dtype=np.uint8)
+    lib = load_library()
+    ptr = a.ctypes.data if len(a) else None
+    units = int(lib.hbs_rtp_ap_units_host(ptr, len(a), None, None, 0))
+    if units < 0:
+        raise HbsError("hbs_rtp_ap_units_host failed: %d" % units)
+    off, size = np.zeros(units, dtype=np.uint64), np.zeros(units, dtype=np.uint64)
+    lib.hbs_rtp_ap_units_host(ptr, len(a), off.ctypes.data, size.ctypes.data, units)
+    return off, size
+
+
 def rtp_packet_offsets(nal_off, nal_packet, max_payload, framing=0):
     """the output offset of every packet of an hbs_rtp_pack call, and the total behind them (packets + 1 entries), from the two
-    per-NAL tables: all packets of a NAL but its last take framing + 12 + max_payload bytes"""
+    per-NAL tables: all packets of a NAL but its last take framing + 12 + max_payload bytes.  With RTP_AGGREGATE the units of an
+    aggregation packet share a packet number: NAL k opens a packet when k == 0 or nal_packet[k] != nal_packet[k - 1]"""
     nal_off, nal_packet = np.asarray(nal_off, dtype=np.uint64), np.asarray(nal_packet, dtype=np.uint64)
-    count = np.diff(nal_packet).astype(np.int64)
-    first = np.repeat(nal_packet[:-1], count)
+    opens = np.concatenate([[True], nal_packet[1:-1] != nal_packet[:-2]]) if len(nal_packet) > 1 else np.zeros(0, dtype=bool)
+    begin, number = nal_off[:-1][opens], nal_packet[:-1][opens]
+    count = np.diff(np.concatenate([number, nal_packet[-1:]])).astype(np.int64)
+    first = np.repeat(number, count)
     within = np.arange(int(nal_packet[-1]), dtype=np.uint64) - first
-    off = np.repeat(nal_off[:-1], count) + within * np.uint64(int(framing) + 12 + int(max_payload))
+    off = np.repeat(begin, count) + within * np.uint64(int(framing) + 12 + int(max_payload))
     return np.concatenate([off, nal_off[-1:]]).astype(np.uint64)
 
 

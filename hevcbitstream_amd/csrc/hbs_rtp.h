@@ -1,7 +1,9 @@
 /*
  * hbs_rtp.h -- hbs_rtp_pack (include/hevcbitstream_amd.h): the rule that turns one NAL unit into RFC 7798 RTP packets, as
  * host/device inline functions -- rtp_nal lays a NAL out (single NAL unit packet or fragmentation units, packets, output
- * bytes), rtp_packet_bytes gives packet p's length and rtp_head_byte every byte in front of its NAL bytes; the kernels of
+ * bytes), rtp_packet_bytes gives packet p's length and rtp_head_byte every byte in front of its NAL bytes; with
+ * HBS_RTP_AGGREGATE rtp_group_next is the greedy group rule and rtp_ap_head_byte every byte in front of an aggregation
+ * packet's first unit; the kernels of
  * hbs_rtp.hip, the two host entry points and the tests all run them -- the receiver's view of one packet (rtp_packet_rule: a
  * host/device function too, behind rtp_packet_host and in the kernels of hbs_rtp_unpack, hbs_rtpun.hip), and the host-visible
  * launcher.  Everything above the launcher compiles with plain g++.
@@ -92,13 +94,73 @@ HBS_HD uint32_t rtp_head_byte(const RtpRule& q, bool fu, bool first, bool last, 
     return (first ? 0x80u : 0u) | (last ? 0x40u : 0u) | ((h0 >> 1) & 63u);
 }
 
+/* ---- aggregation packets (HBS_RTP_AGGREGATE): the group rule and the bytes in front of an AP's first unit -------------- */
+
+constexpr uint32_t kRtpApHead = 2;                  /* an AP's PayloadHdr                                           */
+constexpr uint32_t kRtpApSize = 2;                  /* the size field in front of every unit                        */
+static_assert(HBS_RTP_AP_SPAN == kRtpNalsPerBlock, "a plan workgroup finds its groups without looking outside its NALs");
+
+/* what NAL k adds to an AP's payload, 2 + L; a NAL too long for any packet counts as 65538 so that 256 of them sum in 32 bits */
+HBS_HD uint32_t rtp_ap_weight(uint64_t L) { return kRtpApSize + (uint32_t)(L < 0x10000u ? L : 0x10000u); }
+
+/* a NAL of weight w that shares a packet with no other NAL whatever its neighbours are: 2 + w + (2 + 2) > mp */
+HBS_HD bool rtp_ap_loner(uint32_t w, uint32_t mp) { return (uint64_t)kRtpApHead + w + kRtpApSize + 2u > mp; }
+
+/* next(i) of the group rule for i < hi: the smallest j > i with j == hi, au(j) != au(i) or 2 + sum_{m = i..j} (2 + L_m) > mp.
+ * hi: the end of i's span of HBS_RTP_AP_SPAN NALs or n_nals, whichever is lower; pre(j): the sum of rtp_ap_weight over the
+ * NALs in front of j, from any fixed NAL at or in front of i (pre(hi) exists); au(j): NAL j's AU number.  AU numbers never go
+ * down and weights are positive, so "j ends the group" holds for every j behind the first for which it holds: a binary search.
+ * (Where the AU numbers do go down, which the call refuses, the result is still in (i, hi].) */
+template <class Pre, class Au> HBS_HD uint32_t rtp_group_next(uint32_t i, uint32_t hi, uint32_t mp, Pre pre, Au au)
+{
+    const uint64_t base = pre(i);
+    const uint32_t a = au(i);
+    uint32_t lo = i + 1, top = hi;                                   /* the answer lies in [lo, top] */
+    while (lo < top) {
+        const uint32_t mid = lo + ((top - lo) >> 1);
+        const bool ends = au(mid) != a || (uint64_t)kRtpApHead + (pre(mid + 1) - base) > mp;
+        if (ends) top = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+/* F, layer id and TID of an AP's PayloadHdr: the OR of the units' F bits, the lowest layer id, the lowest TID.  `acc` starts
+ * as kRtpApFoldStart and takes every unit's header bytes; then rtp_ap_payload_hdr */
+constexpr uint32_t kRtpApFoldStart = 63u << 8 | 7u;                  /* F << 16 | layer << 8 | tid */
+HBS_HD uint32_t rtp_ap_fold(uint32_t acc, uint32_t h0, uint32_t h1)
+{
+    const uint32_t f = (acc >> 16) | (h0 >> 7), layer = (h0 & 1u) << 5 | h1 >> 3, tid = h1 & 7u;
+    const uint32_t l0 = (acc >> 8) & 63u, t0 = acc & 7u;
+    return f << 16 | (layer < l0 ? layer : l0) << 8 | (tid < t0 ? tid : t0);
+}
+/* -> byte 0 | byte 1 << 8 */
+HBS_HD uint32_t rtp_ap_payload_hdr(uint32_t acc)
+{
+    const uint32_t f = acc >> 16, layer = (acc >> 8) & 63u, tid = acc & 7u;
+    return (f << 7 | 48u << 1 | layer >> 5) | ((layer & 31u) << 3 | tid) << 8;
+}
+
+/* bytes in front of the NAL bytes of an AP's first unit, and of a later unit */
+HBS_HD uint32_t rtp_ap_first_head(const RtpRule& q) { return q.fr + kRtpHeader + kRtpApHead + kRtpApSize; }
+
+/* byte i (i < rtp_ap_first_head) of an AP whose payload has pay bytes: number j of the call, timestamp ts; marker: its last
+ * unit ends its access unit; hdr: rtp_ap_payload_hdr; L: the first unit's size */
+HBS_HD uint32_t rtp_ap_head_byte(const RtpRule& q, bool marker, uint32_t pay, uint64_t j, uint32_t ts, uint32_t hdr, uint32_t L, uint32_t i)
+{
+    const uint32_t fixed = q.fr + kRtpHeader;
+    if (i < fixed) return rtp_head_byte(q, false, true, true, marker, (uint64_t)fixed + pay, j, ts, 0, 0, i);
+    i -= fixed;
+    if (i < kRtpApHead) return (hdr >> (8u * i)) & 0xFFu;
+    return (i == kRtpApHead ? L >> 8 : L) & 0xFFu;
+}
+
 /* ---- host side: parameters, one NAL, one packet as a receiver reads it ------------------------------------------------- */
 
 inline bool rtp_params_ok(const hbs_rtp_params* p)
 {
     if (!p || !rtp_max_payload_ok(p->max_payload)) return false;
     if (p->payload_type < 0 || p->payload_type > 127 || (p->framing != 0 && p->framing != 2)) return false;
-    return (p->flags & ~HBS_RTP_OPEN_END) == 0u && p->seq <= 0xFFFFu;
+    return (p->flags & ~(HBS_RTP_OPEN_END | HBS_RTP_AGGREGATE)) == 0u && p->seq <= 0xFFFFu;
 }
 
 inline RtpRule rtp_rule(const hbs_rtp_params* p)
@@ -213,15 +275,17 @@ struct RtpArgs {
     unsigned long long* rec_out;   /* n_nals + 1: output offset of NAL k's first packet (then the total)                            */
     unsigned long long* rec_pkt;   /* n_nals + 1: number of NAL k's first packet (then the total)                                   */
     unsigned long long* rec_src;   /* n_nals: start_k                                                                                */
-    unsigned long long* rec_len;   /* n_nals: L                                                                                      */
-    unsigned long long* rec_tm;    /* n_nals: the timestamp, bit 32: the NAL ends its access unit                                   */
+    unsigned long long* rec_len;   /* n_nals: L; with HBS_RTP_AGGREGATE bits 62..63: 0 a packet or FUs of its own, 1 an AP's first unit, 2 a later unit */
+    unsigned long long* rec_tm;    /* n_nals: the timestamp, bit 32: the NAL ends its access unit (an AP's first unit: its last unit does) */
+    uint32_t* rec_ap;              /* n_nals, with HBS_RTP_AGGREGATE only; an AP's first unit: payload bytes | rtp_ap_payload_hdr << 16 */
     unsigned long long* tile_first;/* tiles + 1: the NAL the output tile's first byte lies in                                       */
     uint64_t tiles;                /* output tiles the copy's grid covers                                                           */
     hipEvent_t ev_begin, ev_end;
 };
 
 /* the most output bytes a call can make: L + 15 + framing for a single packet, a head of 15 + framing for every mp - 3 bytes
- * of an FU and one more for its short last packet */
+ * of an FU and one more for its short last packet.  HBS_RTP_AGGREGATE never makes more: an AP of m units takes
+ * (m - 1)(framing + 12) - 2 - 2m >= 6 bytes less than its m single packets, so the bound and the tile count hold for it too */
 inline uint64_t rtp_output_bound(uint64_t n_nals, uint64_t stream_bytes, const RtpRule& q)
 {
     const uint64_t head = q.fr + kRtpHeader + kRtpFuHeader;
@@ -245,6 +309,7 @@ inline void lay_rtp(Carver& w, RtpArgs& a)
     a.rec_src = w.take<unsigned long long>(recs * 8);
     a.rec_len = w.take<unsigned long long>(recs * 8);
     a.rec_tm = w.take<unsigned long long>(recs * 8);
+    a.rec_ap = w.take<uint32_t>((a.flags & HBS_RTP_AGGREGATE) ? recs * 4 : 0);
     a.tile_first = w.take<unsigned long long>(a.tiles ? (a.tiles + 1) * 8 : 0);
 }
 hipError_t launch_rtp_pack(const RtpArgs& a, hipStream_t st);

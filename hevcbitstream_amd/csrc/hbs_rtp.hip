@@ -20,8 +20,19 @@
  *                 sixty-four chunks at a time, a lane a byte of four chunks from the rule, sixteen lanes' bytes put together into one aligned
  *                 16-byte store; the output's last chunk is stored byte-exactly.
  *
+ * HBS_RTP_AGGREGATE (aggregation packets for groups of small NALs) is a second instance of k_rtp_count, k_rtp_place and
+ * k_rtp_copy; the instance without the flag compiles from the statements it had before the flag existed.  In the plan each
+ * workgroup finds the groups of its 256 NALs alone (ap_groups): 2 + L scanned over the lanes, next(i) by binary search
+ * (rtp_group_next), then ONE LANE WALKS EACH RUN between the starts that are known without walking -- lane 0, the first NAL of an
+ * access unit, a NAL that can share a packet with no other and the NAL behind it -- and marks the group starts it meets; the
+ * runs are disjoint, so at most 256 steps are taken in all.  (The other way, eight rounds of pointer doubling, needs eight
+ * tables of jumps in LDS and marks no faster where access units are short.)  A group's first lane folds the PayloadHdr over its
+ * units.  In the copy a unit of an AP is one more kind of NAL: 16 (+ framing) bytes in front of the first unit's bytes, 2 in
+ * front of a later unit's; its chunks take the same fast path, and a slow chunk's bytes find their NAL by search, because a
+ * unit may have as few as 4 output bytes and a chunk may touch five.
+ *
  * Traffic: the NALs' bytes read once and the output written once; 32 B a NAL of the index read by each plan pass, 40 B a NAL of
- * scratch written and read, 8 B a tile.
+ * scratch written and read (44 B with HBS_RTP_AGGREGATE), 8 B a tile.
  */
 #include <hip/hip_runtime.h>
 #include "hbs_rtp.h"
@@ -38,16 +49,20 @@ constexpr int kBatch = 4;                                             /* ... loa
 constexpr int kSlowBatch = 4;                                         /* slow chunks a group of sixteen lanes takes together */
 constexpr uint32_t kLdsNals = 512;                                    /* NALs a tile stages in LDS; more: read from memory */
 constexpr unsigned long long kMarker = 1ull << 32;                    /* rec_tm: the NAL ends its access unit    */
-static_assert(kTile / 16 <= 0x1000 && kTile / 14 < (1u << 20), "a slow chunk and its NAL share a word");
+constexpr unsigned long long kKindShift = 62, kLenMask = (1ull << kKindShift) - 1;   /* rec_len with HBS_RTP_AGGREGATE */
+constexpr uint32_t kOwn = 0, kApFirst = 1, kApLater = 2;              /* ... its kinds                           */
+static_assert(kTile / 16 <= 0x1000 && kTile / 4 < (1u << 20), "a slow chunk and its NAL share a word");
 
 struct NalEval {
     uint64_t start, L;
     uint32_t ts;
     bool bad, marker;
     RtpNal u;
+    uint32_t h0, h1;                                                  /* kAp only: the NAL's header bytes (0, 0 for a bad NAL) */
 };
 
 /* entry k: every check of the call that is about NAL k; each thing is checked before it is used */
+template <bool kAp>
 __device__ __forceinline__ NalEval eval_nal(const RtpArgs& a, uint64_t k)
 {
     const hbs_nal_entry* e = a.index + k;
@@ -55,10 +70,22 @@ __device__ __forceinline__ NalEval eval_nal(const RtpArgs& a, uint64_t k)
     NalEval r;
     r.start = start; r.L = 0; r.ts = 0;
     r.bad = start > end || end > a.n || start < prev_end;
-    if (!r.bad) {
-        r.L = end - start;
-        if (r.L < 2) r.bad = true;
-        else if (((a.src[start] >> 1) & 63u) >= 48u) r.bad = true;
+    if constexpr (!kAp) {
+        if (!r.bad) {
+            r.L = end - start;
+            if (r.L < 2) r.bad = true;
+            else if (((a.src[start] >> 1) & 63u) >= 48u) r.bad = true;
+        }
+    } else {
+        r.h0 = r.h1 = 0;
+        if (!r.bad) {
+            r.L = end - start;
+            if (r.L < 2) r.bad = true;
+            else {                                                    /* (L >= 2: both header bytes are the stream's) */
+                r.h0 = a.src[start]; r.h1 = a.src[start + 1];
+                if (((r.h0 >> 1) & 63u) >= 48u) { r.bad = true; r.h0 = r.h1 = 0; }
+            }
+        }
     }
     uint32_t rel = 0;
     bool au_ok = true;
@@ -85,15 +112,85 @@ __device__ __forceinline__ NalEval eval_nal(const RtpArgs& a, uint64_t k)
     return r;
 }
 
+/* HBS_RTP_AGGREGATE: what the group rule makes of the workgroup's NAL `x` (lane t, NAL k; in: k < n_nals) */
+struct ApLane {
+    uint32_t kind;                                                    /* kOwn, kApFirst, kApLater                           */
+    uint32_t pay;                                                     /* kApFirst: the AP's payload bytes                   */
+    uint32_t hdr;                                                     /* kApFirst: rtp_ap_payload_hdr                       */
+    bool marker;                                                      /* kApFirst: its last unit ends its access unit       */
+    uint64_t out_bytes, packets;                                      /* the lane's share of the output and of the packets  */
+};
+
+__device__ __forceinline__ ApLane ap_groups(const RtpArgs& a, uint64_t k, bool in, const NalEval& x)
+{
+    __shared__ uint32_t s_pre[kRtpNalsPerBlock + 1];                  /* the weights in front of lane t               */
+    __shared__ uint32_t s_au[kRtpNalsPerBlock];
+    __shared__ uint32_t s_hm[kRtpNalsPerBlock];                       /* h0 | h1 << 8 | marker << 16                  */
+    __shared__ uint16_t s_next[kRtpNalsPerBlock];
+    __shared__ uint8_t s_known[kRtpNalsPerBlock], s_start[kRtpNalsPerBlock];
+    const uint32_t t = threadIdx.x;
+    const uint64_t base = k - t, left = a.n_nals - base;              /* (the workgroup has at least one NAL)         */
+    const uint32_t hi = left < (uint64_t)kRtpNalsPerBlock ? (uint32_t)left : (uint32_t)kRtpNalsPerBlock;
+    const uint32_t w = in ? rtp_ap_weight(x.bad ? 2 : x.L) : 0u;
+    uint64_t wv[1] = {w}, ex[1], tot[1];
+    block_scan<1, kRtpPlanLanes>(wv, ex, tot);
+    s_pre[t] = (uint32_t)ex[0];
+    if (t == 0) s_pre[kRtpNalsPerBlock] = (uint32_t)tot[0];
+    s_au[t] = in && a.nal_au ? a.nal_au[k] : 0u;
+    s_hm[t] = x.h0 | x.h1 << 8 | (x.marker ? 1u << 16 : 0u);
+    __syncthreads();
+    uint32_t next = t + 1;
+    bool known = false;
+    if (in) {
+        next = rtp_group_next(t, hi, a.q.mp, [&](uint32_t j) { return (uint64_t)s_pre[j]; }, [&](uint32_t j) { return s_au[j]; });
+        known = t == 0 || s_au[t] != s_au[t - 1] || rtp_ap_loner(w, a.q.mp) || rtp_ap_loner(s_pre[t] - s_pre[t - 1], a.q.mp);
+    }
+    s_next[t] = (uint16_t)next;
+    s_known[t] = known; s_start[t] = known;
+    __syncthreads();
+    if (known)
+        for (uint32_t j = next; j < hi && !s_known[j]; j = s_next[j]) s_start[j] = 1;
+    __syncthreads();
+    ApLane r;
+    r.kind = kOwn; r.pay = 0; r.hdr = 0; r.marker = false; r.out_bytes = 0; r.packets = 0;
+    if (!in) return r;
+    if (!s_start[t]) {
+        r.kind = kApLater; r.out_bytes = w;
+    } else if (next - t >= 2u) {
+        r.kind = kApFirst; r.pay = kRtpApHead + (s_pre[next] - s_pre[t]);
+        uint32_t acc = kRtpApFoldStart;
+        for (uint32_t j = t; j < next; ++j) acc = rtp_ap_fold(acc, s_hm[j] & 0xFFu, (s_hm[j] >> 8) & 0xFFu);
+        r.hdr = rtp_ap_payload_hdr(acc);
+        r.marker = (s_hm[next - 1] >> 16) != 0;
+        r.out_bytes = (uint64_t)a.q.fr + kRtpHeader + kRtpApHead + w; r.packets = 1;
+    } else {
+        r.out_bytes = x.u.out_bytes; r.packets = x.u.packets;
+    }
+    return r;
+}
+
+template <bool kAp>
 __global__ __launch_bounds__(kRtpPlanLanes) void k_rtp_count(RtpArgs a)
 {
     const uint64_t k = (uint64_t)blockIdx.x * kRtpNalsPerBlock + threadIdx.x;
     uint64_t v[4] = {0, 0, 0, 0};
     uint64_t bad = 0;
-    if (k < a.n_nals) {
-        const NalEval x = eval_nal(a, k);
-        if (x.bad) bad = k + 1;
-        else { v[0] = x.u.out_bytes; v[1] = x.u.packets; v[2] = x.L; v[3] = x.u.fu ? 1 : 0; }
+    if constexpr (!kAp) {
+        if (k < a.n_nals) {
+            const NalEval x = eval_nal<false>(a, k);
+            if (x.bad) bad = k + 1;
+            else { v[0] = x.u.out_bytes; v[1] = x.u.packets; v[2] = x.L; v[3] = x.u.fu ? 1 : 0; }
+        }
+    } else {
+        const bool in = k < a.n_nals;
+        NalEval x;
+        x.start = 0; x.L = 0; x.ts = 0; x.bad = false; x.marker = false; x.h0 = x.h1 = 0;
+        if (in) x = eval_nal<true>(a, k);
+        const ApLane g = ap_groups(a, k, in, x);
+        if (in) {
+            if (x.bad) bad = k + 1;                                   /* FU NALs, and in the high word the APs */
+            else { v[0] = g.out_bytes; v[1] = g.packets; v[2] = x.L; v[3] = (g.kind == kOwn && x.u.fu ? 1ull : 0ull) | (g.kind == kApFirst ? 1ull << 32 : 0ull); }
+        }
     }
     bad = block_min_nonzero(bad);
     uint64_t ex[4], tot[4];
@@ -121,11 +218,12 @@ __global__ __launch_bounds__(kPlanLanes) void k_rtp_scan(RtpArgs a, uint64_t blo
         hbs_summary s;
         s.nal_count = packets; s.nal_found = a.n_nals; s.rbsp_bytes = carry[2]; s.stream_bytes = total;
         s.stop_reason = 0; s.error = err;
-        s.reserved[0] = bad; s.reserved[1] = packets; s.reserved[2] = carry[3];
+        s.reserved[0] = bad; s.reserved[1] = packets; s.reserved[2] = carry[3];      /* (APs << 32 | FU NALs: both below 2^32) */
         *a.summary = s;
     }
 }
 
+template <bool kAp>
 __global__ __launch_bounds__(kRtpPlanLanes) void k_rtp_place(RtpArgs a)
 {
     if (a.ctl[0] != 0) return;
@@ -134,15 +232,29 @@ __global__ __launch_bounds__(kRtpPlanLanes) void k_rtp_place(RtpArgs a)
     uint64_t v[2] = {0, 0};
     NalEval x;
     x.start = 0; x.L = 0; x.ts = 0; x.marker = false;
-    if (in) {
-        x = eval_nal(a, k);
-        v[0] = x.u.out_bytes; v[1] = x.u.packets;
+    [[maybe_unused]] ApLane g;
+    if constexpr (!kAp) {
+        if (in) {
+            x = eval_nal<false>(a, k);
+            v[0] = x.u.out_bytes; v[1] = x.u.packets;
+        }
+    } else {
+        x.bad = false; x.h0 = x.h1 = 0;
+        if (in) x = eval_nal<true>(a, k);
+        g = ap_groups(a, k, in, x);
+        v[0] = g.out_bytes; v[1] = g.packets;
     }
     uint64_t off[2], tot[2];
     block_scan<2, kRtpPlanLanes>(v, off, tot);
     if (!in) return;
     const unsigned long long* p = a.part + (uint64_t)blockIdx.x * 8;
     off[0] += p[0]; off[1] += p[1];
+    if constexpr (kAp) {
+        if (g.kind == kApLater) off[1] -= 1;                          /* the packet its group's first unit opened */
+        if (g.kind == kApFirst) x.marker = g.marker;
+        a.rec_ap[k] = g.pay | g.hdr << 16;
+        x.L |= (unsigned long long)g.kind << kKindShift;             /* (L is below 2^46: the output fits out_cap) */
+    }
     a.rec_out[k] = off[0]; a.rec_pkt[k] = off[1];
     a.rec_src[k] = x.start; a.rec_len[k] = x.L;
     a.rec_tm[k] = (unsigned long long)x.ts | (x.marker ? kMarker : 0ull);
@@ -184,13 +296,32 @@ __device__ __forceinline__ uint64_t packet_of(uint64_t q, uint32_t P)
  * output), from the rule; ip: the NAL the chunk's first byte lies in (every NAL has at least 14 output bytes, so the byte lies
  * in that NAL or in one of the two behind it).  Every load is issued whatever the byte turns out to be -- the NAL's two header
  * bytes and its record exist for every NAL -- so that the loads of several bytes a lane are in flight together. */
-__device__ __forceinline__ uint32_t chunk_byte(const RtpArgs& a, const TileNals& tn, uint32_t ip, uint64_t cur)
+/* ... with HBS_RTP_AGGREGATE a unit of an AP has as few as 4 output bytes, so the byte lies in NAL ip or in one of the four
+ * behind it, of the tile's cnt: found by search */
+template <bool kAp>
+__device__ __forceinline__ uint32_t chunk_byte(const RtpArgs& a, const TileNals& tn, uint32_t ip, uint32_t cnt, uint64_t cur)
 {
-    ip += cur >= tn.out(ip + 1) ? 1u : 0u;
-    ip += cur >= tn.out(ip + 1) ? 1u : 0u;
+    if constexpr (!kAp) {
+        ip += cur >= tn.out(ip + 1) ? 1u : 0u;
+        ip += cur >= tn.out(ip + 1) ? 1u : 0u;
+    } else {
+        ip = tn.find(ip, ip + 4u < cnt - 1u ? ip + 4u : cnt - 1u, cur);
+        const uint64_t len = tn.len(ip);
+        const uint32_t kind = (uint32_t)(len >> kKindShift);
+        if (kind != kOwn) {
+            const uint64_t S = tn.src(ip);
+            const uint32_t q = (uint32_t)(cur - tn.out(ip)), L = (uint32_t)len;      /* (an AP has fewer than 2^16 + 14 bytes) */
+            if (kind == kApLater) return q < kRtpApSize ? ((q == 0 ? L >> 8 : L) & 0xFFu) : a.src[S + (q - kRtpApSize)];
+            const uint32_t head = rtp_ap_first_head(a.q);
+            if (q >= head) return a.src[S + (q - head)];
+            const unsigned long long tm = a.rec_tm[tn.j0 + ip], pkt = a.rec_pkt[tn.j0 + ip];
+            const uint32_t ap = a.rec_ap[tn.j0 + ip];
+            return rtp_ap_head_byte(a.q, (tm & kMarker) != 0, ap & 0xFFFFu, pkt, (uint32_t)tm, ap >> 16, L, q);
+        }
+    }
     const uint32_t P = rtp_full_packet_bytes(a.q);
     const uint64_t O = tn.out(ip), E = tn.out(ip + 1), S = tn.src(ip);
-    const bool fu = tn.len(ip) > a.q.mp;
+    const bool fu = (kAp ? tn.len(ip) & kLenMask : tn.len(ip)) > a.q.mp;
     const uint64_t q = cur - O;
     const uint64_t p = fu ? packet_of(q, P) : 0;                     /* the packet of the NAL, where it begins, its bytes */
     const uint64_t pstart = O + p * P;
@@ -204,6 +335,7 @@ __device__ __forceinline__ uint32_t chunk_byte(const RtpArgs& a, const TileNals&
     return payload ? pay : hb;
 }
 
+template <bool kAp>
 __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
 {
     __shared__ unsigned long long s_out[kLdsNals + 1];
@@ -233,6 +365,7 @@ __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
     __syncthreads();
     const uint32_t P = rtp_full_packet_bytes(a.q), F = a.q.mp - 3u, mp = a.q.mp;
     const uint32_t head_single = rtp_head_bytes(a.q, false), head_fu = rtp_head_bytes(a.q, true);
+    [[maybe_unused]] const uint32_t head_ap = rtp_ap_first_head(a.q);
     uint32_t lo = 0;
 #pragma unroll 1
     for (int b = 0; b < kChunks; b += kBatch) {
@@ -252,7 +385,14 @@ __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
                     const uint64_t q = o - tn.out(lo), S = tn.src(lo);
                     uint64_t s;
                     bool ok;
-                    if (tn.len(lo) <= mp) {
+                    uint64_t len = tn.len(lo);
+                    [[maybe_unused]] uint32_t kind = kOwn;
+                    if constexpr (kAp) { kind = (uint32_t)(len >> kKindShift); len &= kLenMask; }
+                    if (kAp && kind != kOwn) {
+                        const uint32_t head = kind == kApFirst ? head_ap : kRtpApSize;
+                        ok = q >= head;
+                        s = S + (q - head);
+                    } else if (len <= mp) {
                         ok = q >= head_single;
                         s = S + (q - head_single);
                     } else {
@@ -291,7 +431,7 @@ __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
                 const uint32_t e = s_slow[c];
                 r[u] = (e & 0xFFFu) << 4;
                 len[u] = tlen - r[u] < 16 ? tlen - r[u] : 16u;
-                if (b < len[u]) v[u] = chunk_byte(a, tn, e >> 12, t0 + r[u] + b);
+                if (b < len[u]) v[u] = chunk_byte<kAp>(a, tn, e >> 12, cnt, t0 + r[u] + b);
             }
         }
 #pragma unroll
@@ -310,20 +450,28 @@ __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
 
 } // namespace
 
+/* the call's launches with (kAp) and without HBS_RTP_AGGREGATE */
+template <bool kAp>
+static void launch_rtp_kernels(const RtpArgs& a, uint64_t blocks, hipStream_t st)
+{
+    if (blocks) hipLaunchKernelGGL(k_rtp_count<kAp>, dim3((unsigned)blocks), dim3(kRtpPlanLanes), 0, st, a);
+    hipLaunchKernelGGL(k_rtp_scan, dim3(1), dim3(kPlanLanes), 0, st, a, blocks);
+    if (a.out && blocks) {
+        hipLaunchKernelGGL(k_rtp_place<kAp>, dim3((unsigned)blocks), dim3(kRtpPlanLanes), 0, st, a);
+        if (a.tiles) {
+            hipLaunchKernelGGL(k_rtp_tiles, dim3((unsigned)((a.tiles + 1 + 255) / 256)), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_rtp_copy<kAp>, dim3((unsigned)a.tiles), dim3(kRT), 0, st, a);
+        }
+    }
+}
+
 hipError_t launch_rtp_pack(const RtpArgs& a, hipStream_t st)
 {
     const uint64_t blocks = (a.n_nals + kRtpNalsPerBlock - 1) / kRtpNalsPerBlock;
     const hipError_t e = begin_launches(a.ev_begin, st);
     if (e != hipSuccess) return e;
-    if (blocks) hipLaunchKernelGGL(k_rtp_count, dim3((unsigned)blocks), dim3(kRtpPlanLanes), 0, st, a);
-    hipLaunchKernelGGL(k_rtp_scan, dim3(1), dim3(kPlanLanes), 0, st, a, blocks);
-    if (a.out && blocks) {
-        hipLaunchKernelGGL(k_rtp_place, dim3((unsigned)blocks), dim3(kRtpPlanLanes), 0, st, a);
-        if (a.tiles) {
-            hipLaunchKernelGGL(k_rtp_tiles, dim3((unsigned)((a.tiles + 1 + 255) / 256)), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(k_rtp_copy, dim3((unsigned)a.tiles), dim3(kRT), 0, st, a);
-        }
-    }
+    if (a.flags & HBS_RTP_AGGREGATE) launch_rtp_kernels<true>(a, blocks, st);
+    else launch_rtp_kernels<false>(a, blocks, st);
     return end_launches(a.ev_end, st);
 }
 

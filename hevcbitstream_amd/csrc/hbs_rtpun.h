@@ -124,6 +124,20 @@ inline RtpuRule rtpu_rule(const hbs_rtp_unpack_params* p)
     return q;
 }
 
+/* hbs_rtp_ap_units_host: rtp_packet_rule, then rtpu_ap_walk over the payload */
+inline int64_t rtp_ap_units_host(const uint8_t* pkt, uint64_t n, uint64_t* off_out, uint64_t* size_out, uint64_t cap)
+{
+    hbs_rtp_packet k;
+    if (rtp_packet_host(pkt, n, &k) != 0 || k.kind != HBS_RTP_AP) return HBS_E_ARG;
+    if (cap && (!off_out || !size_out)) return HBS_E_ARG;
+    uint64_t units = 0, bytes = 0, at = 0;
+    const bool ok = rtpu_ap_walk(RtpBytesAt{pkt}, k.payload_off, k.payload_len, units, bytes, [&](uint64_t off, uint64_t size) {
+        if (at < cap) { off_out[at] = off; size_out[at] = size; }
+        ++at;
+    });
+    return ok ? (int64_t)units : (int64_t)HBS_E_ARG;
+}
+
 /* an RFC 4571 byte stream: a 16-bit big-endian length, then a packet of that many bytes, and so on.  Fills up to `cap` offset /
  * size pairs of the packets (the length fields left out), returns the whole frames, *used_out = the bytes they take.  Stops in
  * front of the first incomplete frame; no length is trusted before it is bounded. */

@@ -399,6 +399,11 @@ hipError_t launch_rtp_unpack(const RtpuArgs& a, hipStream_t st)
 
 extern "C" {
 
+int64_t hbs_rtp_ap_units_host(const uint8_t* pkt, uint64_t n, uint64_t* off_out, uint64_t* size_out, uint64_t cap)
+{
+    return hbs::rtp_ap_units_host(pkt, n, off_out, size_out, cap);
+}
+
 uint64_t hbs_rtp_frames_host(const uint8_t* bytes, uint64_t n, uint64_t* off_out, uint64_t* size_out, uint64_t cap, uint64_t* used_out)
 {
     return hbs::rtp_frames_host(bytes, n, off_out, size_out, cap, used_out);

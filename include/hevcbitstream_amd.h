@@ -111,8 +111,10 @@ typedef struct hbs_ctx hbs_ctx;
  * on the data made on the device -- and may be captured into a HIP graph (hipStreamBeginCapture on the bound stream) after ONE
  * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
- *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack, hbs_rtp_unpack.
- * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py and tests/test_gpu_rtp_unpack.py replay, no
+ *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
+ *   HBS_RTP_AGGREGATE), hbs_rtp_unpack.
+ * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py and
+ * tests/test_gpu_rtp_unpack.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -611,10 +613,22 @@ uint64_t hbs_ts_mux_au_packets_host(uint64_t es_bytes, int time_fields /* 0, 1, 
  * FRAGMENTATION UNITS, when L > mp: the body is the B = L - 2 bytes stream[start + 2, end); n = ceil(B / F) packets (always
  * >= 2, so no FU carries both S and E).  Packet i carries the 2-byte PayloadHdr (h0 & 0x81) | 0x62, h1 (type 49, the NAL's F
  * bit, layer id and TID), then the FU header (i == 0) << 7 | (i == n - 1) << 6 | t, then the body bytes
- * [i F, min((i + 1) F, B)): only the last fragment is short.  No DONL fields (sprop-max-don-diff = 0), no aggregation packets.
+ * [i F, min((i + 1) F, B)): only the last fragment is short.  No DONL fields (sprop-max-don-diff = 0).
  * RTP HEADER, 12 bytes.  0x80, M << 7 | payload_type, the sequence number (seq + j) & 0xFFFF of the call's j-th packet
  * big-endian, the timestamp big-endian, the ssrc big-endian.  M = 1 exactly on the last packet of the last NAL of an access
  * unit: NAL k with k == n_nals - 1 or d_nal_au[k + 1] != d_nal_au[k]; with HBS_RTP_OPEN_END the call's last NAL is exempt.
+ * AGGREGATION PACKETS (RFC 7798 4.4.2), with HBS_RTP_AGGREGATE only; without the flag every byte of output, every table entry
+ * and the summary are what they are without this paragraph.  The call's NALs are cut into GROUPS of consecutive NALs, greedily:
+ * next(i) is the smallest j > i with j == n_nals, j % HBS_RTP_AP_SPAN == 0, a_j != a_i or 2 + sum_{m = i..j} (2 + L_m) > mp; the
+ * group starts are g_0 = 0 and g_{r+1} = next(g_r).  The cut at every multiple of HBS_RTP_AP_SPAN (256) in the call's NAL
+ * numbering is part of the definition: it costs at most one packet more per 256 NALs, no plan workgroup waits for another
+ * because of it, and a call split at a multiple of 256 NALs makes the same packets.  A group never crosses an access unit, so
+ * its NALs share one timestamp.  A group of one NAL is sent as above (single NAL unit packet or FUs).  A group of m >= 2 NALs is
+ * ONE aggregation packet: the RTP header, the 2-byte PayloadHdr F << 7 | 48 << 1 | layer >> 5, (layer & 31) << 3 | tid with F the
+ * OR of (h0 >> 7), layer the lowest (h0 & 1) << 5 | h1 >> 3 and tid the lowest h1 & 7 of its NALs, then for each NAL in order a
+ * big-endian 16-bit L and its L bytes verbatim.  No DONL fields.  For mp < 10 no AP can exist.  M = 1 on an AP exactly when its
+ * last unit ends its access unit (HBS_RTP_OPEN_END exempts the call's last NAL here too); an AP takes one sequence number.
+ * The output is never larger than without the flag: an AP of m units saves (m - 1)(framing + 12) - 2 - 2m >= 6 bytes.
  * ACCESS UNITS AND TIMES.  a_k = d_nal_au[k] - d_nal_au[0]; every step d_nal_au[k] - d_nal_au[k - 1] must be 0 or 1 and
  * a_k < n_aus, so a range is passed by pointer offset into the tables, like a GOP cut to hbs_ts_mux.  d_nal_au == NULL: the
  * whole batch is AU 0 and n_aus is ignored.  The timestamp of AU a, modulo 2^32, is ts_base + (uint32_t)d_pts[a] when d_pts is
@@ -626,11 +640,14 @@ uint64_t hbs_ts_mux_au_packets_host(uint64_t es_bytes, int time_fields /* 0, 1, 
  * n_nals + 1 entries) = the output offset where NAL k's first packet begins, its length field included, entry n_nals the
  * total; d_nal_packet[k] (optional, n_nals + 1) = the number of NAL k's first packet, entry n_nals the packet count.  All
  * packets of a NAL but its last take framing + 12 + mp bytes, so the two tables and the rule give every packet's offset
- * without a table per packet.  d_out == NULL: plan only, the summary alone is written.  n_nals == 0 is valid: an empty output,
+ * without a table per packet.  With HBS_RTP_AGGREGATE the NALs of an AP share a packet: d_nal_packet[k] = the number of the
+ * packet that carries NAL k's first byte, the same for all units of an AP; d_nal_off[k] = where NAL k's share of the output
+ * begins -- for the first NAL of a packet the packet's beginning (length field included), for a later unit of an AP its 16-bit
+ * size field.  Packet p begins at d_nal_off of the first k with d_nal_packet[k] == p.  d_out == NULL: plan only, the summary alone is written.  n_nals == 0 is valid: an empty output,
  * entry 0 of both tables 0.
  *   d_summary   nal_count = packets, nal_found = n_nals, rbsp_bytes = NAL bytes carried (the sum of L), stream_bytes = output
  *               bytes, stop_reason = 0, reserved[1] = packets (the next call's seq is (seq + reserved[1]) & 0xFFFF),
- *               reserved[2] = NALs sent as FUs.
+ *               reserved[2] = aggregation packets << 32 | NALs sent as FUs (the high word is 0 without HBS_RTP_AGGREGATE).
  *               error = HBS_E_ARG with reserved[0] = 1 + the lowest offending NAL when a NAL has L < 2, has t >= 48 (48 to 50
  *               mean AP / FU / PACI to a receiver: filter such NALs out first with hbs_filter_annexb), has an index entry that
  *               is inconsistent by the filter's definition (start > end, end > stream_bytes, start_k < end_{k-1}), breaks an
@@ -638,16 +655,16 @@ uint64_t hbs_ts_mux_au_packets_host(uint64_t es_bytes, int time_fields /* 0, 1, 
  *               the other counts mean nothing then.  Else HBS_E_CAPACITY when out_cap is below the output; the counts are
  *               right.  On either error nothing is written but the summary.
  * Refused with HBS_E_ARG at once, before anything is written: params NULL or out of range (max_payload outside 4..65523,
- * payload_type outside 0..127, framing not 0 or 2, unknown flags, seq above 65535), n_nals above 2^32 - 1, out_cap above 2^46
+ * payload_type outside 0..127, framing not 0 or 2, flags other than HBS_RTP_OPEN_END | HBS_RTP_AGGREGATE, seq above 65535), n_nals above 2^32 - 1, out_cap above 2^46
  * with a d_out, missing or misaligned pointers.
  * Nothing outside [d_out, d_out + output bytes), the n_nals + 1 entries of the two tables and the summary is stored; no load
  * touches a 16-byte granule that holds no byte of the stream, and a NAL's first byte is read only after its entry has been
- * checked; no host synchronisation; scratch comes from the context's workspace (40 bytes a NAL, and 8 bytes per 64 KiB output
- * tile of what out_cap and the stream can hold).
+ * checked; no host synchronisation; scratch comes from the context's workspace (40 bytes a NAL, 44 with HBS_RTP_AGGREGATE, and 8 bytes per
+ * 64 KiB output tile of what out_cap and the stream can hold).
  * Alignment: d_stream, d_out, d_summary 16 bytes; d_index, d_pts, d_nal_off, d_nal_packet 8 bytes; d_nal_au 4 bytes.
- * STATED LIMITS: no aggregation packets (every NAL has a packet of its own); no DONL fields, no interleaving; no PACI; no
- * header extension and no CSRC entries on the sending side; no RTCP; no SRTP.  The way back is hbs_rtp_unpack (below);
- * hbs_rtp_packet_host reads one packet on the host.
+ * STATED LIMITS: no DONL fields, no interleaving; no PACI; no header extension and no CSRC entries on the sending side; no
+ * RTCP; no SRTP.  The way back is hbs_rtp_unpack (below), which reads the output with and without HBS_RTP_AGGREGATE;
+ * hbs_rtp_packet_host reads one packet on the host and hbs_rtp_ap_units_host the units of an aggregation packet.
  *
  * Host side, plain C, no GPU involved.
  * hbs_rtp_nal_packets_host: the packets of a NAL of nal_bytes bytes; 0 for nal_bytes < 2 or a max_payload out of range.
@@ -657,6 +674,10 @@ uint64_t hbs_ts_mux_au_packets_host(uint64_t es_bytes, int time_fields /* 0, 1, 
  * fu_end, nal_type from the FU header, nal_header = the two reconstructed header bytes of the NAL, nal_off / nal_len = the
  * fragment behind the three bytes), 48 an AP, anything else HBS_RTP_OTHER (a payload below 2 bytes: nal_type -1).  0, or
  * HBS_E_ARG for a version other than 2, NULL pointers or a packet shorter than its own fields say.
+ * hbs_rtp_ap_units_host: the units of the aggregation packet pkt[0, n) (without a length field): returns their count and fills
+ * the offset within pkt and the size of the first `cap` of them (off_out and size_out may be NULL when cap is 0).  HBS_E_ARG when
+ * hbs_rtp_packet_host refuses the packet, when its kind is not HBS_RTP_AP, or when rule 4 of hbs_rtp_unpack (below) calls it a
+ * fault: no unit, a size that does not fit, a size below 2, a unit of type 48 or above.  No size is used before it is bounded.
  */
 typedef struct hbs_rtp_params {   /* HOST memory, 32 bytes */
     int32_t  max_payload;   /* most RTP payload bytes in a packet (behind the 12-byte header): 4 .. 65523 */
@@ -669,6 +690,8 @@ typedef struct hbs_rtp_params {   /* HOST memory, 32 bytes */
     uint32_t ts_step;       /* with d_pts == NULL: the timestamp of AU a is ts_base + a * ts_step */
 } hbs_rtp_params;
 #define HBS_RTP_OPEN_END 1u  /* the call's last NAL does not end its access unit: no marker bit on its last packet */
+#define HBS_RTP_AGGREGATE 4u /* consecutive small NALs of an access unit share an aggregation packet                  */
+#define HBS_RTP_AP_SPAN 256  /* ... and no aggregation packet reaches across a multiple of this in the call's NAL numbering */
 
 #define HBS_RTP_SINGLE 0     /* hbs_rtp_packet.kind */
 #define HBS_RTP_FU     1
@@ -694,12 +717,13 @@ int hbs_rtp_pack(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
                  hbs_summary* d_summary);
 uint64_t hbs_rtp_nal_packets_host(uint64_t nal_bytes, int max_payload);
 int hbs_rtp_packet_host(const uint8_t* pkt, uint64_t n, hbs_rtp_packet* out);
+int64_t hbs_rtp_ap_units_host(const uint8_t* pkt, uint64_t n, uint64_t* off_out, uint64_t* size_out, uint64_t cap);
 
 /*
  * ---- RTP packets (RFC 7798) -> Annex-B: single NAL unit packets, aggregation packets, fragmentation units ---------------
  * hbs_rtp_unpack is the receiver's side of the third transport: a table of RTP packets in device memory becomes the Annex-B
  * stream of their NAL units, with the index hbs_parse_headers* and hbs_filter_annexb take, the AU number of every NAL and the
- * timestamp of every AU.  hbs_rtp_pack never makes aggregation packets; a receiver meets them, and this call reads them.
+ * timestamp of every AU.  hbs_rtp_pack makes aggregation packets only with HBS_RTP_AGGREGATE; this call reads them either way.
  *
  * PACKETS.  Packet p is d_in[d_pkt_off[p], d_pkt_off[p] + d_pkt_size[p]), a raw RTP packet without a length field.  Packets may
  * lie anywhere in the buffer, in any order, and may overlap, like the samples of hbs_lenpref_to_annexb; the output follows the
