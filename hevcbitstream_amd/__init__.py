@@ -17,7 +17,8 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST, aud_nal,
                   RTP_PARAMS, RTP_PACKET, RTP_OPEN_END, RTP_AGGREGATE, RTP_AP_SPAN, RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER,
                   rtp_params, rtp_nal_packets, rtp_packet, rtp_ap_units, rtp_packet_offsets,
-                  RTP_UNPACK_PARAMS, RTPU_MATCH_SSRC, rtp_unpack_params, rtp_frames)
+                  RTP_UNPACK_PARAMS, RTPU_MATCH_SSRC, rtp_unpack_params, rtp_frames,
+                  RTP_ORDER_PARAMS, RTPO_MATCH_SSRC, RTPO_AFTER, rtp_order_params)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
            "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
@@ -31,4 +32,5 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "AUINS_AUD", "AUINS_PARAM_SETS", "AUINS_PARAM_SETS_FIRST", "aud_nal",
            "RTP_PARAMS", "RTP_PACKET", "RTP_OPEN_END", "RTP_AGGREGATE", "RTP_AP_SPAN", "RTP_SINGLE", "RTP_FU", "RTP_AP", "RTP_OTHER",
            "rtp_params", "rtp_nal_packets", "rtp_packet", "rtp_ap_units", "rtp_packet_offsets",
-           "RTP_UNPACK_PARAMS", "RTPU_MATCH_SSRC", "rtp_unpack_params", "rtp_frames"]
+           "RTP_UNPACK_PARAMS", "RTPU_MATCH_SSRC", "rtp_unpack_params", "rtp_frames",
+           "RTP_ORDER_PARAMS", "RTPO_MATCH_SSRC", "RTPO_AFTER", "rtp_order_params"]

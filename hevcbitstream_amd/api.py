@@ -56,6 +56,10 @@ RTP_SINGLE, RTP_FU, RTP_AP, RTP_OTHER = 0, 1, 2, 3
 # layout of hbs_rtp_unpack_params and the flags of hbs_rtp_unpack
 RTP_UNPACK_PARAMS = np.dtype([("payload_type", "<i4"), ("startcode_bytes", "<i4"), ("flags", "<u4"), ("ssrc", "<u4")])
 RTPU_MATCH_SSRC = 1
+# layout of hbs_rtp_order_params and the flags of hbs_rtp_order
+RTP_ORDER_PARAMS = np.dtype([("payload_type", "<i4"), ("flags", "<u4"), ("ssrc", "<u4"), ("reserved", "<u4"), ("max_span", "<u8"),
+                             ("after_ext", "<u8")])
+RTPO_MATCH_SSRC, RTPO_AFTER = 1, 2
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -88,7 +92,7 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
            "hbs_au_insert", "hbs_aud_nal_host",
            "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host", "hbs_rtp_ap_units_host",
-           "hbs_rtp_unpack", "hbs_rtp_frames_host"]
+           "hbs_rtp_unpack", "hbs_rtp_frames_host", "hbs_rtp_order"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -245,6 +249,8 @@ def load_library():
                                    C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.hbs_rtp_frames_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.hbs_rtp_frames_host.restype = C.c_uint64
+    lib.hbs_rtp_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     _lib = lib
     return lib
 
@@ -363,6 +369,13 @@ def rtp_unpack_params(payload_type=96, startcode_bytes=4, flags=0, ssrc=0):
     """an hbs_rtp_unpack_params record (ndarray[RTP_UNPACK_PARAMS] of one, host memory)"""
     p = np.zeros(1, dtype=RTP_UNPACK_PARAMS)
     p[0] = (payload_type, startcode_bytes, flags, ssrc)
+    return p
+
+
+def rtp_order_params(payload_type=96, flags=0, ssrc=0, max_span=1 << 20, after_ext=0):
+    """an hbs_rtp_order_params record (ndarray[RTP_ORDER_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=RTP_ORDER_PARAMS)
+    p[0] = (payload_type, flags, ssrc, 0, max_span, after_ext)
     return p
 
 
@@ -1157,6 +1170,63 @@ class Context:
             raise HbsError("hbs_rtp_unpack: error %d" % int(s["error"]))
         return (out[:need], index[: nals * NAL_ENTRY.itemsize], nal_au[: nals * 4].cpu().numpy().view(np.uint32).copy(),
                 au_ts[: aus * 8].cpu().numpy().view(np.uint64).copy(), s)
+
+    def rtp_order_async(self, data, in_bytes, pkt_off, pkt_size, n_packets, params, off_out, size_out, src_out, ext_out, summary,
+                        out_cap=None):
+        """Enqueue hbs_rtp_order on the current torch stream.  data / pkt_off / pkt_size / off_out / size_out / src_out / ext_out /
+        summary are device tensors (src_out, ext_out may be None; off_out and size_out None: plan only); params is an
+        ndarray[RTP_ORDER_PARAMS] of one in host memory.  out_cap (entries) defaults to what the tensors hold.  Returns the
+        call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            caps = [x.numel() * x.element_size() // w for x, w in ((off_out, 8), (size_out, 8), (src_out, 4), (ext_out, 8)) if x is not None]
+            out_cap = min(caps) if caps else 0
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=RTP_ORDER_PARAMS)
+        return self.lib.hbs_rtp_order(self.h, p(data) if in_bytes else None, int(in_bytes), p(pkt_off) if n_packets else None,
+                                      p(pkt_size) if n_packets else None, int(n_packets),
+                                      params.ctypes.data_as(C.c_void_p) if params is not None else None, p(off_out), p(size_out),
+                                      p(src_out), p(ext_out), int(out_cap), p(summary))
+
+    def rtp_order(self, data, pkt_off, pkt_size, in_bytes=None, **params):
+        """Convenience: the table of the RTP packets data[off_p, off_p + size_p) in arrival order (data: device uint8 tensor;
+        pkt_off / pkt_size: uint64 arrays, host or device tensors of their bytes) by sequence number, each packet once; params:
+        the keywords of rtp_order_params (max_span defaults to n_packets + 65536).  Plans first, allocates the exact outputs,
+        runs.  Returns (off device tensor, size device tensor -- the bytes of uint64 tables, what rtp_unpack takes --, src
+        ndarray[uint32], ext ndarray[uint64], summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x):
+            if isinstance(x, np.ndarray):
+                a = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8)
+                return (t.from_numpy(a.copy()).to(dev) if a.size else t.zeros(16, dtype=t.uint8, device=dev)), len(x)
+            return x, x.numel() * x.element_size() // 8
+        d_off, n = dv(pkt_off)
+        d_size, n2 = dv(pkt_size)
+        if n != n2:
+            raise HbsError("hbs_rtp_order: %d packet offsets, %d sizes" % (n, n2))
+        params.setdefault("max_span", n + 65536)
+        prm = rtp_order_params(**params)
+        nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        args = (data, nbytes, d_off, d_size, n, prm)
+        self._check(self.rtp_order_async(*args, None, None, None, None, summary), "hbs_rtp_order")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            if int(s["reserved"][0]):
+                raise HbsError("hbs_rtp_order: error %d (packet %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+            raise HbsError("hbs_rtp_order: error %d (span %d, max_span %d)" % (int(s["error"]), int(s["stream_bytes"]), int(prm["max_span"][0])))
+        kept = int(s["nal_count"])
+        off, size, ext = (t.empty(max(kept, 1) * 8, dtype=t.uint8, device=dev) for _ in range(3))
+        src = t.empty(max(kept, 1) * 4, dtype=t.uint8, device=dev)
+        self._check(self.rtp_order_async(*args, off, size, src, ext, summary, out_cap=kept), "hbs_rtp_order")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_rtp_order: error %d" % int(s["error"]))
+        return (off[: kept * 8], size[: kept * 8], src[: kept * 4].cpu().numpy().view(np.uint32).copy(),
+                ext[: kept * 8].cpu().numpy().view(np.uint64).copy(), s)
 
     # ---- access units -----------------------------------------------------------------
 

@@ -25,6 +25,7 @@
 #include "hbs_auins.h"
 #include "hbs_rtp.h"
 #include "hbs_rtpun.h"
+#include "hbs_rtpord.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -43,8 +44,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kMws    hbs_ts_mux's scratch
  * kIws    hbs_au_insert's scratch
  * kRws    hbs_rtp_pack's scratch
- * kUws    hbs_rtp_unpack's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kBufs };
+ * kUws    hbs_rtp_unpack's scratch
+ * kOws    hbs_rtp_order's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -800,6 +802,37 @@ int hbs_rtp_unpack(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_rtp_unpack(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_unpack");
+}
+
+int hbs_rtp_order(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
+                  const uint64_t* d_pkt_off, const uint64_t* d_pkt_size, uint64_t n_packets,
+                  const hbs_rtp_order_params* params, uint64_t* d_off_out, uint64_t* d_size_out,
+                  uint32_t* d_src_out, uint64_t* d_ext_out, uint64_t out_cap, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_rtp_order_params) == 32, "hbs_rtp_order_params layout");
+    if (!c || !d_summary || !hbs::rtpo_params_ok(params) || n_packets > hbs::kRtpoMaxPackets) return HBS_E_ARG;
+    if (n_packets && (!d_pkt_off || !d_pkt_size || (in_bytes && !d_in))) return HBS_E_ARG;
+    if ((d_off_out == nullptr) != (d_size_out == nullptr) || (!d_off_out && (d_src_out || d_ext_out))) return HBS_E_ARG;
+    if (misaligned(d_in, 15) || misaligned(d_summary, 15) || misaligned(d_pkt_off, 7) || misaligned(d_pkt_size, 7) ||
+        misaligned(d_off_out, 7) || misaligned(d_size_out, 7) || misaligned(d_ext_out, 7) || misaligned(d_src_out, 3)) {
+        snprintf(c->err, sizeof(c->err), "input/summary pointers must be 16-byte aligned, packet tables and 64-bit output tables 8-byte, table positions 4-byte");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::RtpoArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_in; a.n = in_bytes;
+    a.pkt_off = reinterpret_cast<const unsigned long long*>(d_pkt_off);
+    a.pkt_size = reinterpret_cast<const unsigned long long*>(d_pkt_size); a.n_packets = n_packets;
+    a.q = hbs::rtpo_rule(params);
+    a.off_out = reinterpret_cast<unsigned long long*>(d_off_out); a.size_out = reinterpret_cast<unsigned long long*>(d_size_out);
+    a.src_out = d_src_out; a.ext_out = reinterpret_cast<unsigned long long*>(d_ext_out);
+    a.out_cap = out_cap; a.summary = d_summary;
+    const int rc = carve(c, c->buf[kOws], "hipMalloc(RTP order scratch)", [&](hbs::Carver& w) { hbs::lay_rtpo(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_rtp_order(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_order");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,

@@ -1,5 +1,5 @@
 /* hbs_plan.h -- device-only: the scans of a "count, scan, place" plan (hbs_filter.hip, hbs_lenpref.hip, hbs_ts.hip,
- * hbs_tsmux.hip, hbs_rtp.hip, hbs_rtpun.hip, hbs_auins.hip): over the lanes of a workgroup the exclusive sums (block_scan) and
+ * hbs_tsmux.hip, hbs_rtp.hip, hbs_rtpun.hip, hbs_rtpord.hip, hbs_auins.hip): over the lanes of a workgroup the exclusive sums (block_scan) and
  * the exclusive maxima (block_excl_max).  A count kernel leaves 8 words a workgroup -- N sums, then a word that says what was
  * wrong -- and one workgroup of kPlanLanes lanes turns the sums into offsets (scan_parts). */
 #ifndef HBS_PLAN_H
@@ -124,6 +124,28 @@ __device__ __forceinline__ uint64_t scan_parts(unsigned long long* part, uint64_
         for (int q = 0; q < N; ++q) carry[q] += tot[q];
     }
     return block_min_nonzero(flag);
+}
+
+/* one workgroup of kPlanLanes: the per-workgroup maxima last[i] become the maxima of the workgroups in front, last[i] =
+ * max(last[0 .. i)) (0, the identity, for i == 0); returns the maximum of all */
+__device__ __forceinline__ uint64_t max_scan_parts(unsigned long long* last, uint64_t blocks)
+{
+    uint64_t run = 0;
+    for (uint64_t seg = 0; seg < blocks; seg += (uint64_t)kPlanLanes * kPlanPer) {
+        const uint64_t i0 = seg + (uint64_t)threadIdx.x * kPlanPer;
+        uint64_t acc = 0;
+        for (int i = 0; i < kPlanPer && i0 + i < blocks; ++i) { const uint64_t x = last[i0 + i]; if (x > acc) acc = x; }
+        uint64_t cur, tot;
+        block_excl_max<uint64_t, 1, kPlanLanes>(&acc, &cur, &tot);
+        if (run > cur) cur = run;
+        for (int i = 0; i < kPlanPer && i0 + i < blocks; ++i) {
+            const uint64_t x = last[i0 + i];
+            last[i0 + i] = cur;
+            if (x > cur) cur = x;
+        }
+        if (tot > run) run = tot;
+    }
+    return run;
 }
 
 } // namespace hbs

@@ -112,9 +112,9 @@ typedef struct hbs_ctx hbs_ctx;
  * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
- *   HBS_RTP_AGGREGATE), hbs_rtp_unpack.
- * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py and
- * tests/test_gpu_rtp_unpack.py replay, no
+ *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order.
+ * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
+ * tests/test_gpu_rtp_unpack.py and tests/test_gpu_rtp_order.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -782,7 +782,7 @@ int64_t hbs_rtp_ap_units_host(const uint8_t* pkt, uint64_t n, uint64_t* off_out,
  * pieces, 8 bytes per 64 KiB of out_cap).
  * Alignment: d_in, d_out, d_summary 16 bytes; d_pkt_off, d_pkt_size, d_index_out, d_au_ts_out 8 bytes; d_nal_au_out 4 bytes.
  * STATED LIMITS: no reordering and no duplicate removal beyond the table's order (a duplicate comes out twice and counts as a
- * break); no DONL fields, no interleaving; no PACI; a packet that is not this stream's and lies inside a chain breaks the
+ * break): hbs_rtp_order (below) makes the table of a receiver's arrival order that this call reads; no DONL fields, no interleaving; no PACI; a packet that is not this stream's and lies inside a chain breaks the
  * chain; no RTCP; no SRTP.
  *
  * Host side, plain C, no GPU involved.
@@ -808,6 +808,81 @@ int hbs_rtp_unpack(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
                    hbs_summary* d_summary);
 uint64_t hbs_rtp_frames_host(const uint8_t* bytes, uint64_t n, uint64_t* off_out, uint64_t* size_out, uint64_t cap,
                              uint64_t* used_out);
+
+/*
+ * ---- RTP packets in arrival order -> the table hbs_rtp_unpack reads: by sequence number, without duplicates ---------------
+ * hbs_rtp_order is the jitter-buffer step in front of hbs_rtp_unpack: a table of RTP packets in the order a receiver got them
+ * -- late packets, duplicates, 16-bit sequence numbers that wrap -- becomes the table of the same packets in the sender's
+ * order, each once.  No packet byte is moved: the output is a permutation of a subset of the input table's entries.
+ *
+ * PACKETS are table entries exactly as hbs_rtp_unpack takes them: packet p is d_in[d_pkt_off[p], d_pkt_off[p] + d_pkt_size[p]),
+ * anywhere in d_in, in any order, overlapping allowed.  The TABLE order is the arrival order.
+ *
+ * THE RULE, in this order.
+ * 1. ENTRY FAULT and HEADER FAULT: steps 1 and 2 of hbs_rtp_unpack's packet rule, by the same function (rtp_packet_rule): off +
+ *    size wraps or exceeds in_bytes; fewer than 12 bytes, a version other than 2, shorter than its own CSRC / extension / padding
+ *    fields say, a fragmentation unit's payload below 3 bytes.  Any fault: error = HBS_E_ARG and reserved[0] = 1 + the lowest
+ *    faulty entry, the other counts are 0 and nothing but the summary is written.  Every entry is bounded before a byte of its
+ *    packet is read.  A table that passes here never produces a header fault in hbs_rtp_unpack (its aggregation packet and FU
+ *    type faults look at the payload, which this call does not).
+ * 2. OTHER: the payload type differs from params->payload_type, or, with HBS_RTPO_MATCH_SSRC, the ssrc differs from
+ *    params->ssrc.  The packet is left out of the output and of the sequence.
+ * 3. EXTENDED SEQUENCE NUMBER of the accepted packets (neither faulty nor OTHER) a_0, a_1, ... in TABLE order.  With sext16(x) =
+ *    the low 16 bits of x read as a signed number (sext16(0x8000) = -32768):
+ *      ext(a_0) = 2^48 + seq(a_0), or, with HBS_RTPO_AFTER, params->after_ext + sext16(seq(a_0) - params->after_ext);
+ *      ext(a_i) = ext(a_(i-1)) + sext16(seq(a_i) - seq(a_(i-1))).
+ *    With n_packets below 2^32 no value leaves (2^47, 2^49 + 2^48); after_ext must lie in [2^48, 2^62].  (A prefix sum of signed
+ *    16-bit differences: no sequential walk.)  The numbers are the sender's whenever any two packets that arrive next to each
+ *    other lie fewer than 2^15 apart in the sender's order; the call cannot see where that does not hold.
+ * 4. LATE (with HBS_RTPO_AFTER only): ext <= params->after_ext.  The packet is dropped.
+ * 5. DUPLICATE: an accepted packet that is not late and whose ext equals that of an accepted, not late packet earlier in the
+ *    table.  It is dropped: the first arrival wins.  Contents are not compared.
+ * 6. KEPT: every other accepted packet.
+ *
+ * THE OUTPUT.  The kept packets in ascending ext: d_off_out[k] / d_size_out[k] are copied from the packet's input entry,
+ * d_src_out[k] (optional) is that entry's table position, d_ext_out[k] (optional) its ext.  d_off_out and d_size_out go into
+ * hbs_rtp_unpack as its d_pkt_off / d_pkt_size, with the same d_in.
+ * SPAN = the highest kept ext - base + 1, where base is the lowest kept ext, or params->after_ext + 1 with HBS_RTPO_AFTER; 0
+ * when nothing is kept.  MOVED = the kept packets for which an earlier table entry, accepted and not late, has a higher ext.
+ *   d_summary   nal_count = kept packets, nal_found = accepted packets, stream_bytes = span, rbsp_bytes = the highest kept ext
+ *               (the next call's after_ext; 0 when nothing is kept), stop_reason = 0; reserved[1] = lost = span - kept (the
+ *               sequence numbers inside the span that no packet carried); reserved[2] = duplicates << 32 | moved.  The others
+ *               are n_packets - nal_found, the late ones nal_found - nal_count - duplicates.
+ *               HBS_E_CAPACITY when span > params->max_span: nal_found and stream_bytes are right, nal_count, rbsp_bytes,
+ *               reserved[1] and reserved[2] are 0.  HBS_E_CAPACITY when, with outputs, kept > out_cap: all counts are right.
+ *               On any error nothing but the summary is written.
+ * d_off_out == d_size_out == NULL: plan only -- the summary alone is written and out_cap is not looked at.  n_packets == 0 is
+ * valid.  CHAINING: a receiver calls once per batch with HBS_RTPO_AFTER and after_ext = the rbsp_bytes of the last call that
+ * kept a packet; a packet that arrives behind the batch its number belongs to is LATE there.
+ * Refused with HBS_E_ARG at once, before anything is written: params NULL or out of range (payload_type outside 0..127, unknown
+ * flags, reserved != 0, max_span outside 1..2^33, with HBS_RTPO_AFTER an after_ext outside [2^48, 2^62]), n_packets above
+ * 2^32 - 2, one of d_off_out / d_size_out without the other, d_src_out or d_ext_out without them, missing or misaligned pointers
+ * (with packets: the two tables, and d_in when in_bytes is not 0).  The outputs may not alias the input tables.
+ * Nothing outside the first nal_count entries of the outputs and the summary is stored; no load touches a 16-byte granule that
+ * holds no byte of d_in[0, in_bytes); no host synchronisation; scratch comes from the context's workspace and is sized by
+ * n_packets and max_span alone: 12 bytes a packet and 168 bytes per 256 packets, 4 bytes a slot (a slot per extended sequence
+ * number of max_span) and 64 bytes per 256 slots.  The device work follows the span the call finds, not max_span.
+ * Alignment: d_in, d_summary 16 bytes; d_pkt_off, d_pkt_size, d_off_out, d_size_out, d_ext_out 8 bytes; d_src_out 4 bytes.
+ * STATED LIMITS: one SSRC's stream a call (HBS_RTPO_MATCH_SSRC picks it); no timing-based release -- the caller decides when a
+ * batch is complete; no FEC, no RTX; a duplicate is recognised by its sequence number only.
+ */
+typedef struct hbs_rtp_order_params {   /* HOST memory, 32 bytes */
+    int32_t  payload_type;      /* 0 .. 127: packets of another type are not this stream's */
+    uint32_t flags;             /* HBS_RTPO_* */
+    uint32_t ssrc;              /* read with HBS_RTPO_MATCH_SSRC */
+    uint32_t reserved;          /* 0 */
+    uint64_t max_span;          /* 1 .. 2^33: the widest range of extended sequence numbers the call may have to hold */
+    uint64_t after_ext;         /* read with HBS_RTPO_AFTER: the extended sequence number of the last packet already delivered */
+} hbs_rtp_order_params;
+#define HBS_RTPO_MATCH_SSRC 1u  /* packets whose ssrc differs from params->ssrc are not this stream's */
+#define HBS_RTPO_AFTER      2u  /* the sequence continues behind params->after_ext; packets at or in front of it are late */
+
+int hbs_rtp_order(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
+                  const uint64_t* d_pkt_off, const uint64_t* d_pkt_size, uint64_t n_packets,
+                  const hbs_rtp_order_params* params,
+                  uint64_t* d_off_out, uint64_t* d_size_out /* both or neither; neither: plan only */,
+                  uint32_t* d_src_out /* optional */, uint64_t* d_ext_out /* optional */, uint64_t out_cap /* entries */,
+                  hbs_summary* d_summary);
 
 /*
  * K4: header parse, one NAL per lane (64 per wavefront), over the RBSP arena and index that
