@@ -60,6 +60,15 @@ RTPU_MATCH_SSRC = 1
 RTP_ORDER_PARAMS = np.dtype([("payload_type", "<i4"), ("flags", "<u4"), ("ssrc", "<u4"), ("reserved", "<u4"), ("max_span", "<u8"),
                              ("after_ext", "<u8")])
 RTPO_MATCH_SSRC, RTPO_AFTER = 1, 2
+# layout of hbs_mp4_params / hbs_mp4_frag / hbs_mp4_init_params, the flags of hbs_mp4_fragment and hbs_mp4_init_host
+MP4_PARAMS = np.dtype([("length_size", "<i4"), ("flags", "<u4"), ("track_id", "<u4"), ("sequence", "<u4"), ("max_samples", "<u4"),
+                       ("sample_duration", "<u4"), ("base_time", "<u8")])
+MP4_FRAG = np.dtype([("out_off", "<u8"), ("out_bytes", "<u8"), ("first_au", "<u8"), ("decode_time", "<u8"), ("samples", "<u4"),
+                     ("sequence", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+MP4_INIT_PARAMS = np.dtype([("track_id", "<u4"), ("timescale", "<u4"), ("width", "<u4"), ("height", "<u4"), ("length_size", "<i4"),
+                            ("chroma_format_idc", "<i4"), ("bit_depth_luma", "<i4"), ("bit_depth_chroma", "<i4")])
+MP4_CUT_AT_IRAP = 1
+MP4_HEV1 = 1
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -92,7 +101,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
            "hbs_au_insert", "hbs_aud_nal_host",
            "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host", "hbs_rtp_ap_units_host",
-           "hbs_rtp_unpack", "hbs_rtp_frames_host", "hbs_rtp_order"]
+           "hbs_rtp_unpack", "hbs_rtp_frames_host", "hbs_rtp_order",
+           "hbs_mp4_fragment", "hbs_mp4_fragment_bytes_host", "hbs_mp4_init_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -251,6 +261,13 @@ def load_library():
     lib.hbs_rtp_frames_host.restype = C.c_uint64
     lib.hbs_rtp_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.hbs_mp4_fragment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.c_void_p]
+    lib.hbs_mp4_fragment_bytes_host.argtypes = [C.c_uint64, C.c_uint64]
+    lib.hbs_mp4_fragment_bytes_host.restype = C.c_uint64
+    lib.hbs_mp4_init_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+    lib.hbs_mp4_init_host.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -377,6 +394,39 @@ def rtp_order_params(payload_type=96, flags=0, ssrc=0, max_span=1 << 20, after_e
     p = np.zeros(1, dtype=RTP_ORDER_PARAMS)
     p[0] = (payload_type, flags, ssrc, 0, max_span, after_ext)
     return p
+
+
+def mp4_params(length_size=4, flags=0, track_id=1, sequence=1, max_samples=0, sample_duration=0, base_time=0):
+    """an hbs_mp4_params record (ndarray[MP4_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=MP4_PARAMS)
+    p[0] = (length_size, flags, track_id, sequence, max_samples, sample_duration, base_time)
+    return p
+
+
+def mp4_fragment_bytes(samples, sample_bytes):
+    """hbs_mp4_fragment_bytes_host: the bytes of one fragment of `samples` samples that hold `sample_bytes` bytes"""
+    return int(load_library().hbs_mp4_fragment_bytes_host(int(samples), int(sample_bytes)))
+
+
+def mp4_init(nals, track_id=1, timescale=90000, width=1920, height=1080, length_size=4, chroma_format_idc=1, bit_depth_luma=8,
+             bit_depth_chroma=8, flags=0):
+    """hbs_mp4_init_host: the init segment (ftyp + moov) for the fragments of hbs_mp4_fragment, as bytes.  nals: the VPS / SPS /
+    PPS NAL units (bytes-like, no start codes), in the order their arrays list them.  Raises HbsError for what the call refuses."""
+    lib = load_library()
+    prm = np.zeros(1, dtype=MP4_INIT_PARAMS)
+    prm[0] = (track_id, timescale, width, height, length_size, chroma_format_idc, bit_depth_luma, bit_depth_chroma)
+    bufs = [np.frombuffer(bytes(x), dtype=np.uint8) if len(x) else np.zeros(0, dtype=np.uint8) for x in nals]
+    ptrs = (C.c_void_p * max(len(bufs), 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    sizes = np.array([b.size for b in bufs], dtype=np.uint64)
+    args = (prm.ctypes.data_as(C.c_void_p), int(flags), C.cast(ptrs, C.c_void_p), sizes.ctypes.data_as(C.c_void_p), len(bufs))
+    need = int(lib.hbs_mp4_init_host(*args, None, 0))
+    if need < 0:
+        raise HbsError("hbs_mp4_init_host: error %d" % need)
+    out = np.zeros(need, dtype=np.uint8)
+    got = int(lib.hbs_mp4_init_host(*args, out.ctypes.data_as(C.c_void_p), need))
+    if got != need:
+        raise HbsError("hbs_mp4_init_host: %d, then %d" % (need, got))
+    return out.tobytes()
 
 
 def rtp_frames(data, cap=None):
@@ -1227,6 +1277,67 @@ class Context:
             raise HbsError("hbs_rtp_order: error %d" % int(s["error"]))
         return (off[: kept * 8], size[: kept * 8], src[: kept * 4].cpu().numpy().view(np.uint32).copy(),
                 ext[: kept * 8].cpu().numpy().view(np.uint64).copy(), s)
+
+    # ---- fragmented MP4 -----------------------------------------------------------------
+
+    def mp4_fragment_async(self, stream, stream_bytes, index, n_nals, nal_au, au, n_aus, params, out, summary, keep=None, dts=None,
+                           pts=None, sample_off=None, sample_size=None, frag=None, frag_cap=None, out_cap=None):
+        """Enqueue hbs_mp4_fragment on the current torch stream.  stream / index / nal_au / au / out / summary / keep / dts / pts /
+        sample_off / sample_size / frag are device tensors (out None: plan only; keep, dts, pts, sample_off with sample_size and
+        frag may be None); params is an ndarray[MP4_PARAMS] of one in host memory.  frag_cap (records) and out_cap (bytes)
+        default to what the tensors hold.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if out_cap is None:
+            out_cap = out.numel() if out is not None else 0
+        if frag_cap is None:
+            frag_cap = frag.numel() * frag.element_size() // MP4_FRAG.itemsize if frag is not None else 0
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=MP4_PARAMS)
+        return self.lib.hbs_mp4_fragment(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None,
+                                         int(n_nals), p(keep), p(nal_au) if n_nals else None, p(au) if n_aus else None, int(n_aus),
+                                         p(dts), p(pts), params.ctypes.data_as(C.c_void_p) if params is not None else None,
+                                         p(out), int(out_cap), p(sample_off), p(sample_size), p(frag), int(frag_cap), p(summary))
+
+    def mp4_fragment(self, stream, index, nal_au, au, keep=None, dts=None, pts=None, stream_bytes=None, **params):
+        """Convenience: the access units of `stream` (device uint8 tensor) as fMP4 fragments.  index: ndarray[NAL_ENTRY], nal_au:
+        one uint32 per NAL, au: ndarray[ACCESS_UNIT], keep: None or a byte per NAL, dts / pts: None or one uint64 per AU -- host
+        arrays or device uint8 tensors of their bytes; params: the keywords of mp4_params.  Plans first, allocates the exact
+        output, runs.  Returns (out device tensor, sample_off ndarray[uint64], sample_size ndarray[uint64],
+        frags ndarray[MP4_FRAG], summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+
+        def dv(x, dtype):
+            if isinstance(x, np.ndarray):
+                b = np.ascontiguousarray(x, dtype=dtype).view(np.uint8).reshape(-1)
+                return t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
+            return x
+        n = len(index) if isinstance(index, np.ndarray) else index.numel() * index.element_size() // NAL_ENTRY.itemsize
+        n_aus = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
+        index, nal_au, au = dv(index, NAL_ENTRY), dv(nal_au, np.uint32), dv(au, ACCESS_UNIT)
+        keep, dts, pts = dv(keep, np.uint8), dv(dts, np.uint64), dv(pts, np.uint64)
+        prm = mp4_params(**params)
+        nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        args = (stream, nbytes, index, n, nal_au, au, n_aus, prm)
+        kw = dict(keep=keep, dts=dts, pts=pts)
+        self._check(self.mp4_fragment_async(*args, None, summary, **kw), "hbs_mp4_fragment")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_fragment: error %d (NAL %d, access unit %d)"
+                           % (int(s["error"]), int(s["reserved"][0]) - 1, int(s["reserved"][1]) - 1))
+        need, frags = int(s["stream_bytes"]), int(s["nal_count"])
+        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
+        so, ss = (t.empty(max(n_aus, 1) * 8, dtype=t.uint8, device=dev) for _ in range(2))
+        fr = t.empty(max(frags, 1) * MP4_FRAG.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.mp4_fragment_async(*args, out, summary, sample_off=so, sample_size=ss, frag=fr, frag_cap=frags, out_cap=need, **kw),
+                    "hbs_mp4_fragment")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_fragment: error %d" % int(s["error"]))
+        return (out[:need], so[: n_aus * 8].cpu().numpy().view(np.uint64).copy(), ss[: n_aus * 8].cpu().numpy().view(np.uint64).copy(),
+                fr[: frags * MP4_FRAG.itemsize].cpu().numpy().view(MP4_FRAG).copy(), s)
 
     # ---- access units -----------------------------------------------------------------
 

@@ -26,6 +26,7 @@
 #include "hbs_rtp.h"
 #include "hbs_rtpun.h"
 #include "hbs_rtpord.h"
+#include "hbs_mp4.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -45,8 +46,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kIws    hbs_au_insert's scratch
  * kRws    hbs_rtp_pack's scratch
  * kUws    hbs_rtp_unpack's scratch
- * kOws    hbs_rtp_order's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kBufs };
+ * kOws    hbs_rtp_order's scratch
+ * kPws    hbs_mp4_fragment's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -833,6 +835,48 @@ int hbs_rtp_order(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_rtp_order(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_order");
+}
+
+int hbs_mp4_fragment(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                     const hbs_nal_entry* d_index, uint64_t n_nals, const uint8_t* d_keep,
+                     const uint32_t* d_nal_au, const hbs_access_unit* d_au, uint64_t n_aus,
+                     const uint64_t* d_dts, const uint64_t* d_pts, const hbs_mp4_params* params,
+                     uint8_t* d_out, uint64_t out_cap, uint64_t* d_sample_off, uint64_t* d_sample_size,
+                     hbs_mp4_frag* d_frag, uint64_t frag_cap, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_mp4_params) == 32 && sizeof(hbs_mp4_frag) == 48 && sizeof(hbs_mp4_init_params) == 32, "hbs_mp4_* layout");
+    if (!c || !d_summary || !hbs::mp4_params_ok(params) || n_nals > 0xFFFFFFFFull || n_aus > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_nals ? (!d_index || !d_nal_au || (stream_bytes && !d_stream)) : n_aus != 0) return HBS_E_ARG;
+    if (n_aus && !d_au) return HBS_E_ARG;
+    if ((d_sample_off == nullptr) != (d_sample_size == nullptr)) return HBS_E_ARG;
+    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_au, 15) || misaligned(d_frag, 15) || misaligned(d_summary, 15) ||
+        misaligned(d_index, 7) || misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_sample_off, 7) || misaligned(d_sample_size, 7) ||
+        misaligned(d_nal_au, 3)) {
+        snprintf(c->err, sizeof(c->err), "stream/output/AU table/fragment table/summary pointers must be 16-byte aligned, index, times and sample tables 8-byte, AU numbers 4-byte");
+        return HBS_E_ARG;
+    }
+    if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::Mp4Args a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_stream; a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals; a.keep = d_keep;
+    a.nal_au = d_nal_au; a.au = d_au; a.n_aus = n_aus;
+    a.dts = reinterpret_cast<const unsigned long long*>(d_dts); a.pts = reinterpret_cast<const unsigned long long*>(d_pts);
+    a.L = (uint32_t)params->length_size; a.flags = params->flags; a.track_id = params->track_id; a.sequence = params->sequence;
+    a.max_samples = params->max_samples; a.sample_duration = params->sample_duration; a.base_time = params->base_time;
+    a.out = d_out; a.out_cap = out_cap; a.summary = d_summary;
+    if (d_out) {
+        a.sample_off = reinterpret_cast<unsigned long long*>(d_sample_off); a.sample_size = reinterpret_cast<unsigned long long*>(d_sample_size);
+        a.frag = d_frag; a.frag_cap = frag_cap;
+    }
+    /* the copy's grid: the tiles out_cap has room for, and no more than the call can make */
+    const uint64_t most = hbs::mp4_output_bound(n_nals, n_aus, stream_bytes, a.L);
+    a.tiles = d_out && n_nals ? hbs::mp4_tiles(out_cap < most ? out_cap : most) : 0;
+    const int rc = carve(c, c->buf[kPws], "hipMalloc(MP4 scratch)", [&](hbs::Carver& w) { hbs::lay_mp4(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_mp4_fragment(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_fragment");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,

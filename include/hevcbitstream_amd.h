@@ -112,9 +112,9 @@ typedef struct hbs_ctx hbs_ctx;
  * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
- *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order.
+ *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
- * tests/test_gpu_rtp_unpack.py and tests/test_gpu_rtp_order.py replay, no
+ * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py and tests/test_gpu_mp4.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -412,6 +412,123 @@ int hbs_lenpref_to_annexb(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, 
                           int startcode_bytes /* 3: 00 00 01, 4: 00 00 00 01 */, uint64_t nal_cap,
                           uint8_t* d_out, uint64_t out_cap,
                           uint64_t* d_sample_off_out /* optional, n_samples + 1 */, hbs_summary* d_summary);
+
+/*
+ * ---- access units -> fragmented MP4 (ISO/IEC 14496-12): moof + mdat fragments, and the init segment ----------------------
+ * hbs_mp4_fragment writes the container around the samples of hbs_annexb_to_lenpref: every fragment is a moof, whose one trun
+ * describes its samples, and an mdat that holds them, as DASH / CMAF / fragmented MP4 want them.  The index, the AU numbers and
+ * flags of hbs_access_units and the times of hbs_ts_demux / hbs_rtp_unpack are all it reads besides the stream.
+ * hbs_mp4_init_host writes the matching init segment on the host.
+ *
+ * SAMPLES.  AU a is the kept NALs k (d_keep as in hbs_annexb_to_lenpref; NULL: all) with a_k = d_nal_au[k] - d_nal_au[0] == a.
+ * Every step d_nal_au[k] - d_nal_au[k-1] is 0 or 1 and a_(n_nals-1) == n_aus - 1 (hbs_rtp_pack's pointer-offset rule: a GOP
+ * cut is passed as d_index + first_nal, d_nal_au + first_nal, d_au + first_au).  Of d_au[a] only flags & HBS_AU_IRAP is read.
+ * The sample is the records of its kept NALs back to back, exactly as hbs_annexb_to_lenpref makes them: L = length_size bytes
+ * of big-endian length, then stream[start, end).  A kept NAL longer than 2^(8 L) - 1 is an error; an AU with nothing kept is a
+ * sample of size 0.  B(a) = the record bytes of all AUs below a.
+ * TIMES.  dts(a) = d_dts ? d_dts[a] : base_time + a * sample_duration, taken exactly, not wrapped; an exact dts(a) of 2^62 or
+ * more is an error at that AU (so is the ~0 "absent" of hbs_ts_demux).  duration(a) = dts(a+1) - dts(a), which must lie in
+ * [0, 2^32 - 1]; duration(n_aus - 1) = sample_duration.  cts(a) = (d_pts ? d_pts[a] : dts(a)) - dts(a), which must lie in
+ * [-2^31, 2^31 - 1]; a d_pts[a] of 2^62 or more is an error.
+ * FRAGMENT CUTS.  s(a) = the largest b <= a with b == 0, or with HBS_MP4_CUT_AT_IRAP set and AU b an IRAP.  AU a begins a
+ * fragment iff a == s(a), or max_samples > 0 and (a - s(a)) % max_samples == 0.  Fragment r has first AU f_r and S_r samples.
+ * BYTES OF FRAGMENT r (every integer big-endian).  It begins at O_r = B(f_r) + 16 f_r + 96 r and is, with S = S_r:
+ *   moof  size 88 + 16 S   'moof'
+ *     mfhd  00 00 00 10 'mfhd' 00 00 00 00  sequence(4) = (params->sequence + r) mod 2^32
+ *     traf  size 64 + 16 S 'traf'
+ *       tfhd  00 00 00 10 'tfhd' 00 02 00 00  track_id(4)                 (default-base-is-moof)
+ *       tfdt  00 00 00 14 'tfdt' 01 00 00 00  dts(f_r)(8)
+ *       trun  size 20 + 16 S 'trun' 01 00 0F 01  S(4)  data_offset(4) = 96 + 16 S
+ *             then per sample: duration(4) size(4) flags(4) cts(4, two's complement)
+ *             flags = 0x02000000 for an AU with HBS_AU_IRAP, else 0x01010000
+ *   mdat  size 8 + P (4) 'mdat', then the P = B(f_r + S) - B(f_r) sample bytes
+ * P > 2^32 - 9 is an error at AU f_r: there is no 64-bit mdat.  So is S > (2^32 - 89) / 16, whose moof size has no 32 bits.
+ * Sample a of fragment r lies at O_r + 96 + 16 S_r + B(a) - B(f_r): d_sample_off[a] / d_sample_size[a] (optional, both or
+ * neither, n_aus entries each) say so, in exactly the form hbs_lenpref_to_annexb reads.  d_frag[r] (optional, frag_cap
+ * entries) is hbs_mp4_frag below.  The output is B(n_aus) + 16 n_aus + 96 R bytes for R fragments:
+ * hbs_mp4_fragment_bytes_host(S, P) = 96 + 16 S + P is one fragment's.
+ *
+ * d_summary: nal_count = fragments R, nal_found = n_nals, rbsp_bytes = B(n_aus), stream_bytes = output bytes, stop_reason = 0,
+ * reserved[2] = kept NALs.  error = HBS_E_ARG with reserved[0] = 1 + the lowest offending NAL for an index inconsistent by
+ * hbs_filter_annexb's definition, a broken AU-number rule or a record too long for L; HBS_E_ARG with reserved[1] = 1 + the lowest
+ * offending AU for a time rule or a fragment-size rule (reported at the fragment's first AU; the fragment sizes are only
+ * looked at when no NAL offends).  Either or both may be set; the other counts mean nothing then.  Otherwise HBS_E_CAPACITY when
+ * out_cap is below the output or frag_cap < R with a d_frag; the counts are right then.  On any error nothing but the summary
+ * is written.  d_out == NULL: plan only, the summary alone is written (the tables are not).  n_nals == 0 with n_aus == 0 is
+ * valid: an empty output with no fragment.
+ * Refused with HBS_E_ARG at once, before anything is written: a length_size other than 1, 2, 4, unknown flags, track_id 0,
+ * base_time of 2^62 or more, n_nals or n_aus above 2^32 - 1, n_nals == 0 with n_aus != 0, out_cap above 2^46 with a d_out, one
+ * of the two sample tables without the other, missing or misaligned pointers.
+ * Nothing outside [d_out, d_out + output bytes), d_sample_off / d_sample_size[0, n_aus), d_frag[0, R) and the summary is
+ * stored; no load touches a 16-byte granule that holds no byte of the stream; the plan reads no stream byte at all (lengths
+ * come from the index); no host synchronisation.  Scratch comes from the context's workspace and is sized by n_nals, n_aus and
+ * out_cap alone: 16 bytes a NAL and 24 an AU with a d_out (8 an AU without), 64 bytes per 256 NALs, 80 per 256 AUs, and 16
+ * bytes per 64 KiB of min(out_cap, stream_bytes + L n_nals + 112 n_aus) -- so pass what the plan gave as out_cap.
+ * Alignment: d_stream, d_out, d_au, d_frag, d_summary 16 bytes; d_index, d_dts, d_pts, d_sample_off, d_sample_size 8 bytes;
+ * d_nal_au 4 bytes; d_keep any byte.
+ * STATED LIMITS: one track; 32-bit mdat and moof sizes; no styp, sidx, prft, emsg, senc or encryption; no edit list (a stream
+ * with reordering begins with a positive composition offset); nothing reads MP4 on the device -- moof -> sample table is a
+ * later call.
+ *
+ * hbs_mp4_init_host (plain C, no GPU): the init segment for those fragments -- ftyp (iso6, 0, iso6, mp41), then moov with
+ * mvhd (rate 0x00010000, volume 0x0100, unity matrix, next_track_ID = track_id + 1), one trak (tkhd flags 3 with
+ * width << 16, height << 16; mdia with mdhd, language 0x55C4, hdlr 'vide' "VideoHandler", minf with vmhd flags 1, dinf / dref
+ * with one 'url ' of flags 1, stbl with stsd and empty stts, stsc, stsz, stco) and mvex / trex (track_id, description index 1,
+ * three zeros).  Every version is 0 and every time and duration 0; mvhd and mdhd carry `timescale`.  The stsd holds one
+ * 'hvc1' (HBS_MP4_HEV1: 'hev1') VisualSampleEntry: data_reference_index 1, width, height, 0x00480000 twice, frame_count 1,
+ * 32 zero bytes of name, depth 0x0018, 0xFFFF, then the hvcC:
+ *   01, the 12 bytes general_profile_space .. general_level_idc of the first SPS among the NALs (bytes [3, 15) of that NAL with
+ *   its emulation prevention bytes stripped, the two NAL header bytes counted), F0 00, FC, FC | chroma_format_idc,
+ *   F8 | bit_depth_luma - 8, F8 | bit_depth_chroma - 8, 00 00, numTemporalLayers << 3 | temporalIdNested << 2 | length_size - 1
+ *   (from stripped byte 2 of that SPS, b: ((b >> 1) & 7) + 1 and b & 1), numOfArrays, and one array each for the types 32, 33,
+ *   34 that occur, in that order: array_completeness << 7 | type ('hvc1': 1, 'hev1': 0), the count (2 bytes), then per NAL of
+ *   the type, in the given order, its 16-bit length and its bytes.
+ * nal[i] / nal_bytes[i], i < n: VPS / SPS / PPS NAL units without start codes.  Returns the bytes the segment takes; it is
+ * written to out only when cap suffices.  HBS_E_ARG: a NULL pointer, unknown flags, n of 0 or above 65535, track_id 0 or
+ * 2^32 - 1, timescale 0, width or height outside 1..65535, a length_size other than 1, 2, 4, chroma_format_idc outside 0..3, a
+ * bit depth outside 8..15 (the hvcC has three bits for each), a NAL shorter than 2 bytes or longer than 65535, a NAL type
+ * outside 32..34, no SPS, an SPS with fewer than 15 bytes once stripped.  Every length is bounded before it is used; no byte
+ * outside the NALs is read.
+ */
+typedef struct hbs_mp4_params {   /* HOST memory, 32 bytes */
+    int32_t  length_size;      /* 1, 2 or 4: as hbs_annexb_to_lenpref */
+    uint32_t flags;            /* HBS_MP4_* */
+    uint32_t track_id;         /* 1 .. 2^32 - 1 */
+    uint32_t sequence;         /* mfhd sequence_number of the call's first fragment; fragment r carries (sequence + r) mod 2^32 */
+    uint32_t max_samples;      /* 0: no limit; else no fragment holds more samples */
+    uint32_t sample_duration;  /* duration of the call's last AU, and of every AU when d_dts == NULL */
+    uint64_t base_time;        /* with d_dts == NULL: dts(a) = base_time + a * sample_duration */
+} hbs_mp4_params;
+#define HBS_MP4_CUT_AT_IRAP 1u  /* a fragment begins at every AU with HBS_AU_IRAP */
+
+typedef struct hbs_mp4_frag {     /* 48 bytes */
+    uint64_t out_off, out_bytes;  /* the fragment (moof + mdat) in the output */
+    uint64_t first_au;            /* its first sample, numbered within the call */
+    uint64_t decode_time;         /* tfdt baseMediaDecodeTime */
+    uint32_t samples, sequence, flags /* HBS_AU_IRAP when its first sample is one */, reserved;
+} hbs_mp4_frag;
+
+struct hbs_access_unit;            /* hbs_access_units' record, below */
+int hbs_mp4_fragment(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
+                     const hbs_nal_entry* d_index, uint64_t n_nals, const uint8_t* d_keep /* nullable */,
+                     const uint32_t* d_nal_au, const struct hbs_access_unit* d_au, uint64_t n_aus,
+                     const uint64_t* d_dts /* nullable */, const uint64_t* d_pts /* nullable */,
+                     const hbs_mp4_params* params,
+                     uint8_t* d_out, uint64_t out_cap,
+                     uint64_t* d_sample_off, uint64_t* d_sample_size /* optional, both or neither, n_aus */,
+                     hbs_mp4_frag* d_frag /* optional */, uint64_t frag_cap,
+                     hbs_summary* d_summary);
+uint64_t hbs_mp4_fragment_bytes_host(uint64_t samples, uint64_t sample_bytes);   /* 96 + 16 S + bytes */
+
+typedef struct hbs_mp4_init_params {  /* 32 bytes */
+    uint32_t track_id, timescale, width, height;    /* width, height: 1..65535 */
+    int32_t  length_size;                            /* 1, 2, 4 */
+    int32_t  chroma_format_idc, bit_depth_luma, bit_depth_chroma;   /* 0..3, 8..15, 8..15 */
+} hbs_mp4_init_params;
+#define HBS_MP4_HEV1 1   /* sample entry 'hev1' (sets may also be in band), array_completeness 0; default 'hvc1', 1 */
+int64_t hbs_mp4_init_host(const hbs_mp4_init_params* p, int flags,
+                          const uint8_t* const* nal, const uint64_t* nal_bytes, uint64_t n /* VPS / SPS / PPS NALs, no start codes */,
+                          uint8_t* out, uint64_t cap);   /* bytes needed; written only when cap suffices; HBS_E_ARG */
 
 /*
  * ---- MPEG transport stream (ISO/IEC 13818-1) -> Annex-B elementary stream, PES times ----------------------------------
