@@ -69,6 +69,12 @@ MP4_INIT_PARAMS = np.dtype([("track_id", "<u4"), ("timescale", "<u4"), ("width",
                             ("chroma_format_idc", "<i4"), ("bit_depth_luma", "<i4"), ("bit_depth_chroma", "<i4")])
 MP4_CUT_AT_IRAP = 1
 MP4_HEV1 = 1
+# layout of hbs_mp4_read_params / hbs_mp4_track (hbs_mp4_samples, hbs_mp4_init_read_host)
+MP4_READ_PARAMS = np.dtype([("flags", "<u4"), ("track_id", "<u4"), ("trex_duration", "<u4"), ("trex_size", "<u4"), ("trex_flags", "<u4"),
+                            ("reserved", "<u4", (3,))])
+MP4_TRACK = np.dtype([("track_id", "<u4"), ("timescale", "<u4"), ("width", "<u4"), ("height", "<u4"), ("length_size", "<i4"),
+                      ("entry", "<u4"), ("trex_duration", "<u4"), ("trex_size", "<u4"), ("trex_flags", "<u4"), ("n_nals", "<u4"),
+                      ("hvcc_off", "<u8"), ("hvcc_bytes", "<u8"), ("reserved", "<u4", (2,))])
 # layout of hbs_parsed_nal
 WRITTEN = np.dtype([("rc", "<i4"), ("rbsp_size", "<u4"), ("slice_data_size", "<i4"), ("pad", "<u4")])
 PARSED = np.dtype([("rc", "<i4"), ("nal_unit_type", "<i4"), ("nal_layer_id", "<i4"), ("nal_temporal_id_plus1", "<i4"),
@@ -102,7 +108,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_au_insert", "hbs_aud_nal_host",
            "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host", "hbs_rtp_ap_units_host",
            "hbs_rtp_unpack", "hbs_rtp_frames_host", "hbs_rtp_order",
-           "hbs_mp4_fragment", "hbs_mp4_fragment_bytes_host", "hbs_mp4_init_host"]
+           "hbs_mp4_fragment", "hbs_mp4_fragment_bytes_host", "hbs_mp4_init_host",
+           "hbs_mp4_samples", "hbs_mp4_init_read_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -268,6 +275,11 @@ def load_library():
     lib.hbs_mp4_fragment_bytes_host.restype = C.c_uint64
     lib.hbs_mp4_init_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
     lib.hbs_mp4_init_host.restype = C.c_int64
+    lib.hbs_mp4_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hbs_mp4_samples.restype = C.c_int
+    lib.hbs_mp4_init_read_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.hbs_mp4_init_read_host.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -427,6 +439,32 @@ def mp4_init(nals, track_id=1, timescale=90000, width=1920, height=1080, length_
     if got != need:
         raise HbsError("hbs_mp4_init_host: %d, then %d" % (need, got))
     return out.tobytes()
+
+
+def mp4_read_params(track_id=0, trex_duration=0, trex_size=0, trex_flags=0, flags=0):
+    """an hbs_mp4_read_params record (ndarray[MP4_READ_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=MP4_READ_PARAMS)
+    p[0] = (flags, track_id, trex_duration, trex_size, trex_flags, (0, 0, 0))
+    return p
+
+
+def mp4_init_read(segment_bytes, track_id=0):
+    """hbs_mp4_init_read_host: the track record (an MP4_TRACK record) of an init segment (bytes-like) and the parameter-set NALs
+    of its hvcC as slices of the segment, in array order.  Raises HbsError for what the call refuses."""
+    lib = load_library()
+    seg = np.frombuffer(bytes(segment_bytes), dtype=np.uint8)
+    trk = np.zeros(1, dtype=MP4_TRACK)
+    sp = seg.ctypes.data_as(C.c_void_p) if seg.size else None
+    n = int(lib.hbs_mp4_init_read_host(sp, seg.size, int(track_id), trk.ctypes.data_as(C.c_void_p), None, None, 0))
+    if n < 0:
+        raise HbsError("hbs_mp4_init_read_host: error %d" % n)
+    off, size = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+    got = int(lib.hbs_mp4_init_read_host(sp, seg.size, int(track_id), trk.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+                                         size.ctypes.data_as(C.c_void_p), n))
+    if got != n:
+        raise HbsError("hbs_mp4_init_read_host: %d, then %d" % (n, got))
+    raw = seg.tobytes()
+    return trk[0].copy(), [raw[int(off[i]): int(off[i]) + int(size[i])] for i in range(n)]
 
 
 def rtp_frames(data, cap=None):
@@ -1338,6 +1376,70 @@ class Context:
             raise HbsError("hbs_mp4_fragment: error %d" % int(s["error"]))
         return (out[:need], so[: n_aus * 8].cpu().numpy().view(np.uint64).copy(), ss[: n_aus * 8].cpu().numpy().view(np.uint64).copy(),
                 fr[: frags * MP4_FRAG.itemsize].cpu().numpy().view(MP4_FRAG).copy(), s)
+
+    def mp4_samples_async(self, data, in_bytes, params, summary, seg=None, seg_stride=16, n_segs=0, moof_cap=0, sample_cap=0,
+                          sample_off=None, sample_size=None, dts=None, pts=None, sample_flags=None, frag=None):
+        """Enqueue hbs_mp4_samples on the current torch stream.  data / summary / seg / sample_off / sample_size / dts / pts /
+        sample_flags / frag are device tensors (seg None: one segment, the buffer; sample_off with sample_size None: plan only;
+        dts, pts, sample_flags, frag may be None); params is an ndarray[MP4_READ_PARAMS] of one in host memory.  Returns the
+        call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=MP4_READ_PARAMS)
+        return self.lib.hbs_mp4_samples(self.h, p(data) if in_bytes else None, int(in_bytes), p(seg), int(seg_stride), int(n_segs),
+                                        params.ctypes.data_as(C.c_void_p) if params is not None else None, int(moof_cap),
+                                        int(sample_cap), p(sample_off), p(sample_size), p(dts), p(pts), p(sample_flags), p(frag),
+                                        p(summary))
+
+    def mp4_samples(self, data, seg=None, seg_stride=None, in_bytes=None, moof_cap=None, **params):
+        """Convenience: the sample table of the fMP4 segments in `data` (device uint8 tensor).  seg: None (one segment, the
+        buffer), an (n, 2) uint64 host array of offsets and sizes, an ndarray[MP4_FRAG], or a device uint8 tensor of records with
+        seg_stride (default 16); moof_cap: the most moofs the plan has room for (default: in_bytes // 8, at most 4096; the plan
+        is run again with the count when that was too few); params: the keywords of mp4_read_params.  Plans, allocates the
+        exact tables, runs.  Returns (sample_off, sample_size, dts, pts, flags, frags ndarray[MP4_FRAG], summary record), host
+        arrays."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
+        n_segs = 0
+        if isinstance(seg, np.ndarray):
+            if seg.dtype == MP4_FRAG:
+                seg_stride, n_segs = MP4_FRAG.itemsize, len(seg)
+            else:
+                seg = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1, 2)
+                seg_stride, n_segs = 16, len(seg)
+            b = seg.view(np.uint8).reshape(-1)
+            seg = t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
+        elif seg is not None:
+            seg_stride = 16 if seg_stride is None else int(seg_stride)
+            n_segs = seg.numel() * seg.element_size() // seg_stride
+        prm = mp4_read_params(**params)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        kw = dict(seg=seg, seg_stride=seg_stride or 16, n_segs=n_segs)
+        cap = min(nbytes // 8, 4096) if moof_cap is None else int(moof_cap)
+        for _ in range(2):
+            self._check(self.mp4_samples_async(data, nbytes, prm, summary, moof_cap=cap, **kw), "hbs_mp4_samples")
+            s = self.read_summary(summary)
+            if int(s["error"]) == -4 and int(s["nal_found"]) > cap:          # HBS_E_CAPACITY: the default was too small
+                cap = int(s["nal_found"])
+                continue
+            break
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_samples: error %d (segment %d, moof %d, sample %d)"
+                           % (int(s["error"]), int(s["reserved"][0]) - 1, int(s["reserved"][1]) - 1, int(s["reserved"][2]) - 1))
+        n, m = int(s["nal_count"]), int(s["nal_found"])
+        so, ss, dt, pt = (t.empty(max(n, 1) * 8, dtype=t.uint8, device=dev) for _ in range(4))
+        fl = t.empty(max(n, 1) * 4, dtype=t.uint8, device=dev)
+        fr = t.empty(max(m, 1) * MP4_FRAG.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.mp4_samples_async(data, nbytes, prm, summary, moof_cap=m, sample_cap=n, sample_off=so, sample_size=ss, dts=dt,
+                                           pts=pt, sample_flags=fl, frag=fr, **kw), "hbs_mp4_samples")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_samples: error %d" % int(s["error"]))
+        u64 = lambda x: x[: n * 8].cpu().numpy().view(np.uint64).copy()          # noqa: E731
+        return (u64(so), u64(ss), u64(dt), u64(pt), fl[: n * 4].cpu().numpy().view(np.uint32).copy(),
+                fr[: m * MP4_FRAG.itemsize].cpu().numpy().view(MP4_FRAG).copy(), s)
 
     # ---- access units -----------------------------------------------------------------
 

@@ -27,6 +27,7 @@
 #include "hbs_rtpun.h"
 #include "hbs_rtpord.h"
 #include "hbs_mp4.h"
+#include "hbs_mp4rd.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -47,8 +48,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kRws    hbs_rtp_pack's scratch
  * kUws    hbs_rtp_unpack's scratch
  * kOws    hbs_rtp_order's scratch
- * kPws    hbs_mp4_fragment's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kBufs };
+ * kPws    hbs_mp4_fragment's scratch
+ * kQws    hbs_mp4_samples' scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -877,6 +879,42 @@ int hbs_mp4_fragment(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_mp4_fragment(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_fragment");
+}
+
+int hbs_mp4_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const void* d_seg, uint64_t seg_stride, uint64_t n_segs,
+                    const hbs_mp4_read_params* params, uint64_t moof_cap, uint64_t sample_cap,
+                    uint64_t* d_sample_off, uint64_t* d_sample_size, uint64_t* d_dts, uint64_t* d_pts, uint32_t* d_sample_flags,
+                    hbs_mp4_frag* d_frag, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_mp4_read_params) == 32 && sizeof(hbs_mp4_track) == 64 && sizeof(hbs::Mp4TrunRec) == 64, "hbs_mp4_samples layouts");
+    if (!c || !d_summary || !hbs::mp4_read_params_ok(params) || in_bytes > hbs::kRdMaxIn || (in_bytes && !d_in)) return HBS_E_ARG;
+    if (d_seg && (seg_stride < 16 || seg_stride % 8 != 0 || n_segs > 0xFFFFFFFFull)) return HBS_E_ARG;
+    if ((d_sample_off == nullptr) != (d_sample_size == nullptr)) return HBS_E_ARG;
+    if (!d_sample_off && (d_dts || d_pts || d_sample_flags || d_frag)) return HBS_E_ARG;
+    if (moof_cap > 0xFFFFFFFFull || (d_sample_off && sample_cap > 0xFFFFFFFFull)) return HBS_E_ARG;
+    if (misaligned(d_in, 15) || misaligned(d_frag, 15) || misaligned(d_summary, 15) || misaligned(d_seg, 7) || misaligned(d_sample_off, 7) ||
+        misaligned(d_sample_size, 7) || misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_sample_flags, 3)) {
+        snprintf(c->err, sizeof(c->err), "input/fragment table/summary pointers must be 16-byte aligned, segment table and 64-bit sample tables 8-byte, sample flags 4-byte");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::Mp4RdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_in; a.n = in_bytes;
+    a.seg = static_cast<const uint8_t*>(d_seg); a.seg_stride = seg_stride; a.n_segs = d_seg ? n_segs : 1;
+    a.x.track_id = params->track_id; a.x.dur = params->trex_duration; a.x.size = params->trex_size; a.x.flags = params->trex_flags;
+    a.moof_cap = moof_cap; a.summary = d_summary;
+    if (d_sample_off) {
+        a.out = true; a.sample_cap = sample_cap;
+        a.sample_off = reinterpret_cast<unsigned long long*>(d_sample_off); a.sample_size = reinterpret_cast<unsigned long long*>(d_sample_size);
+        a.dts = reinterpret_cast<unsigned long long*>(d_dts); a.pts = reinterpret_cast<unsigned long long*>(d_pts);
+        a.sample_flags = d_sample_flags; a.frag = d_frag;
+    }
+    const int rc = carve(c, c->buf[kQws], "hipMalloc(MP4 read scratch)", [&](hbs::Carver& w) { hbs::lay_mp4rd(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_mp4_samples(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_samples");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,

@@ -112,9 +112,9 @@ typedef struct hbs_ctx hbs_ctx;
  * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
- *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment.
+ *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
- * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py and tests/test_gpu_mp4.py replay, no
+ * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py and tests/test_gpu_mp4_read.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -467,8 +467,7 @@ int hbs_lenpref_to_annexb(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, 
  * Alignment: d_stream, d_out, d_au, d_frag, d_summary 16 bytes; d_index, d_dts, d_pts, d_sample_off, d_sample_size 8 bytes;
  * d_nal_au 4 bytes; d_keep any byte.
  * STATED LIMITS: one track; 32-bit mdat and moof sizes; no styp, sidx, prft, emsg, senc or encryption; no edit list (a stream
- * with reordering begins with a positive composition offset); nothing reads MP4 on the device -- moof -> sample table is a
- * later call.
+ * with reordering begins with a positive composition offset).  hbs_mp4_samples, below, reads fragments back.
  *
  * hbs_mp4_init_host (plain C, no GPU): the init segment for those fragments -- ftyp (iso6, 0, iso6, mp41), then moov with
  * mvhd (rate 0x00010000, volume 0x0100, unity matrix, next_track_ID = track_id + 1), one trak (tkhd flags 3 with
@@ -529,6 +528,132 @@ typedef struct hbs_mp4_init_params {  /* 32 bytes */
 int64_t hbs_mp4_init_host(const hbs_mp4_init_params* p, int flags,
                           const uint8_t* const* nal, const uint64_t* nal_bytes, uint64_t n /* VPS / SPS / PPS NALs, no start codes */,
                           uint8_t* out, uint64_t cap);   /* bytes needed; written only when cap suffices; HBS_E_ARG */
+
+/*
+ * ---- fragmented MP4 -> sample table: moof, traf, tfhd, tfdt, trun read on the device; the init segment on the host -------
+ * hbs_mp4_samples turns the moof boxes of CMAF / DASH / fMP4 segments that lie in device memory into what
+ * hbs_lenpref_to_annexb reads -- per sample its offset and size -- and into decode time, presentation time and flags, with
+ * one hbs_mp4_frag a moof.  It reads what other muxers write: optional fields, three levels of defaults, 64-bit box sizes,
+ * several truns, data offsets that continue.  hbs_mp4_init_read_host reads the init segment on the host: length_size for
+ * hbs_lenpref_to_annexb, the trex defaults for hbs_mp4_read_params.  Every integer in a box is big-endian.
+ *
+ * SEGMENTS.  Segment i is d_in[off_i, off_i + size_i): off_i and size_i are the first two uint64_t of the record at
+ * d_seg + i * seg_stride, seg_stride a multiple of 8 and at least 16.  A stride of 16 is a plain table; a stride of 48 takes
+ * d_frag of hbs_mp4_fragment as it is (out_off and out_bytes are its first two fields).  d_seg == NULL: one segment, the whole
+ * buffer; n_segs is ignored.  A segment is a chain of top-level boxes that tiles it exactly.  A BOX at p in a container that
+ * ends at e is size(4) type(4); size == 1: a 64-bit largesize follows the type and is the size, which must be 16 or more;
+ * size == 0: the box runs to e; any other size below 8 is an error; so are fewer than 8 bytes (16 with a largesize) between p
+ * and e, and a size larger than e - p.  The next box is at p + size; the chain ends when p == e.  Any type other than 'moof'
+ * is stepped over (styp, sidx, prft, emsg, free, mdat, ftyp, moov ...).  A box that breaks a rule is a CHAIN ERROR at that
+ * segment; so is a segment that leaves the buffer (off_i + size_i > in_bytes, or the sum wraps).
+ * One lane walks one segment's chain, twice (to count the moofs, and to place them once their numbers are known), as
+ * hbs_lenpref_to_annexb does for a sample's records.  So a buffer of very many fragments passed as ONE segment is walked by one
+ * lane, at the latency of one dependent load a box: pass a segment table (a record a fragment, or a few) to avoid that.
+ *
+ * INSIDE A MOOF.  The children of moof and traf are chained by the same rule, the container's end for e; unknown children are
+ * stepped over at every level (senc, saiz, saio, sbgp, sgpd, uuid ...).  A child that breaks the rule is a MOOF ERROR, as is
+ * everything called an error below.  Of several mfhd, tfhd or tfdt in one container the first is read.
+ *   mfhd  payload (behind the box header) version/flags(4) sequence(4): the version must be 0 and the payload 8 bytes or more.
+ *         A moof without an mfhd is an error.
+ *   traf  the one read is the first whose tfhd carries params->track_id; with track_id == 0 the first.  Every traf in front of
+ *         it must have a well-formed tfhd.  Later trafs, of the same track too, are not looked at (a stated limit).  A moof
+ *         without such a traf is a fragment of 0 samples.
+ *   tfhd  version/flags(4) track_id(4), then by flag: 0x000001 base_data_offset(8), 0x000002 sample_description_index(4,
+ *         skipped), 0x000008 default duration(4), 0x000010 default size(4), 0x000020 default flags(4); a payload shorter than
+ *         those fields is an error.  0x020000 is default-base-is-moof; 0x010000 (duration-is-empty) and the version are ignored.
+ *         BASE: with 0x000001, off_i + base_data_offset (the offset within the segment's file); otherwise the moof's first
+ *         byte -- except for a traf that is not its moof's first and sets neither 0x000001 nor 0x020000: the standard's "end of
+ *         the previous traf's data" is not supported, an error.
+ *   tfdt  version/flags(4), then the time: version 0 32 bits, version 1 64 bits; any other version, a shorter payload or no
+ *         tfdt in the traf that is read is an error (a stated limit: CMAF and DASH require the box).
+ *   trun  version/flags(4) count(4), then by flag 0x001 data_offset(4, signed), 0x004 first_sample_flags(4), then count
+ *         entries of, by flag and in this order, 0x100 duration(4), 0x200 size(4), 0x400 flags(4), 0x800 composition
+ *         offset(4: version 0 unsigned, version 1 signed): 4 x popcount(flags & 0xF00) bytes an entry.  8 + 4 [0x001] +
+ *         4 [0x004] + count x entry must not exceed the payload; a version above 1 is an error.  Any number of truns, in
+ *         order.  DATA BEGIN: with 0x001, base + data_offset; without, where the previous trun of the traf ended (a trun of
+ *         count 0 with 0x001 ends at its data begin); the traf's first trun without 0x001 begins at base.
+ *
+ * SAMPLES are numbered through the call in segment, moof, trun and entry order.  size = the entry's, else the tfhd's, else
+ * params->trex_size; duration the same way.  flags = the entry's, else first_sample_flags for entry 0 of a trun with 0x004,
+ * else the tfhd's, else trex_flags.  offset = the trun's data begin + the sizes of the trun's earlier entries.  dts = the tfdt
+ * time + the durations of all earlier samples of the moof, across its truns; pts = dts + composition offset; all exact, not
+ * wrapped.  A SAMPLE ERROR: dts of 2^62 or more, pts outside [0, 2^62), offset + size > in_bytes, a negative data begin.
+ * d_sample_off / d_sample_size are exactly what hbs_lenpref_to_annexb reads, d_dts / d_pts what hbs_mp4_fragment, hbs_ts_mux and
+ * hbs_rtp_pack read.  d_sample_flags is the raw 32-bit word: a sync sample is one with bit 0x00010000
+ * (sample_is_non_sync_sample) clear.
+ *
+ * FRAGMENT TABLE.  d_frag[m] for moof m (numbered through the call): out_off = its offset in d_in; out_bytes = the distance
+ * to the next moof of the same segment, or to the segment's end; first_au = its first sample's number; decode_time = the tfdt
+ * time; samples; sequence = the mfhd's; flags = HBS_AU_IRAP iff it has a sample and its first sample is a sync sample;
+ * reserved = 0.  On the output of hbs_mp4_fragment, one segment a fragment or all in one, this is that call's d_frag field
+ * for field.
+ *
+ * d_summary: nal_count = samples N, nal_found = moofs M, rbsp_bytes = the sum of the sample sizes, stream_bytes = in_bytes,
+ * stop_reason = 0.  The stages are looked at in this order and the first that fails ends the call:
+ *   a chain error          error = HBS_E_ARG, reserved[0] = 1 + the lowest such segment; no count means anything
+ *   M > moof_cap           error = HBS_E_CAPACITY; nal_found = M is right, the moofs were not read: nal_count = rbsp_bytes = 0
+ *   a moof error           error = HBS_E_ARG, reserved[1] = 1 + the lowest such moof; M is right, nal_count = rbsp_bytes = 0
+ *   N > sample_cap         (with outputs) error = HBS_E_CAPACITY; M and N are right, the samples were not read: rbsp_bytes = 0
+ *   a sample error         error = HBS_E_ARG, reserved[2] = 1 + the lowest such sample; M and N are right, rbsp_bytes = 0
+ * reserved words not named are 0.  On any error nothing but the summary is written.  d_sample_off == NULL: plan only, the
+ * summary alone is written and sample_cap sizes nothing -- moof_cap still sizes the moofs' scratch, and each moof's lane goes
+ * through its entries itself: one lane a moof, a step an entry that has bytes (so a moof's plan is bounded by its size, and a
+ * moof of one very large trun is planned by one lane, at the cost per entry that profiles/r19/mp4rd_time.txt records); a trun
+ * whose entries have no bytes, whose count nothing in the box bounds, is settled in closed form whatever its count.  n_segs == 0 with a d_seg is valid and gives nothing; so is an empty buffer as one segment.
+ * Refused with HBS_E_ARG at once: params->flags != 0 (none is defined), non-zero reserved words, a seg_stride below 16 or not
+ * a multiple of 8 (with a d_seg), n_segs above 2^32 - 1, in_bytes above 2^62, one sample table without the other, d_dts, d_pts,
+ * d_sample_flags or d_frag without the sample tables, moof_cap above 2^32 - 1, sample_cap above 2^32 - 1 with outputs, missing
+ * or misaligned pointers.
+ * Nothing outside d_sample_off / d_sample_size / d_dts / d_pts / d_sample_flags[0, N), d_frag[0, M) and the summary is stored;
+ * no load touches a 16-byte granule that holds no byte of d_in[0, in_bytes); no mdat payload byte is read (only box headers
+ * along the chains and the boxes named above); no host synchronisation.  Scratch comes from the context's workspace and is
+ * sized by n_segs, moof_cap and sample_cap alone: 8 bytes a segment, 96 bytes a moof of moof_cap, with outputs 68 bytes a
+ * sample of sample_cap, and 64, 128 and 128 bytes per 256 of each.  The grids are sized the same way -- so pass what the plan
+ * gave, not "plenty".
+ * Alignment: d_in, d_frag, d_summary 16 bytes; d_seg and the four 64-bit tables 8 bytes; d_sample_flags 4 bytes.
+ * STATED LIMITS: one track a call; a missing tfdt is an error; the "end of the previous traf's data" base is not supported;
+ * no encryption (senc, saiz, saio are stepped over; the samples stay as they are); no sidx-driven access (pass the segments);
+ * one lane walks a segment's chain.
+ *
+ * hbs_mp4_init_read_host (plain C, no GPU): the counterpart of hbs_mp4_init_host.  It walks seg[0, n) by the box rule above:
+ * moov; its trak boxes in order -- tkhd (version 0 or 1: track_id, width and height, the integer parts), mdia / mdhd (version
+ * 0 or 1: timescale), mdia / minf / stbl / stsd, whose first 'hvc1' or 'hev1' entry that holds an hvcC is the one read --
+ * and mvex / trex of that track (its three defaults).  track_id 0: the first trak with such an entry.  From the hvcC:
+ * length_size = (byte 21 & 3) + 1, and for every array in order every NAL's offset and size within seg.  Returns the number
+ * of those NALs; nal_off / nal_bytes are written for the first `cap` of them (so call with cap 0 first, or with room for
+ * out->n_nals).  HBS_E_ARG: a NULL seg or out, anything malformed or missing (a box that breaks the size rule, no moov, no such
+ * track or one without an hvcC, a tkhd / mdhd version above 1 or a payload too short for its fields, an hvcC whose version
+ * byte is not 1 or whose arrays leave it, no trex for the track).  Every length is bounded before it is used; no byte at or
+ * behind seg + n is read.  On the output of hbs_mp4_init_host it returns what went in.
+ */
+typedef struct hbs_mp4_read_params {   /* HOST memory, 32 bytes */
+    uint32_t flags;                    /* none defined yet: must be 0 */
+    uint32_t track_id;                 /* the track whose traf is read; 0: the first traf of every moof */
+    uint32_t trex_duration, trex_size, trex_flags;   /* defaults of the init segment's trex */
+    uint32_t reserved[3];              /* 0 */
+} hbs_mp4_read_params;
+
+int hbs_mp4_samples(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
+                    const void* d_seg /* nullable */, uint64_t seg_stride, uint64_t n_segs,
+                    const hbs_mp4_read_params* params,
+                    uint64_t moof_cap, uint64_t sample_cap,
+                    uint64_t* d_sample_off, uint64_t* d_sample_size,   /* both or neither; NULL: plan only */
+                    uint64_t* d_dts, uint64_t* d_pts,                  /* optional, each on its own */
+                    uint32_t* d_sample_flags,                          /* optional */
+                    hbs_mp4_frag* d_frag /* optional, moof_cap entries */,
+                    hbs_summary* d_summary);
+
+typedef struct hbs_mp4_track {      /* 64 bytes */
+    uint32_t track_id, timescale, width, height;
+    int32_t  length_size;           /* lengthSizeMinusOne + 1 */
+    uint32_t entry;                 /* fourcc: 'hvc1' or 'hev1' */
+    uint32_t trex_duration, trex_size, trex_flags;
+    uint32_t n_nals;                /* parameter-set NALs in the hvcC, all arrays */
+    uint64_t hvcc_off, hvcc_bytes;  /* the hvcC payload within the segment */
+    uint32_t reserved[2];
+} hbs_mp4_track;
+int64_t hbs_mp4_init_read_host(const uint8_t* seg, uint64_t n, uint32_t track_id /* 0: the first video track with an hvcC */,
+                               hbs_mp4_track* out, uint64_t* nal_off, uint64_t* nal_bytes, uint64_t cap);
 
 /*
  * ---- MPEG transport stream (ISO/IEC 13818-1) -> Annex-B elementary stream, PES times ----------------------------------
