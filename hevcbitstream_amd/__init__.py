@@ -20,7 +20,8 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   RTP_UNPACK_PARAMS, RTPU_MATCH_SSRC, rtp_unpack_params, rtp_frames,
                   RTP_ORDER_PARAMS, RTPO_MATCH_SSRC, RTPO_AFTER, rtp_order_params,
                   MP4_PARAMS, MP4_FRAG, MP4_INIT_PARAMS, MP4_CUT_AT_IRAP, MP4_HEV1, mp4_params, mp4_fragment_bytes, mp4_init,
-                  MP4_READ_PARAMS, MP4_TRACK, mp4_read_params, mp4_init_read)
+                  MP4_READ_PARAMS, MP4_TRACK, mp4_read_params, mp4_init_read,
+                  MP4_STBL, MP4_STBL_CO64, mp4_stbl_find, mp4_track_read)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
            "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
@@ -37,4 +38,5 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "RTP_UNPACK_PARAMS", "RTPU_MATCH_SSRC", "rtp_unpack_params", "rtp_frames",
            "RTP_ORDER_PARAMS", "RTPO_MATCH_SSRC", "RTPO_AFTER", "rtp_order_params",
            "MP4_PARAMS", "MP4_FRAG", "MP4_INIT_PARAMS", "MP4_CUT_AT_IRAP", "MP4_HEV1", "mp4_params", "mp4_fragment_bytes", "mp4_init",
-           "MP4_READ_PARAMS", "MP4_TRACK", "mp4_read_params", "mp4_init_read"]
+           "MP4_READ_PARAMS", "MP4_TRACK", "mp4_read_params", "mp4_init_read",
+           "MP4_STBL", "MP4_STBL_CO64", "mp4_stbl_find", "mp4_track_read"]

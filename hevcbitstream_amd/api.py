@@ -91,6 +91,11 @@ SEI_MAX_MESSAGES = 6
 EXT_NAL = np.dtype([("num_sei_messages", "<i4"), ("primary_pic_type", "<i4"), ("filler_bytes", "<u4"), ("reserved", "<u4"),
                     ("sei", [("payloadType", "<i4"), ("payloadSize", "<i4"), ("payload_off", "<u4"), ("reserved", "<u4")], (SEI_MAX_MESSAGES,))])
 
+# layout of hbs_mp4_stbl (hbs_mp4_stbl_find_host, hbs_mp4_stbl_samples): each box reference is (off, bytes)
+MP4_STBL = np.dtype([("stsz", "<u8", (2,)), ("stco", "<u8", (2,)), ("stsc", "<u8", (2,)), ("stts", "<u8", (2,)), ("ctts", "<u8", (2,)),
+                     ("stss", "<u8", (2,)), ("flags", "<u4"), ("reserved0", "<u4"), ("file_bytes", "<u8"), ("reserved", "<u8", (2,))])
+MP4_STBL_CO64 = 1
+
 EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stream", "hbs_ctx_use_own_stream",
            "hbs_ctx_get_stream",
            "hbs_ctx_synchronize", "hbs_last_error", "hbs_index_extract", "hbs_index_extract_host", "hbs_read_summary",
@@ -109,7 +114,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_rtp_pack", "hbs_rtp_nal_packets_host", "hbs_rtp_packet_host", "hbs_rtp_ap_units_host",
            "hbs_rtp_unpack", "hbs_rtp_frames_host", "hbs_rtp_order",
            "hbs_mp4_fragment", "hbs_mp4_fragment_bytes_host", "hbs_mp4_init_host",
-           "hbs_mp4_samples", "hbs_mp4_init_read_host"]
+           "hbs_mp4_samples", "hbs_mp4_init_read_host", "hbs_mp4_stbl_samples", "hbs_mp4_stbl_find_host",
+           "hbs_mp4_track_read_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -280,6 +286,13 @@ def load_library():
     lib.hbs_mp4_samples.restype = C.c_int
     lib.hbs_mp4_init_read_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     lib.hbs_mp4_init_read_host.restype = C.c_int64
+    lib.hbs_mp4_track_read_host.argtypes = lib.hbs_mp4_init_read_host.argtypes
+    lib.hbs_mp4_track_read_host.restype = C.c_int64
+    lib.hbs_mp4_stbl_find_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]
+    lib.hbs_mp4_stbl_find_host.restype = C.c_int
+    lib.hbs_mp4_stbl_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    lib.hbs_mp4_stbl_samples.restype = C.c_int
     _lib = lib
     return lib
 
@@ -448,23 +461,44 @@ def mp4_read_params(track_id=0, trex_duration=0, trex_size=0, trex_flags=0, flag
     return p
 
 
-def mp4_init_read(segment_bytes, track_id=0):
+def mp4_init_read(segment_bytes, track_id=0, _call="hbs_mp4_init_read_host"):
     """hbs_mp4_init_read_host: the track record (an MP4_TRACK record) of an init segment (bytes-like) and the parameter-set NALs
     of its hvcC as slices of the segment, in array order.  Raises HbsError for what the call refuses."""
     lib = load_library()
+    read = getattr(lib, _call)
     seg = np.frombuffer(bytes(segment_bytes), dtype=np.uint8)
     trk = np.zeros(1, dtype=MP4_TRACK)
     sp = seg.ctypes.data_as(C.c_void_p) if seg.size else None
-    n = int(lib.hbs_mp4_init_read_host(sp, seg.size, int(track_id), trk.ctypes.data_as(C.c_void_p), None, None, 0))
+    n = int(read(sp, seg.size, int(track_id), trk.ctypes.data_as(C.c_void_p), None, None, 0))
     if n < 0:
-        raise HbsError("hbs_mp4_init_read_host: error %d" % n)
+        raise HbsError("%s: error %d" % (_call, n))
     off, size = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
-    got = int(lib.hbs_mp4_init_read_host(sp, seg.size, int(track_id), trk.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+    got = int(read(sp, seg.size, int(track_id), trk.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
                                          size.ctypes.data_as(C.c_void_p), n))
     if got != n:
-        raise HbsError("hbs_mp4_init_read_host: %d, then %d" % (n, got))
+        raise HbsError("%s: %d, then %d" % (_call, n, got))
     raw = seg.tobytes()
     return trk[0].copy(), [raw[int(off[i]): int(off[i]) + int(size[i])] for i in range(n)]
+
+
+def mp4_track_read(file_bytes, track_id=0):
+    """hbs_mp4_track_read_host: mp4_init_read for a progressive file (or its moov), which has no mvex: the same record with
+    the trex fields 0, and the parameter-set NALs of the hvcC."""
+    return mp4_init_read(file_bytes, track_id, _call="hbs_mp4_track_read_host")
+
+
+def mp4_stbl_find(data, base=0, track_id=0):
+    """hbs_mp4_stbl_find_host: where the sample table boxes of one track of a progressive MP4 lie (an ndarray[MP4_STBL] of one,
+    host memory).  data: the file, or its moov alone with base = the moov's position in the file (bytes-like).  Raises HbsError
+    for what the call refuses."""
+    lib = load_library()
+    seg = np.frombuffer(bytes(data), dtype=np.uint8)
+    rec = np.zeros(1, dtype=MP4_STBL)
+    rc = int(lib.hbs_mp4_stbl_find_host(seg.ctypes.data_as(C.c_void_p) if seg.size else None, seg.size, int(base), int(track_id),
+                                        rec.ctypes.data_as(C.c_void_p)))
+    if rc != 0:
+        raise HbsError("hbs_mp4_stbl_find_host: error %d" % rc)
+    return rec
 
 
 def rtp_frames(data, cap=None):
@@ -1440,6 +1474,44 @@ class Context:
         u64 = lambda x: x[: n * 8].cpu().numpy().view(np.uint64).copy()          # noqa: E731
         return (u64(so), u64(ss), u64(dt), u64(pt), fl[: n * 4].cpu().numpy().view(np.uint32).copy(),
                 fr[: m * MP4_FRAG.itemsize].cpu().numpy().view(MP4_FRAG).copy(), s)
+
+    def mp4_stbl_samples_async(self, data, in_bytes, tables, summary, sample_cap=0, sample_off=None, sample_size=None, dts=None, pts=None,
+                               sample_flags=None):
+        """Enqueue hbs_mp4_stbl_samples on the current torch stream.  data / summary / sample_off / sample_size / dts / pts /
+        sample_flags are device tensors (sample_off with sample_size None: plan only; dts, pts, sample_flags may be None); tables
+        is an ndarray[MP4_STBL] of one in host memory (mp4_stbl_find).  Returns the call's return code (0, or HBS_E_ARG for
+        arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if tables is not None:
+            tables = np.ascontiguousarray(tables, dtype=MP4_STBL)
+        return self.lib.hbs_mp4_stbl_samples(self.h, p(data), int(in_bytes), tables.ctypes.data_as(C.c_void_p) if tables is not None else None,
+                                             int(sample_cap), p(sample_off), p(sample_size), p(dts), p(pts), p(sample_flags), p(summary))
+
+    def mp4_stbl_samples(self, data, tables, in_bytes=None):
+        """Convenience: the sample table of the progressive MP4 whose table boxes lie in `data` (device uint8 tensor) where
+        `tables` (mp4_stbl_find) says.  Plans, allocates the exact tables, runs.  Returns (sample_off, sample_size, dts, pts,
+        flags, summary record), host arrays."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        self._check(self.mp4_stbl_samples_async(data, nbytes, tables, summary), "hbs_mp4_stbl_samples")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_stbl_samples: error %d (box %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        n = int(s["nal_count"])
+        if n > 0xFFFFFFFF:
+            raise HbsError("hbs_mp4_stbl_samples: %d samples" % n)
+        so, ss, dt, pt = (t.empty(max(n, 1) * 8, dtype=t.uint8, device=dev) for _ in range(4))
+        fl = t.empty(max(n, 1) * 4, dtype=t.uint8, device=dev)
+        self._check(self.mp4_stbl_samples_async(data, nbytes, tables, summary, sample_cap=n, sample_off=so, sample_size=ss, dts=dt, pts=pt,
+                                                sample_flags=fl), "hbs_mp4_stbl_samples")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_stbl_samples: error %d (sample %d)" % (int(s["error"]), int(s["reserved"][2]) - 1))
+        u64 = lambda x: x[: n * 8].cpu().numpy().view(np.uint64).copy()          # noqa: E731
+        return u64(so), u64(ss), u64(dt), u64(pt), fl[: n * 4].cpu().numpy().view(np.uint32).copy(), s
 
     # ---- access units -----------------------------------------------------------------
 

@@ -28,6 +28,7 @@
 #include "hbs_rtpord.h"
 #include "hbs_mp4.h"
 #include "hbs_mp4rd.h"
+#include "hbs_mp4stbl.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -49,8 +50,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kUws    hbs_rtp_unpack's scratch
  * kOws    hbs_rtp_order's scratch
  * kPws    hbs_mp4_fragment's scratch
- * kQws    hbs_mp4_samples' scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kBufs };
+ * kQws    hbs_mp4_samples' scratch
+ * kSws    hbs_mp4_stbl_samples' scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -915,6 +917,50 @@ int hbs_mp4_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const vo
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_mp4_samples(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_samples");
+}
+
+int hbs_mp4_stbl_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const hbs_mp4_stbl* tables, uint64_t sample_cap,
+                         uint64_t* d_sample_off, uint64_t* d_sample_size, uint64_t* d_dts, uint64_t* d_pts, uint32_t* d_sample_flags,
+                         hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_mp4_stbl) == 128 && sizeof(hbs_mp4_box_ref) == 16, "hbs_mp4_stbl_samples layouts");
+    if (!c || !d_summary || !d_in || !hbs::mp4_stbl_ok(tables) || in_bytes > hbs::kRdMaxIn || tables->file_bytes > hbs::kRdMaxIn) return HBS_E_ARG;
+    if ((d_sample_off == nullptr) != (d_sample_size == nullptr)) return HBS_E_ARG;
+    if (!d_sample_off && (d_dts || d_pts || d_sample_flags)) return HBS_E_ARG;
+    if (d_sample_off && sample_cap > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (misaligned(d_in, 15) || misaligned(d_summary, 15) || misaligned(d_sample_off, 7) || misaligned(d_sample_size, 7) || misaligned(d_dts, 7) ||
+        misaligned(d_pts, 7) || misaligned(d_sample_flags, 3)) {
+        snprintf(c->err, sizeof(c->err), "input/summary pointers must be 16-byte aligned, the 64-bit sample tables 8-byte, sample flags 4-byte");
+        return HBS_E_ARG;
+    }
+    hbs::StblArgs a;
+    memset(&a, 0, sizeof(a));
+    const hbs_mp4_box_ref* ref[hbs::kStBoxes] = {&tables->stsz, &tables->stco, &tables->stsc, &tables->stts, &tables->ctts, &tables->stss};
+    a.co64 = (tables->flags & HBS_MP4_STBL_CO64) != 0u;
+    const uint64_t fixed[hbs::kStBoxes] = {12, 8, 8, 8, 8, 8}, entry[hbs::kStBoxes] = {4, a.co64 ? 8u : 4u, 12, 8, 8, 4};
+    for (int b = 0; b < hbs::kStBoxes; ++b) {
+        const uint64_t off = ref[b]->off, bytes = ref[b]->bytes;
+        if (!bytes && b <= hbs::kStts) { snprintf(c->err, sizeof(c->err), "stsz, stco / co64, stsc and stts are required"); return HBS_E_ARG; }
+        if (bytes && (off > in_bytes || bytes > in_bytes - off)) { snprintf(c->err, sizeof(c->err), "a table box leaves the buffer"); return HBS_E_ARG; }
+        a.box[b].off = bytes ? off : 0; a.box[b].bytes = bytes;
+        /* what sizes the grids and the scratch: the entries the payload has bytes for (a count has 32 bits) */
+        const uint64_t room = bytes > fixed[b] ? (bytes - fixed[b]) / entry[b] : 0;
+        a.cap[b] = room < 0xFFFFFFFFull ? room : 0xFFFFFFFFull;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    a.src = d_in; a.n = in_bytes; a.file_bytes = tables->file_bytes ? tables->file_bytes : in_bytes;
+    a.summary = d_summary;
+    if (d_sample_off) {
+        a.out = true; a.sample_cap = sample_cap;
+        a.sample_off = reinterpret_cast<unsigned long long*>(d_sample_off); a.sample_size = reinterpret_cast<unsigned long long*>(d_sample_size);
+        a.dts = reinterpret_cast<unsigned long long*>(d_dts); a.pts = reinterpret_cast<unsigned long long*>(d_pts);
+        a.sample_flags = d_sample_flags;
+    }
+    const int rc = carve(c, c->buf[kSws], "hipMalloc(MP4 sample table scratch)", [&](hbs::Carver& w) { hbs::lay_mp4stbl(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_mp4_stbl_samples(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_stbl_samples");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,

@@ -326,9 +326,10 @@ inline int64_t mp4rd_hvcc(const uint8_t* p, uint64_t at, uint64_t end, int32_t& 
     return (int64_t)n;
 }
 
-/* one trak p[at, end): 1 a video track with an hvcC (out's track fields and the NALs filled), 0 not one, -1 malformed */
+/* one trak p[at, end): 1 a video track with an hvcC (out's track fields and the NALs filled; p[stbl_at, stbl_end) its stbl's
+ * children), 0 not one, -1 malformed */
 inline int mp4rd_trak(const uint8_t* p, uint64_t at, uint64_t end, hbs_mp4_track* out, int64_t& n_nals, uint64_t* nal_off, uint64_t* nal_bytes,
-                      uint64_t cap)
+                      uint64_t cap, uint64_t& stbl_at, uint64_t& stbl_end)
 {
     uint64_t a, e;
     int rc = mp4rd_child(p, at, end, HBS_MP4_FOURCC('t', 'k', 'h', 'd'), a, e);
@@ -353,6 +354,7 @@ inline int mp4rd_trak(const uint8_t* p, uint64_t at, uint64_t end, hbs_mp4_track
         rc = mp4rd_child(p, a, e, path[i], ca, ce);
         if (rc < 0) return -1;
         if (rc == 0) return i == 0 ? 0 : -1;                   /* (a trak without a minf is not ours; below it the boxes are required) */
+        if (i == 2) { stbl_at = a; stbl_end = e; }
         a = ca; e = ce;
     }
     if (e - a < 8) return -1;
@@ -378,32 +380,44 @@ inline int mp4rd_trak(const uint8_t* p, uint64_t at, uint64_t end, hbs_mp4_track
     return 0;
 }
 
-inline int64_t mp4_init_read_host(const uint8_t* seg, uint64_t n, uint32_t track_id, hbs_mp4_track* out, uint64_t* nal_off, uint64_t* nal_bytes,
-                                  uint64_t cap)
+/* The walk that hbs_mp4_init_read_host and hbs_mp4_stbl_find_host share: the moov of seg[0, n) (its children: seg[ma, me)) and
+ * in it the trak asked for -- track_id, or with 0 the first that is a video track with an hvcC; the others are stepped over,
+ * but must be well-formed.  t and the NALs as mp4rd_trak leaves them; seg[sa, se) the children of the track's stbl. */
+inline bool mp4rd_find_track(const uint8_t* seg, uint64_t n, uint32_t track_id, hbs_mp4_track& t, int64_t& n_nals, uint64_t* nal_off,
+                             uint64_t* nal_bytes, uint64_t cap, uint64_t& ma, uint64_t& me, uint64_t& sa, uint64_t& se)
 {
-    if (!seg || !out || n > kRdMaxIn || (cap && (!nal_off || !nal_bytes))) return HBS_E_ARG;
-    uint64_t ma, me;
-    if (mp4rd_child(seg, 0, n, HBS_MP4_FOURCC('m', 'o', 'o', 'v'), ma, me) <= 0) return HBS_E_ARG;
-    hbs_mp4_track t;
-    int64_t n_nals = -1;
+    if (mp4rd_child(seg, 0, n, HBS_MP4_FOURCC('m', 'o', 'o', 'v'), ma, me) <= 0) return false;
+    n_nals = -1;
     bool found = false;
     for (uint64_t at = ma; at < me;) {
         Mp4Box b;
-        if (!mp4rd_box(seg, at, me, b)) return HBS_E_ARG;
+        if (!mp4rd_box(seg, at, me, b)) return false;
         if (b.type == HBS_MP4_FOURCC('t', 'r', 'a', 'k') && !found) {
-            memset(&t, 0, sizeof(t));
+            hbs_mp4_track k;
+            memset(&k, 0, sizeof(k));
             /* the track asked for must be a video track with an hvcC; with track_id 0 the others are stepped over */
-            int64_t k = -1;
-            const int rc = mp4rd_trak(seg, at + b.head, at + b.size, &t, k, nal_off, nal_bytes, cap);
-            if (rc < 0) return HBS_E_ARG;
-            if (track_id == 0u ? rc == 1 : t.track_id == track_id) {
-                if (rc != 1) return HBS_E_ARG;
-                found = true; n_nals = k;
+            int64_t kn = -1;
+            uint64_t ka = 0, ke = 0;
+            const int rc = mp4rd_trak(seg, at + b.head, at + b.size, &k, kn, nal_off, nal_bytes, cap, ka, ke);
+            if (rc < 0) return false;
+            if (track_id == 0u ? rc == 1 : k.track_id == track_id) {
+                if (rc != 1) return false;
+                found = true; n_nals = kn; t = k; sa = ka; se = ke;
             }
         }
         at += b.size;
     }
-    if (!found) return HBS_E_ARG;
+    return found;
+}
+
+inline int64_t mp4_init_read_host(const uint8_t* seg, uint64_t n, uint32_t track_id, hbs_mp4_track* out, uint64_t* nal_off, uint64_t* nal_bytes,
+                                  uint64_t cap)
+{
+    if (!seg || !out || n > kRdMaxIn || (cap && (!nal_off || !nal_bytes))) return HBS_E_ARG;
+    uint64_t ma, me, sa, se;
+    hbs_mp4_track t;
+    int64_t n_nals = -1;
+    if (!mp4rd_find_track(seg, n, track_id, t, n_nals, nal_off, nal_bytes, cap, ma, me, sa, se)) return HBS_E_ARG;
     uint64_t xa, xe;
     if (mp4rd_child(seg, ma, me, HBS_MP4_FOURCC('m', 'v', 'e', 'x'), xa, xe) <= 0) return HBS_E_ARG;
     bool have_trex = false;

@@ -112,9 +112,11 @@ typedef struct hbs_ctx hbs_ctx;
  * warm-up call with the same arguments, which sizes the scratch, and replayed on other contents of the same buffers:
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
- *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples.
+ *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples,
+ *   hbs_mp4_stbl_samples.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
- * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py and tests/test_gpu_mp4_read.py replay, no
+ * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py and
+ * tests/test_gpu_mp4_stbl.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -613,7 +615,7 @@ int64_t hbs_mp4_init_host(const hbs_mp4_init_params* p, int flags,
  * Alignment: d_in, d_frag, d_summary 16 bytes; d_seg and the four 64-bit tables 8 bytes; d_sample_flags 4 bytes.
  * STATED LIMITS: one track a call; a missing tfdt is an error; the "end of the previous traf's data" base is not supported;
  * no encryption (senc, saiz, saio are stepped over; the samples stay as they are); no sidx-driven access (pass the segments);
- * one lane walks a segment's chain.
+ * a file without fragments is read by hbs_mp4_stbl_samples, below; one lane walks a segment's chain.
  *
  * hbs_mp4_init_read_host (plain C, no GPU): the counterpart of hbs_mp4_init_host.  It walks seg[0, n) by the box rule above:
  * moov; its trak boxes in order -- tkhd (version 0 or 1: track_id, width and height, the integer parts), mdia / mdhd (version
@@ -654,6 +656,91 @@ typedef struct hbs_mp4_track {      /* 64 bytes */
 } hbs_mp4_track;
 int64_t hbs_mp4_init_read_host(const uint8_t* seg, uint64_t n, uint32_t track_id /* 0: the first video track with an hvcC */,
                                hbs_mp4_track* out, uint64_t* nal_off, uint64_t* nal_bytes, uint64_t cap);
+
+/*
+ * ---- progressive MP4 -> sample table: stsz, stco / co64, stsc, stts, ctts, stss read on the device; the boxes found on the host
+ * A plain .mp4 / .mov is one moov whose stbl describes every sample, and one mdat.  hbs_mp4_stbl_find_host finds the six table
+ * boxes of one track; hbs_mp4_stbl_samples reads them from device memory and writes what hbs_mp4_samples writes for
+ * fragments: per sample its offset and size (what hbs_lenpref_to_annexb reads), decode time, presentation time and flags.
+ * Every integer in a box is big-endian; the tables lie at any byte alignment.
+ *
+ * hbs_mp4_stbl_find_host (plain C, no GPU) walks seg[0, n) by the box rule stated above hbs_mp4_samples and finds the moov and
+ * the trak exactly as hbs_mp4_init_read_host does (one walk serves both; track_id 0: the first track with an hvcC), then the
+ * children of its mdia / minf / stbl.  Of several boxes of one type the first is used, of stco and co64 whichever comes first.
+ * Every `off` is the payload's offset within seg (behind the box header) plus `base`: a caller who passes only the moov cut
+ * from file position P passes base = P and gets file offsets.  file_bytes is left 0.  HBS_E_ARG: a NULL seg or out, n above
+ * 2^62, a malformed chain, no such track, no stsz, stsc or stts, neither stco nor co64 (a stz2 without a stsz is such a file:
+ * compact sample sizes are a stated limit), one of the table boxes with an empty payload.  No byte at or behind seg + n is
+ * read.  The edit list (elst) is not applied: times are the media's (a stated limit).
+ * hbs_mp4_track_read_host is hbs_mp4_init_read_host for such a file: the same walk, the same record and parameter-set NALs
+ * (length_size for hbs_lenpref_to_annexb, the sets for hbs_au_insert), but no mvex is asked for -- a progressive file has
+ * none -- and the three trex fields of the record are 0.
+ *
+ * hbs_mp4_stbl_samples reads the boxes from d_in at the offsets in `tables`.  The rules, every payload beginning with
+ * version/flags(4):
+ *   stsz  sample_size(4) count N(4), then N sizes(4) iff sample_size == 0.  With sample_size != 0 nothing in the box bounds N.
+ *   stco  count C(4), then C chunk offsets(4);  co64 (HBS_MP4_STBL_CO64): offsets(8).
+ *   stsc  count E(4), then E entries first_chunk(4) samples_per_chunk(4) description index(4, ignored: a stated limit).
+ *         first_chunk is 1 in entry 0, strictly increasing, and at most C.  Entry e covers the chunks up to the next entry's
+ *         first_chunk, the last entry up to C.  samples_per_chunk 0 is valid: those chunks hold no sample.  The chunks must
+ *         hold N samples or more between them; surplus chunks and surplus room in the last chunk used are ignored.
+ *   stts  count(4), then entries sample_count(4) delta(4).  The counts must sum to N or more; surplus is ignored; entries of
+ *         count 0 are valid.
+ *   ctts  (optional) count(4), then entries sample_count(4) offset(4): unsigned at version 0, signed at version 1; a version
+ *         above 1 is an error.  Counts that sum to less than N leave the remaining samples at offset 0.
+ *   stss  (optional) count(4), then 1-based sample numbers(4), strictly increasing, none 0; numbers above N are ignored.
+ *         Absent: every sample is a sync sample.  Present and empty: none is.
+ * The versions of stsz, stco, co64, stsc, stts and stss must be 0; a payload shorter than its fixed part plus count x entry is
+ * an error.
+ * SAMPLE s, in table order: size from stsz; off = its chunk's offset + the sizes of the earlier samples of that chunk; dts =
+ * the sum of the earlier samples' deltas; pts = dts + composition offset; flags = 0 for a sync sample, 0x00010000 for any other
+ * (the bit hbs_mp4_samples documents).  All sums are exact 64-bit quantities and none wraps into a success: counts and
+ * samples_per_chunk of 2^32 - 1 are legal inputs to the checks.
+ *
+ * The stages are looked at in this order and the first that fails ends the call; on any error only the summary is written:
+ *   a table error     error = HBS_E_ARG, reserved[0] = 1 + the first broken box in the order stsz, stco, stsc, stts, ctts, stss
+ *                     (the coverage rules count at stsc and stts); no count means anything
+ *   N > sample_cap    (with outputs) error = HBS_E_CAPACITY; nal_count = N and nal_found = C are right, rbsp_bytes = 0
+ *   a sample error    (looked for only with outputs) error = HBS_E_ARG, reserved[2] = 1 + the lowest such sample: off + size
+ *                     above file_bytes (in_bytes when that is 0), an offset sum that wraps, dts of 2^62 or more, pts outside
+ *                     [0, 2^62); N and C are right, rbsp_bytes = 0
+ * d_summary: nal_count = N, nal_found = C, rbsp_bytes = the sum of the sizes, stream_bytes = in_bytes, stop_reason = 0.
+ * d_sample_off == NULL: plan only -- the table errors are looked for and the summary is written; sample_cap sizes nothing.
+ * WORK.  Grids and scratch are sized by the payload byte counts in `tables` and by sample_cap (a table cannot have more entries
+ * than its bytes allow), never by a count read from a box: a stsz of constant size or a stts of one entry that claims
+ * 2^32 - 1 samples costs a plan no more than an honest one.  With outputs the work is bounded by sample_cap plus the entries.
+ * Scratch: 64 bytes per 256 entries of the longest of stsc / stts / ctts / stss; plan only 64 bytes per 256 sizes of a stsz;
+ * with outputs 8 bytes an entry of stsc and ctts, 16 an entry of stts, and 128 bytes per 256 samples of sample_cap.
+ * Refused with HBS_E_ARG at once: unknown flags or non-zero reserved words; a required box (stsz, stco, stsc, stts) with
+ * bytes == 0, or a box that leaves d_in[0, in_bytes); in_bytes or file_bytes above 2^62; sample_cap above 2^32 - 1 with
+ * outputs; one sample table without the other, or d_dts, d_pts or d_sample_flags without the sample tables; missing or
+ * misaligned pointers.  Alignment: d_in and d_summary 16 bytes, the four 64-bit tables 8, d_sample_flags 4.
+ * Nothing outside d_sample_off / d_sample_size / d_dts / d_pts / d_sample_flags[0, N) and the summary is stored; no load
+ * touches a 16-byte granule that holds no byte of d_in[0, in_bytes); no mdat byte is read; no host synchronisation and no
+ * allocation once the scratch has its size.
+ * STATED LIMITS: one track a call; no stz2 (compact sample sizes); the edit list is not applied; the sample description index
+ * is ignored (one sample entry); no encryption (the samples stay as they are).
+ */
+#define HBS_MP4_STBL_CO64 1u           /* hbs_mp4_stbl.flags: .stco refers to a co64 (64-bit entries) */
+typedef struct hbs_mp4_box_ref { uint64_t off, bytes; } hbs_mp4_box_ref;  /* the payload behind the box header; bytes == 0: no such box */
+typedef struct hbs_mp4_stbl {        /* HOST memory, 128 bytes */
+    hbs_mp4_box_ref stsz, stco, stsc, stts, ctts, stss;   /* stco: the stco or the co64 */
+    uint32_t flags;                  /* HBS_MP4_STBL_CO64: .stco refers to a co64 (64-bit entries) */
+    uint32_t reserved0;              /* 0 */
+    uint64_t file_bytes;             /* what sample offsets are checked against; 0: in_bytes of the device call */
+    uint64_t reserved[2];            /* 0 */
+} hbs_mp4_stbl;
+int hbs_mp4_stbl_find_host(const uint8_t* seg, uint64_t n, uint64_t base, uint32_t track_id, hbs_mp4_stbl* out);
+int64_t hbs_mp4_track_read_host(const uint8_t* seg, uint64_t n, uint32_t track_id /* 0: the first video track with an hvcC */,
+                                hbs_mp4_track* out, uint64_t* nal_off, uint64_t* nal_bytes, uint64_t cap);
+
+int hbs_mp4_stbl_samples(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
+                         const hbs_mp4_stbl* tables,          /* host memory */
+                         uint64_t sample_cap,
+                         uint64_t* d_sample_off, uint64_t* d_sample_size,   /* both or neither; NULL: plan only */
+                         uint64_t* d_dts, uint64_t* d_pts,                  /* optional, each on its own */
+                         uint32_t* d_sample_flags,                          /* optional */
+                         hbs_summary* d_summary);
 
 /*
  * ---- MPEG transport stream (ISO/IEC 13818-1) -> Annex-B elementary stream, PES times ----------------------------------
