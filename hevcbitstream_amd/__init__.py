@@ -21,7 +21,8 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   RTP_ORDER_PARAMS, RTPO_MATCH_SSRC, RTPO_AFTER, rtp_order_params,
                   MP4_PARAMS, MP4_FRAG, MP4_INIT_PARAMS, MP4_CUT_AT_IRAP, MP4_HEV1, mp4_params, mp4_fragment_bytes, mp4_init,
                   MP4_READ_PARAMS, MP4_TRACK, mp4_read_params, mp4_init_read,
-                  MP4_STBL, MP4_STBL_CO64, mp4_stbl_find, mp4_track_read)
+                  MP4_STBL, MP4_STBL_CO64, mp4_stbl_find, mp4_track_read,
+                  MP4_STBL_WRITE_PARAMS, mp4_stbl_write_params, mp4_stbl_write_bytes, mp4_moov)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
            "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
@@ -39,4 +40,5 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "RTP_ORDER_PARAMS", "RTPO_MATCH_SSRC", "RTPO_AFTER", "rtp_order_params",
            "MP4_PARAMS", "MP4_FRAG", "MP4_INIT_PARAMS", "MP4_CUT_AT_IRAP", "MP4_HEV1", "mp4_params", "mp4_fragment_bytes", "mp4_init",
            "MP4_READ_PARAMS", "MP4_TRACK", "mp4_read_params", "mp4_init_read",
-           "MP4_STBL", "MP4_STBL_CO64", "mp4_stbl_find", "mp4_track_read"]
+           "MP4_STBL", "MP4_STBL_CO64", "mp4_stbl_find", "mp4_track_read",
+           "MP4_STBL_WRITE_PARAMS", "mp4_stbl_write_params", "mp4_stbl_write_bytes", "mp4_moov"]

@@ -95,6 +95,9 @@ EXT_NAL = np.dtype([("num_sei_messages", "<i4"), ("primary_pic_type", "<i4"), ("
 MP4_STBL = np.dtype([("stsz", "<u8", (2,)), ("stco", "<u8", (2,)), ("stsc", "<u8", (2,)), ("stts", "<u8", (2,)), ("ctts", "<u8", (2,)),
                      ("stss", "<u8", (2,)), ("flags", "<u4"), ("reserved0", "<u4"), ("file_bytes", "<u8"), ("reserved", "<u8", (2,))])
 MP4_STBL_CO64 = 1
+# layout of hbs_mp4_stbl_write_params (hbs_mp4_stbl_write)
+MP4_STBL_WRITE_PARAMS = np.dtype([("flags", "<u4"), ("max_chunk_samples", "<u4"), ("sample_duration", "<u4"), ("reserved0", "<u4"),
+                                  ("base_time", "<u8"), ("data_offset", "<u8")])
 
 EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stream", "hbs_ctx_use_own_stream",
            "hbs_ctx_get_stream",
@@ -115,7 +118,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_rtp_unpack", "hbs_rtp_frames_host", "hbs_rtp_order",
            "hbs_mp4_fragment", "hbs_mp4_fragment_bytes_host", "hbs_mp4_init_host",
            "hbs_mp4_samples", "hbs_mp4_init_read_host", "hbs_mp4_stbl_samples", "hbs_mp4_stbl_find_host",
-           "hbs_mp4_track_read_host"]
+           "hbs_mp4_track_read_host",
+           "hbs_mp4_stbl_write", "hbs_mp4_stbl_write_bytes_host", "hbs_mp4_moov_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -293,6 +297,13 @@ def load_library():
     lib.hbs_mp4_stbl_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
     lib.hbs_mp4_stbl_samples.restype = C.c_int
+    lib.hbs_mp4_stbl_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.hbs_mp4_stbl_write.restype = C.c_int
+    lib.hbs_mp4_stbl_write_bytes_host.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_uint32]
+    lib.hbs_mp4_stbl_write_bytes_host.restype = C.c_uint64
+    lib.hbs_mp4_moov_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
+    lib.hbs_mp4_moov_host.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -434,24 +445,47 @@ def mp4_fragment_bytes(samples, sample_bytes):
 
 
 def mp4_init(nals, track_id=1, timescale=90000, width=1920, height=1080, length_size=4, chroma_format_idc=1, bit_depth_luma=8,
-             bit_depth_chroma=8, flags=0):
+             bit_depth_chroma=8, flags=0, _moov=None):
     """hbs_mp4_init_host: the init segment (ftyp + moov) for the fragments of hbs_mp4_fragment, as bytes.  nals: the VPS / SPS /
     PPS NAL units (bytes-like, no start codes), in the order their arrays list them.  Raises HbsError for what the call refuses."""
     lib = load_library()
+    name = "hbs_mp4_moov_host" if _moov is not None else "hbs_mp4_init_host"
+    call = getattr(lib, name)
     prm = np.zeros(1, dtype=MP4_INIT_PARAMS)
     prm[0] = (track_id, timescale, width, height, length_size, chroma_format_idc, bit_depth_luma, bit_depth_chroma)
     bufs = [np.frombuffer(bytes(x), dtype=np.uint8) if len(x) else np.zeros(0, dtype=np.uint8) for x in nals]
     ptrs = (C.c_void_p * max(len(bufs), 1))(*[b.ctypes.data if b.size else None for b in bufs])
     sizes = np.array([b.size for b in bufs], dtype=np.uint64)
     args = (prm.ctypes.data_as(C.c_void_p), int(flags), C.cast(ptrs, C.c_void_p), sizes.ctypes.data_as(C.c_void_p), len(bufs))
-    need = int(lib.hbs_mp4_init_host(*args, None, 0))
+    if _moov is not None:
+        args += (int(_moov[0]), int(_moov[1]))
+    need = int(call(*args, None, 0))
     if need < 0:
-        raise HbsError("hbs_mp4_init_host: error %d" % need)
+        raise HbsError("%s: error %d" % (name, need))
     out = np.zeros(need, dtype=np.uint8)
-    got = int(lib.hbs_mp4_init_host(*args, out.ctypes.data_as(C.c_void_p), need))
+    got = int(call(*args, out.ctypes.data_as(C.c_void_p), need))
     if got != need:
-        raise HbsError("hbs_mp4_init_host: %d, then %d" % (need, got))
+        raise HbsError("%s: %d, then %d" % (name, need, got))
     return out.tobytes()
+
+
+def mp4_moov(nals, duration, tables_bytes, **kw):
+    """hbs_mp4_moov_host: ftyp and the moov of a progressive file up to and including the stsd, as bytes; the `tables_bytes` bytes
+    that hbs_mp4_stbl_write writes complete the moov.  duration: reserved[1] of that call's summary.  The other arguments are
+    mp4_init's.  Raises HbsError for what the call refuses."""
+    return mp4_init(nals, _moov=(duration, tables_bytes), **kw)
+
+
+def mp4_stbl_write_params(flags=0, max_chunk_samples=0, sample_duration=0, base_time=0, data_offset=0):
+    """an hbs_mp4_stbl_write_params record (ndarray[MP4_STBL_WRITE_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=MP4_STBL_WRITE_PARAMS)
+    p[0] = (flags, max_chunk_samples, sample_duration, 0, base_time, data_offset)
+    return p
+
+
+def mp4_stbl_write_bytes(n_samples, with_ctts=True, with_stss=True, flags=0):
+    """hbs_mp4_stbl_write_bytes_host: an upper bound of the bytes hbs_mp4_stbl_write writes for n_samples samples"""
+    return int(load_library().hbs_mp4_stbl_write_bytes_host(int(n_samples), int(bool(with_ctts)), int(bool(with_stss)), int(flags)))
 
 
 def mp4_read_params(track_id=0, trex_duration=0, trex_size=0, trex_flags=0, flags=0):
@@ -1512,6 +1546,41 @@ class Context:
             raise HbsError("hbs_mp4_stbl_samples: error %d (sample %d)" % (int(s["error"]), int(s["reserved"][2]) - 1))
         u64 = lambda x: x[: n * 8].cpu().numpy().view(np.uint64).copy()          # noqa: E731
         return u64(so), u64(ss), u64(dt), u64(pt), fl[: n * 4].cpu().numpy().view(np.uint32).copy(), s
+
+    def mp4_stbl_write_async(self, sample_off, sample_size, n_samples, params, summary, dts=None, pts=None, sample_flags=None, out=None,
+                             out_cap=0, tables=None):
+        """Enqueue hbs_mp4_stbl_write on the current torch stream.  sample_off / sample_size / dts / pts / sample_flags / out /
+        tables / summary are device tensors (dts, pts, sample_flags, tables may be None; out None: plan only); params is an
+        ndarray[MP4_STBL_WRITE_PARAMS] of one in host memory (mp4_stbl_write_params).  Returns the call's return code (0, or
+        HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=MP4_STBL_WRITE_PARAMS)
+        return self.lib.hbs_mp4_stbl_write(self.h, p(sample_off), p(sample_size), int(n_samples), p(dts), p(pts), p(sample_flags),
+                                           params.ctypes.data_as(C.c_void_p) if params is not None else None, p(out), int(out_cap),
+                                           p(tables), p(summary))
+
+    def mp4_stbl_write(self, sample_off, sample_size, n_samples, params, dts=None, pts=None, sample_flags=None):
+        """Convenience: the sample table boxes of the samples in the device tables.  Plans, allocates the exact output, runs.
+        Returns (boxes: device uint8 tensor of exactly T bytes, tables: ndarray[MP4_STBL] of one, summary record)."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        rec = t.zeros(MP4_STBL.itemsize, dtype=t.uint8, device=dev)
+        kw = dict(dts=dts, pts=pts, sample_flags=sample_flags)
+        self._check(self.mp4_stbl_write_async(sample_off, sample_size, n_samples, params, summary, **kw), "hbs_mp4_stbl_write")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_stbl_write: error %d (sample %d, box %d)" % (int(s["error"]), int(s["reserved"][2]) - 1, int(s["reserved"][0]) - 1))
+        total = int(s["stream_bytes"])
+        out = t.empty(total, dtype=t.uint8, device=dev)
+        self._check(self.mp4_stbl_write_async(sample_off, sample_size, n_samples, params, summary, out=out, out_cap=total, tables=rec, **kw),
+                    "hbs_mp4_stbl_write")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_mp4_stbl_write: error %d" % int(s["error"]))
+        return out, rec.cpu().numpy().view(MP4_STBL).copy(), s
 
     # ---- access units -----------------------------------------------------------------
 

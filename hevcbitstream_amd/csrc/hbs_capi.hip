@@ -29,6 +29,7 @@
 #include "hbs_mp4.h"
 #include "hbs_mp4rd.h"
 #include "hbs_mp4stbl.h"
+#include "hbs_mp4stblw.h"
 
 constexpr int kTimingRing = 64;       /* timed calls whose event pairs are kept (hbs_ctx_kernel_ms_back) */
 
@@ -51,8 +52,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kOws    hbs_rtp_order's scratch
  * kPws    hbs_mp4_fragment's scratch
  * kQws    hbs_mp4_samples' scratch
- * kSws    hbs_mp4_stbl_samples' scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kBufs };
+ * kSws    hbs_mp4_stbl_samples' scratch
+ * kVws    hbs_mp4_stbl_write's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -961,6 +963,33 @@ int hbs_mp4_stbl_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, con
     if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
     const hipError_t e = hbs::launch_mp4_stbl_samples(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_stbl_samples");
+}
+
+int hbs_mp4_stbl_write(hbs_ctx* c, const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples, const uint64_t* d_dts,
+                       const uint64_t* d_pts, const uint32_t* d_sample_flags, const hbs_mp4_stbl_write_params* params, uint8_t* d_out,
+                       uint64_t out_cap, hbs_mp4_stbl* d_tables, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_mp4_stbl_write_params) == 32, "hbs_mp4_stbl_write_params layout");
+    if (!c || !d_summary || !hbs::mp4_stbl_write_params_ok(params) || n_samples > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_samples && (!d_sample_off || !d_sample_size)) return HBS_E_ARG;
+    if (misaligned(d_out, 15) || misaligned(d_tables, 15) || misaligned(d_summary, 15) || misaligned(d_sample_off, 7) || misaligned(d_sample_size, 7) ||
+        misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_sample_flags, 3)) {
+        snprintf(c->err, sizeof(c->err), "output/box record/summary pointers must be 16-byte aligned, the 64-bit sample tables 8-byte, sample flags 4-byte");
+        return HBS_E_ARG;
+    }
+    if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::StblwArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in.off = d_sample_off; a.in.size = d_sample_size; a.in.n = n_samples; a.in.dts = d_dts; a.in.pts = d_pts; a.in.sflags = d_sample_flags;
+    a.in.sample_duration = params->sample_duration; a.in.base_time = params->base_time; a.in.data_offset = params->data_offset;
+    a.co64 = (params->flags & HBS_MP4_STBL_CO64) != 0u; a.max_chunk = params->max_chunk_samples;
+    a.out = d_out; a.out_cap = out_cap; a.tables = d_tables; a.summary = d_summary;
+    const int rc = carve(c, c->buf[kVws], "hipMalloc(MP4 sample table writer scratch)", [&](hbs::Carver& w) { hbs::lay_mp4stblw(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_mp4_stbl_write(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_stbl_write");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,

@@ -1,10 +1,10 @@
 /*
- * hbs_mp4.h -- hbs_mp4_fragment and hbs_mp4_init_host (include/hevcbitstream_amd.h): the rule that lays one fMP4 fragment
- * (moof + mdat, ISO/IEC 14496-12) out, as host/device inline functions -- mp4_head_word gives every 32-bit word of the
- * container bytes in front of a fragment's samples, mp4_frag_byte the byte at a fragment-relative offset, mp4_len_byte a byte
- * of a record's length field; the copy kernel of hbs_mp4.hip, the host checks and the tests all run them -- the times' rule,
- * the init segment's builder (plain host code, no GPU), and the host-visible launcher.  Everything above the launcher compiles
- * with plain g++.
+ * hbs_mp4.h -- hbs_mp4_fragment, hbs_mp4_init_host and hbs_mp4_moov_host (include/hevcbitstream_amd.h): the rule that lays
+ * one fMP4 fragment (moof + mdat, ISO/IEC 14496-12) out, as host/device inline functions -- mp4_head_word gives every 32-bit
+ * word of the container bytes in front of a fragment's samples, mp4_frag_byte the byte at a fragment-relative offset,
+ * mp4_len_byte a byte of a record's length field; the copy kernel of hbs_mp4.hip, the host checks and the tests all run them --
+ * the times' rule, the builder of the init segment and of a progressive file's moov (mp4_moov_build: plain host code, no GPU),
+ * and the host-visible launcher.  Everything above the launcher compiles with plain g++.
  */
 #ifndef HBS_MP4_H
 #define HBS_MP4_H
@@ -158,9 +158,9 @@ struct Mp4Writer {
     void bytes(const uint8_t* b, uint64_t k) { for (uint64_t i = 0; i < k; ++i) u8(b[i]); }
     uint64_t box(uint32_t fourcc) { const uint64_t at = n; u32(0); u32(fourcc); return at; }
     uint64_t full(uint32_t fourcc, uint32_t flags) { const uint64_t at = box(fourcc); u32(flags & 0xFFFFFFu); return at; }
-    void end(uint64_t at)
+    void end(uint64_t at, uint64_t behind = 0)                  /* behind: bytes of the box that the caller appends later */
     {
-        const uint64_t size = n - at;
+        const uint64_t size = n - at + behind;
         if (p) { p[at] = (uint8_t)(size >> 24); p[at + 1] = (uint8_t)(size >> 16); p[at + 2] = (uint8_t)(size >> 8); p[at + 3] = (uint8_t)size; }
     }
     void matrix() { u32(0x00010000u); zeros(12); u32(0x00010000u); zeros(12); u32(0x40000000u); }
@@ -180,9 +180,16 @@ inline uint32_t mp4_strip_prefix(const uint8_t* nal, uint64_t n, uint8_t* out, u
     return got;
 }
 
-inline int64_t mp4_init_host(const hbs_mp4_init_params* p, int flags, const uint8_t* const* nal, const uint64_t* nal_bytes, uint64_t n,
-                             uint8_t* out, uint64_t cap)
+/* hbs_mp4_init_host (prog == nullptr) and hbs_mp4_moov_host share one builder: with a prog the times carry its duration, the
+ * stbl ends behind the stsd, there is no mvex, and every box that holds the stbl counts prog->tables_bytes more than is written */
+struct Mp4Prog { uint64_t duration, tables_bytes; };
+
+inline int64_t mp4_moov_build(const hbs_mp4_init_params* p, int flags, const uint8_t* const* nal, const uint64_t* nal_bytes, uint64_t n,
+                              const Mp4Prog* prog, uint8_t* out, uint64_t cap)
 {
+    if (prog && (prog->duration > 0xFFFFFFFFull || prog->tables_bytes % 4u != 0 || prog->tables_bytes > 0xFFFFFFFFull)) return HBS_E_ARG;
+    const uint32_t dur = prog ? (uint32_t)prog->duration : 0u;
+    const uint64_t tb = prog ? prog->tables_bytes : 0;
     if (!p || (flags & ~HBS_MP4_HEV1) || !nal || !nal_bytes || n == 0 || n > 65535u || (cap && !out)) return HBS_E_ARG;
     if (p->track_id == 0 || p->track_id == 0xFFFFFFFFu || p->timescale == 0) return HBS_E_ARG;
     if (p->width < 1 || p->width > 65535u || p->height < 1 || p->height > 65535u) return HBS_E_ARG;
@@ -212,21 +219,21 @@ inline int64_t mp4_init_host(const hbs_mp4_init_params* p, int flags, const uint
         const uint64_t moov = w.box(HBS_MP4_FOURCC('m', 'o', 'o', 'v'));
         {
             const uint64_t mvhd = w.full(HBS_MP4_FOURCC('m', 'v', 'h', 'd'), 0);
-            w.u32(0); w.u32(0); w.u32(p->timescale); w.u32(0);
+            w.u32(0); w.u32(0); w.u32(p->timescale); w.u32(dur);
             w.u32(0x00010000u); w.u16(0x0100u); w.zeros(10);
             w.matrix(); w.zeros(24); w.u32(p->track_id + 1u);
             w.end(mvhd);
             const uint64_t trak = w.box(HBS_MP4_FOURCC('t', 'r', 'a', 'k'));
             {
                 const uint64_t tkhd = w.full(HBS_MP4_FOURCC('t', 'k', 'h', 'd'), 3);
-                w.u32(0); w.u32(0); w.u32(p->track_id); w.u32(0); w.u32(0);
+                w.u32(0); w.u32(0); w.u32(p->track_id); w.u32(0); w.u32(dur);
                 w.zeros(8); w.u16(0); w.u16(0); w.u16(0); w.u16(0);
                 w.matrix(); w.u32(p->width << 16); w.u32(p->height << 16);
                 w.end(tkhd);
                 const uint64_t mdia = w.box(HBS_MP4_FOURCC('m', 'd', 'i', 'a'));
                 {
                     const uint64_t mdhd = w.full(HBS_MP4_FOURCC('m', 'd', 'h', 'd'), 0);
-                    w.u32(0); w.u32(0); w.u32(p->timescale); w.u32(0); w.u16(0x55C4u); w.u16(0);
+                    w.u32(0); w.u32(0); w.u32(p->timescale); w.u32(dur); w.u16(0x55C4u); w.u16(0);
                     w.end(mdhd);
                     const uint64_t hdlr = w.full(HBS_MP4_FOURCC('h', 'd', 'l', 'r'), 0);
                     w.u32(0); w.u32(HBS_MP4_FOURCC('v', 'i', 'd', 'e')); w.zeros(12);
@@ -267,27 +274,46 @@ inline int64_t mp4_init_host(const hbs_mp4_init_params* p, int flags, const uint
                                 }
                             }
                             w.end(hvcc); w.end(entry); w.end(stsd);
-                            const uint64_t stts = w.full(HBS_MP4_FOURCC('s', 't', 't', 's'), 0); w.u32(0); w.end(stts);
-                            const uint64_t stsc = w.full(HBS_MP4_FOURCC('s', 't', 's', 'c'), 0); w.u32(0); w.end(stsc);
-                            const uint64_t stsz = w.full(HBS_MP4_FOURCC('s', 't', 's', 'z'), 0); w.u32(0); w.u32(0); w.end(stsz);
-                            const uint64_t stco = w.full(HBS_MP4_FOURCC('s', 't', 'c', 'o'), 0); w.u32(0); w.end(stco);
+                            if (!prog) {
+                                const uint64_t stts = w.full(HBS_MP4_FOURCC('s', 't', 't', 's'), 0); w.u32(0); w.end(stts);
+                                const uint64_t stsc = w.full(HBS_MP4_FOURCC('s', 't', 's', 'c'), 0); w.u32(0); w.end(stsc);
+                                const uint64_t stsz = w.full(HBS_MP4_FOURCC('s', 't', 's', 'z'), 0); w.u32(0); w.u32(0); w.end(stsz);
+                                const uint64_t stco = w.full(HBS_MP4_FOURCC('s', 't', 'c', 'o'), 0); w.u32(0); w.end(stco);
+                            }
                         }
-                        w.end(stbl);
+                        w.end(stbl, tb);
                     }
-                    w.end(minf);
+                    w.end(minf, tb);
                 }
-                w.end(mdia);
+                w.end(mdia, tb);
             }
-            w.end(trak);
-            const uint64_t mvex = w.box(HBS_MP4_FOURCC('m', 'v', 'e', 'x'));
-            const uint64_t trex = w.full(HBS_MP4_FOURCC('t', 'r', 'e', 'x'), 0);
-            w.u32(p->track_id); w.u32(1); w.u32(0); w.u32(0); w.u32(0);
-            w.end(trex); w.end(mvex);
+            w.end(trak, tb);
+            if (!prog) {
+                const uint64_t mvex = w.box(HBS_MP4_FOURCC('m', 'v', 'e', 'x'));
+                const uint64_t trex = w.full(HBS_MP4_FOURCC('t', 'r', 'e', 'x'), 0);
+                w.u32(p->track_id); w.u32(1); w.u32(0); w.u32(0); w.u32(0);
+                w.end(trex); w.end(mvex);
+            }
         }
-        w.end(moov);
+        w.end(moov, tb);
+        if (prog && w.n - moov + tb > 0xFFFFFFFFull) return HBS_E_ARG;   /* the moov's size has 32 bits */
         if (pass || w.n > cap) return (int64_t)w.n;          /* (the sets are at most 65535 x 65537 bytes: no wrap) */
     }
     return HBS_E_ARG;                                          /* not reached */
+}
+
+inline int64_t mp4_init_host(const hbs_mp4_init_params* p, int flags, const uint8_t* const* nal, const uint64_t* nal_bytes, uint64_t n,
+                             uint8_t* out, uint64_t cap)
+{
+    return mp4_moov_build(p, flags, nal, nal_bytes, n, nullptr, out, cap);
+}
+
+/* hbs_mp4_moov_host: ftyp and the moov up to and including the stsd; the tables_bytes of hbs_mp4_stbl_write complete it */
+inline int64_t mp4_moov_host(const hbs_mp4_init_params* p, int flags, const uint8_t* const* nal, const uint64_t* nal_bytes, uint64_t n,
+                             uint64_t duration, uint64_t tables_bytes, uint8_t* out, uint64_t cap)
+{
+    const Mp4Prog prog{duration, tables_bytes};
+    return mp4_moov_build(p, flags, nal, nal_bytes, n, &prog, out, cap);
 }
 
 #ifdef __HIPCC__

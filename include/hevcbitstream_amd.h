@@ -113,10 +113,10 @@ typedef struct hbs_ctx hbs_ctx;
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
  *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples,
- *   hbs_mp4_stbl_samples.
+ *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
- * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py and
- * tests/test_gpu_mp4_stbl.py replay, no
+ * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py,
+ * tests/test_gpu_mp4_stbl.py and tests/test_gpu_mp4_stbl_write.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -741,6 +741,102 @@ int hbs_mp4_stbl_samples(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
                          uint64_t* d_dts, uint64_t* d_pts,                  /* optional, each on its own */
                          uint32_t* d_sample_flags,                          /* optional */
                          hbs_summary* d_summary);
+
+/*
+ * ---- sample table -> progressive MP4: stts, ctts, stss, stsc, stsz, stco / co64 written on the device; the moov around them on the host
+ * The counterpart of hbs_mp4_stbl_samples.  hbs_mp4_stbl_write takes the per-sample tables that hbs_annexb_to_lenpref,
+ * hbs_mp4_fragment, hbs_mp4_samples and hbs_mp4_stbl_samples write -- offset and size, optionally decode time, presentation
+ * time and flags -- and writes the children of a stbl behind its stsd; hbs_mp4_moov_host writes ftyp and the moov up to and
+ * including that stsd.  With the caller's 8 bytes of mdat header and the sample bytes, which already lie on the device, that is
+ * a whole .mp4.  No sample byte (mdat) is read.
+ *
+ * OUTPUT.  d_out receives whole boxes in this order: stts, ctts (iff d_pts), stss (iff d_sample_flags), stsc, stsz, then stco or,
+ * with HBS_MP4_STBL_CO64, co64.  Each is size(4) type(4) version/flags(4) = 0 (ctts: see below), then the payload exactly as
+ * the section above specifies it for the reader.  Every integer is big-endian, every box size a multiple of 4; the T bytes of
+ * the six boxes are written with 32-bit stores and no byte outside [d_out, d_out + T) is touched.
+ * THE RULES, with N = n_samples, o(k) = d_sample_off[k] + data_offset and z(k) = d_sample_size[k]:
+ *   CHUNKS  Sample k is contiguous iff k > 0 and d_sample_off[k] == d_sample_off[k-1] + z(k-1), taken exactly.  s(k) is the
+ *           largest j <= k that is not contiguous.  Sample k begins a chunk iff k == s(k), or max_chunk_samples > 0 and
+ *           (k - s(k)) % max_chunk_samples == 0 (the form of hbs_mp4_fragment's cut rule).  There are C chunks; chunk c has the
+ *           first sample f_c and L_c samples.
+ *   stco    count C, then o(f_c) in 32 bits; co64: in 64 bits.
+ *   stsc    an entry (c + 1, L_c, 1) for every chunk c with c == 0 or L_c != L_(c-1); N == 0: no entry.
+ *   stsz    if N > 0, every z(k) equals z(0) and z(0) != 0: sample_size = z(0), count N, no table.  Otherwise sample_size = 0,
+ *           count N, then the N sizes.
+ *   stts    dts(k) = d_dts ? d_dts[k] : base_time + k * sample_duration, exactly.  delta(k) = dts(k+1) - dts(k); delta(N-1),
+ *           and every delta when d_dts == NULL, is sample_duration.  The entries are run-length: an entry begins at k == 0 and
+ *           wherever delta(k) != delta(k-1).  d_dts == NULL: one entry (N, sample_duration), none for N == 0.
+ *   ctts    written iff d_pts != NULL, even when every offset is 0.  cts(k) = d_pts[k] - dts(k), run-length in the same way;
+ *           version 1 (signed offsets) iff some cts(k) < 0, else version 0.
+ *   stss    written iff d_sample_flags != NULL, even when empty: the 1-based numbers of the samples with
+ *           (d_sample_flags[k] & 0x00010000) == 0, ascending.
+ * A SAMPLE ERROR, all taken exactly in 64 bits: z(k) above 2^32 - 1; an o(k) that wraps, or o(k) + z(k) at or above 2^62;
+ * without HBS_MP4_STBL_CO64 a chunk's o(f_c) above 2^32 - 1, reported at f_c; dts(k) of 2^62 or more; a delta(k) outside
+ * [0, 2^32 - 1], reported at k; d_pts[k] of 2^62 or more; cts(k) outside [-2^31, 2^31 - 1].
+ * A BOX SIZE ERROR: a box whose size would pass 2^32 - 1 (an stts, ctts or stsc of 2^29 entries or so and more, a co64 or an
+ * stsz or stss of near 2^32).
+ *
+ * d_summary: nal_count = N, nal_found = C, rbsp_bytes = the sum of the z(k), stream_bytes = T, stop_reason = 0, reserved[1] =
+ * the sum of all deltas (the media duration for hbs_mp4_moov_host).  The stages are looked at in this order and the first that
+ * fails ends the call:
+ *   a sample error     error = HBS_E_ARG, reserved[2] = 1 + the lowest such sample; only nal_count means anything
+ *   a box size error   error = HBS_E_ARG, reserved[0] = 1 + the box, numbered in the output's order (stts 0 .. stco / co64 5);
+ *                      only nal_count means anything
+ *   out_cap < T        (with a d_out) error = HBS_E_CAPACITY; the counts, T and the duration are right
+ * On any error nothing but the summary is written.  d_out == NULL: plan only -- the same checks run, the summary and d_tables
+ * are written.  T does not depend on data_offset, because stco or co64 is the caller's flag, not chosen from the offsets: so a
+ * plan gives the T that the real call will write.
+ * d_tables (optional, DEVICE memory) is the hbs_mp4_stbl that hbs_mp4_stbl_find_host would fill for these boxes with a base
+ * that makes d_out offset 0: payload offsets behind the 8-byte box headers, bytes == 0 for an absent ctts / stss, flags = the
+ * CO64 bit, file_bytes = 0, reserved words 0.  Copied to the host it is the `tables` argument of hbs_mp4_stbl_samples.
+ * Refused with HBS_E_ARG at once: unknown flags or a non-zero reserved0; n_samples above 2^32 - 1; base_time or data_offset of
+ * 2^62 or more; out_cap above 2^46 with a d_out; a missing d_summary or params, missing sample tables with n_samples > 0;
+ * misaligned pointers.  Alignment: the four 64-bit tables 8 bytes, d_sample_flags 4, d_out, d_tables and d_summary 16.
+ * n_samples == 0 is valid: four boxes of count 0 (68 bytes), plus a ctts / stss of count 0 if asked for.
+ * hbs_mp4_stbl_write_bytes_host: an upper bound of T -- an entry a sample in every box -- for a caller who does not plan; 0 for
+ * n_samples above 2^32 - 1.
+ * GUARANTEES: no host synchronisation; no allocation once the scratch has its size; the scratch comes from the context's
+ * workspace and is sized by n_samples alone (24 bytes a sample, 200 bytes per 256 samples, 256 bytes); every grid is sized by
+ * n_samples, never by a count computed on the device; no sample byte is read.
+ *
+ * hbs_mp4_moov_host (plain C, no GPU) writes ftyp and the moov up to and including the stsd: everything as hbs_mp4_init_host
+ * specifies it, except that there is no mvex, the stbl holds the stsd alone (no empty tables), mvhd, tkhd and mdhd carry
+ * `duration`, and the sizes of moov, trak, mdia, minf and stbl already count tables_bytes more than is written.  The stbl is the
+ * last child all the way up, so this prefix followed by the T bytes of hbs_mp4_stbl_write (tables_bytes = T, duration =
+ * reserved[1] of its summary) is a complete moov.  Returns the bytes of the prefix; it is written only when cap suffices.
+ * HBS_E_ARG: everything hbs_mp4_init_host refuses; a duration above 2^32 - 1 (the boxes are version 0: a stated limit); a
+ * tables_bytes that is not a multiple of 4; a tables_bytes that takes the moov past 2^32 - 1.
+ * THE TWO FILE LAYOUTS.  The mdat header is the caller's 8 bytes: size(4) = 8 + the sample bytes, 'mdat'; the size has 32
+ * bits, so the samples of one file stay below 2^32 - 8 bytes (there is no 64-bit mdat: a stated limit).
+ *   ftyp + mdat + moov   one call: the prefix has F bytes of ftyp (its first box), data_offset = F + 8; the file is ftyp, the
+ *                        mdat header, the samples, the prefix behind its ftyp, the T bytes.
+ *   ftyp + moov + mdat   plan first (d_out == NULL) and read T from the summary; the prefix has P bytes; then the real call
+ *                        with data_offset = P + T + 8; the file is the prefix, the T bytes, the mdat header, the samples.
+ * STATED LIMITS: one track; no edit list (a stream with reordering begins with a positive composition offset); no stz2; no
+ * sdtp; one sample entry (every stsc entry names description 1); no encryption.
+ */
+typedef struct hbs_mp4_stbl_write_params {   /* HOST memory, 32 bytes */
+    uint32_t flags;              /* HBS_MP4_STBL_CO64: write a co64; otherwise a stco */
+    uint32_t max_chunk_samples;  /* 0: chunks are cut by contiguity alone */
+    uint32_t sample_duration;    /* delta of the last sample, and of every sample when d_dts == NULL */
+    uint32_t reserved0;          /* 0 */
+    uint64_t base_time;          /* with d_dts == NULL: dts(k) = base_time + k * sample_duration */
+    uint64_t data_offset;        /* added to every d_sample_off[k]: where the sample bytes will lie in the file */
+} hbs_mp4_stbl_write_params;
+
+int hbs_mp4_stbl_write(hbs_ctx* ctx,
+                       const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
+                       const uint64_t* d_dts /* nullable */, const uint64_t* d_pts /* nullable */,
+                       const uint32_t* d_sample_flags /* nullable */,
+                       const hbs_mp4_stbl_write_params* params,
+                       uint8_t* d_out /* NULL: plan only */, uint64_t out_cap,
+                       hbs_mp4_stbl* d_tables /* optional, DEVICE memory, 128 bytes, 16-aligned */,
+                       hbs_summary* d_summary);
+uint64_t hbs_mp4_stbl_write_bytes_host(uint64_t n_samples, int with_ctts, int with_stss, uint32_t flags);  /* upper bound */
+int64_t hbs_mp4_moov_host(const hbs_mp4_init_params* p, int flags,
+                          const uint8_t* const* nal, const uint64_t* nal_bytes, uint64_t n,
+                          uint64_t duration, uint64_t tables_bytes,
+                          uint8_t* out, uint64_t cap);   /* bytes needed; written only when cap suffices; HBS_E_ARG */
 
 /*
  * ---- MPEG transport stream (ISO/IEC 13818-1) -> Annex-B elementary stream, PES times ----------------------------------
