@@ -5,15 +5,33 @@ holds the block counts and the expected errors on the CPU, so that the GPU tests
 
 A case is a Case: `a` holds the call's arguments (host arrays and numbers), `caps` the capacities a run is given, `room` what
 the outputs of a run hold in front of their canaries (the needs of the good case the variant was made from), `bad` the edited
-entry of a malformed variant.  want(case) is the reference's answer to a run, want(case, plan=True) to a plan."""
+entry of a malformed variant.  want(case) is the reference's answer to a run, want(case, plan=True) to a plan.
+
+CALLS2 are the seven calls that came later, for tests/test_gpu_sequences_rtp_mp4.py: hbs_rtp_pack without and with
+HBS_RTP_AGGREGATE, hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples, hbs_mp4_stbl_samples and hbs_mp4_stbl_write.
+Their scratch is laid out by capacities of the caller as well, so they have a variant a capacity that is one short (SHORTS) and
+a "roomy" variant with every capacity well above the need, whose outputs are as large as the capacities (`spare`: the room behind
+what is written).  A malformed variant of theirs says which summary word names the fault and with what (`named`), whether a plan
+looks for it (`in_plan`) and which table the edited entry lies in (`among`).  order_of, unpack_of, samples_of and stbl_of are the
+later stages of the pipelines, each on what the reference says the stage in front puts out."""
 import numpy as np
 
 from tests import _auins_ref as INS
 from tests import _filter_ref as F
 from tests import _lenpref_ref as LP
+from tests import _mp4_read_ref as MR
+from tests import _mp4_ref as MF
+from tests import _mp4_stbl_ref as MS
+from tests import _mp4_stbl_write_ref as MW
+from tests import _rtp_ap_ref as RA
+from tests import _rtp_order_ref as RO
+from tests import _rtp_ref as R
+from tests import _rtp_unpack_ref as RU
 from tests import _ts_ref as TSD
 from tests import _tsmux_ref as TSM
 from tests.test_gpu_lenpref import random_aus
+from tests.test_gpu_mp4_read import moofs_of
+from tests.test_gpu_mp4_stbl import case as stbl_case, track as stbl_track
 from tests.test_gpu_ts import FAULTS
 
 CALLS = ("a2l", "l2a", "tsd", "tsm", "ins")          # annexb_to_lenpref, lenpref_to_annexb, ts_demux, ts_mux, au_insert
@@ -24,12 +42,36 @@ E_ARG, E_CAPACITY = -3, -4
 NAL_BLOCK, SAMPLE_BLOCK, PACKET_BLOCK, TSM_AU_BLOCK, INS_AU_BLOCK = 2048, 256, 2048, 256, 256
 TSM_COPY_BLOCK = 2048                                 # output packets of a copy workgroup of hbs_ts_mux
 PID = 0x100
+# the RTP calls, after CALLS: hbs_rtp_pack without and with HBS_RTP_AGGREGATE, hbs_rtp_unpack, hbs_rtp_order
+RTP_CALLS = ("rtp", "rtpa", "rtpu", "rtpo")
+# ... and the MP4 calls: hbs_mp4_fragment, hbs_mp4_samples, hbs_mp4_stbl_samples, hbs_mp4_stbl_write
+MP4_CALLS = ("mp4f", "mp4s", "stbl", "stblw")
+CALLS2 = RTP_CALLS + MP4_CALLS
+# items of a plan workgroup (hbs_rtp.h: kRtpNalsPerBlock = kRtpPlanLanes, hbs_rtpun.h: kRtpuPacketsPerBlock, hbs_rtpord.h:
+# kRtpoLanes, a lane a packet or a lane a slot) and the output bytes of a copy workgroup (hbs_rtp.h: kRtpTileBytes; hbs_rtp_unpack
+# copies through the piece table, whose tiles are as large)
+RTP_NAL_BLOCK, RTPU_PACKET_BLOCK, RTPO_BLOCK = 256, 256, 256
+TILE = 64 * 1024
+# hbs_mp4.h: kMp4NalsPerBlock = kMp4Lanes * kMp4NalsPer, kMp4AusPerBlock = kMp4Lanes, kMp4TileBytes = 64 KiB; hbs_mp4rd.h: kRdLanes
+# (segments, moofs and samples); hbs_mp4stbl.h: kStLanes (table entries and samples); hbs_mp4stblw.h: kSwLanes (samples, chunks, runs)
+MP4_NAL_BLOCK, MP4_AU_BLOCK, MP4RD_BLOCK, STBL_BLOCK, STBLW_BLOCK = 256, 256, 256, 256, 256
+ROOM_ITEMS, ROOM_BYTES = 3 * 256 + 1, TILE + 1        # what a roomy variant gives a counted and a byte capacity above the need
+# the capacities a run is given one short, a variant each; "short_span" is hbs_rtp_order's max_span
+SHORTS = dict(rtp=("short",), rtpa=("short",), rtpu=("short", "short_nal", "short_au"), rtpo=("short", "short_span"),
+              mp4f=("short", "short_frag"), mp4s=("short_moof", "short_sample"), stbl=("short_sample",), stblw=("short",))
+SHORT_CAP = dict(short="out_cap", short_nal="nal_cap", short_au="au_cap", short_frag="frag_cap", short_moof="moof_cap",
+                 short_sample="sample_cap")
+PLAN_SHORT = ("short_span", "short_moof")             # capacities a plan looks at as well: max_span, moof_cap
 
 
 class Case:
     def __init__(self, call, name, a, bad=None):
         self.call, self.name, self.a, self.bad = call, name, a, bad
         self.caps, self.room = {}, {}
+        self.spare = {}                                # output -> the bytes of room behind what a roomy variant writes
+        # a malformed variant: the summary word that names the fault and its value (1 + bad, or 1 + the box for a table error of
+        # hbs_mp4_stbl_samples); does a plan find the fault; (items, items per workgroup) of the table the edited entry lies in
+        self.named, self.in_plan, self.among = None, True, None
         self._want = {}
 
     def __repr__(self):
@@ -43,6 +85,22 @@ def blocks(n, per):
 def items(case):
     """what the call's plan kernels count -> a tuple of (items, items per plan workgroup)"""
     a = case.a
+    if case.call in ("rtp", "rtpa"):
+        return ((len(a["index"]), RTP_NAL_BLOCK),)
+    if case.call == "rtpu":
+        return ((len(a["off"]), RTPU_PACKET_BLOCK),)
+    if case.call == "rtpo":                        # the packets, and the slots of the span the call finds
+        return ((len(a["off"]), RTPO_BLOCK), (want(case, plan=True)[-1]["stream_bytes"], RTPO_BLOCK))
+    if case.call == "mp4f":
+        return ((len(a["index"]), MP4_NAL_BLOCK), (len(a["au"]), MP4_AU_BLOCK))
+    if case.call == "mp4s":                        # moofs and samples (the segments: tests/test_seq_cases.py)
+        s = want(case, plan=True)[-1]
+        return ((s["nal_found"], MP4RD_BLOCK), (s["nal_count"], MP4RD_BLOCK))
+    if case.call == "stbl":                        # samples, and the entries of the longest of stsc, stts, ctts, stss
+        return ((want(case, plan=True)[-1]["nal_count"], STBL_BLOCK), (max(stbl_entries(a["rec"]).values()), STBL_BLOCK))
+    if case.call == "stblw":                       # samples, chunks, the runs of the stts
+        w = want(case, plan=True)
+        return ((w[-1]["nal_count"], STBLW_BLOCK), (w[-1]["nal_found"], STBLW_BLOCK), (stbl_entries(w[1].view(MS.STBL))["stts"], STBLW_BLOCK))
     if case.call == "a2l":
         return ((len(a["idx"]), NAL_BLOCK),)
     if case.call == "l2a":
@@ -54,6 +112,11 @@ def items(case):
     return ((len(a["index"]), NAL_BLOCK), (len(a["au"]), INS_AU_BLOCK))
 
 
+def stbl_entries(rec):
+    """the entries of stsc, stts, ctts and stss by the bytes of their payloads"""
+    return {name: max(int(rec[name][0][1]) - 8, 0) // per for name, per in (("stsc", 12), ("stts", 8), ("ctts", 8), ("stss", 4))}
+
+
 def plan_blocks(case):
     return tuple(blocks(n, per) for n, per in items(case))
 
@@ -61,6 +124,23 @@ def plan_blocks(case):
 def reference(case, plan=False):
     """the plain loop on the case's arguments (a plan looks at no capacity)"""
     a, c = case.a, ({} if plan else case.caps)
+    if case.call in ("rtp", "rtpa"):
+        return RA.pack(a["stream"], a["index"], a["nal_au"], a["n_aus"], a["pts"], a["prm"], c.get("out_cap"))
+    if case.call == "rtpu":
+        r = RU.unpack(a["data"], a["off"], a["size"], a["prm"], c.get("out_cap"), c.get("nal_cap"), c.get("au_cap"))
+        return r["out"], r["index"], r["nal_au"], r["au_ts"], r["summary"]
+    if case.call == "rtpo":
+        r = RO.order(a["data"], a["off"], a["size"], a["prm"], c.get("out_cap"))
+        return r["off"], r["size"], r["src"], r["ext"], r["summary"]
+    if case.call == "mp4f":
+        return MF.fragment(a["stream"], a["index"], a["keep"], a["nal_au"], a["au"], a["dts"], a["pts"], a["prm"], c.get("out_cap"), c.get("frag_cap"))
+    if case.call == "mp4s":                        # (moof_cap sizes the plan's scratch too, and the plan looks at it)
+        return MR.samples(a["data"], a["segs"], a["prm"], moof_cap=case.caps.get("moof_cap"), sample_cap=c.get("sample_cap"), tables=not plan)
+    if case.call == "stbl":
+        return MS.read(a["data"], a["rec"], outputs=False) if plan else MS.read(a["data"], a["rec"], sample_cap=c.get("sample_cap"))
+    if case.call == "stblw":                       # (a plan writes d_tables, and the reference gives the boxes all the same)
+        blob, rec, s = MW.call(a, **({} if plan else dict(out_cap=c["out_cap"])))
+        return (None if blob is None else np.frombuffer(blob, dtype=np.uint8)), (None if rec is None else rec.view(np.uint8).reshape(-1)), s
     if case.call == "a2l":
         return LP.to_lenpref_ref(a["s"], a["idx"], a["keep"], a["L"], a["nal_au"], a["n_aus"], c.get("out_cap"))
     if case.call == "l2a":
@@ -94,6 +174,26 @@ def needs(case):
     w = want(case, plan=True)
     s = w[-1]
     assert s["error"] == 0, (case, s)
+    if case.call in ("rtp", "rtpa"):
+        n = len(case.a["index"])
+        return dict(out_cap=s["stream_bytes"]), dict(out=s["stream_bytes"], no=(n + 1) * 8, npk=(n + 1) * 8)
+    if case.call == "rtpu":
+        nals, aus = s["nal_count"], s["reserved"][1]
+        return dict(out_cap=s["stream_bytes"], nal_cap=nals, au_cap=aus), dict(out=s["stream_bytes"], io=nals * 32, nau=nals * 4, ats=aus * 8)
+    if case.call == "rtpo":
+        kept = s["nal_count"]
+        return dict(out_cap=kept), dict(ooff=kept * 8, osize=kept * 8, src=kept * 4, ext=kept * 8)
+    if case.call == "mp4f":
+        m, frags = len(case.a["au"]), s["nal_count"]
+        return dict(out_cap=s["stream_bytes"], frag_cap=frags), dict(out=s["stream_bytes"], so=m * 8, ss=m * 8, fr=frags * MF.FRAG.itemsize)
+    if case.call == "mp4s":
+        n, m = s["nal_count"], s["nal_found"]
+        return dict(moof_cap=m, sample_cap=n), dict(so=n * 8, ss=n * 8, dts=n * 8, pts=n * 8, sfl=n * 4, fr=m * MF.FRAG.itemsize)
+    if case.call == "stbl":
+        n = s["nal_count"]
+        return dict(sample_cap=n), dict(so=n * 8, ss=n * 8, dts=n * 8, pts=n * 8, sfl=n * 4)
+    if case.call == "stblw":
+        return dict(out_cap=s["stream_bytes"]), dict(out=s["stream_bytes"], tab=MS.STBL.itemsize)
     if case.call == "a2l":
         return dict(out_cap=s["stream_bytes"]), dict(out=s["stream_bytes"], io=s["nal_count"] * 32, so=(case.a["n_aus"] + 1) * 8)
     if case.call == "l2a":
@@ -107,6 +207,8 @@ def needs(case):
 
 
 def finish(case):
+    if case.call == "mp4s":                        # the plan's moof_cap is the count of a plan without a limit
+        case.caps = dict(moof_cap=MR.samples(case.a["data"], case.a["segs"], case.a["prm"], tables=False)[-1]["nal_found"])
     case.caps, case.room = needs(case)
     return case
 
@@ -209,7 +311,135 @@ def make_ins(which, seed):
                                           first=0, count=n, flags=flags)))
 
 
-MAKERS = dict(a2l=make_a2l, l2a=make_l2a, tsd=make_tsd, tsm=make_tsm, ins=make_ins)
+# NALs of the hbs_rtp_pack cases: one plan workgroup; three and a ragged fourth, the output across three copy tiles and more;
+# between them with the other framing, another max_payload, HBS_RTP_OPEN_END and times by ts_step
+RTP = dict(small=dict(n=200, max_nal=900, times=True, prm=R.params(max_payload=300, seq=65400, ts_base=0xFFFFFF00)),
+           large=dict(n=3 * RTP_NAL_BLOCK + 57, max_nal=900, times=True, prm=R.params(max_payload=300, seq=65400, ts_base=0xFFFFFF00)),
+           odd=dict(n=RTP_NAL_BLOCK + 100, max_nal=400, times=False, prm=R.params(max_payload=100, framing=2, flags=R.OPEN_END, seq=7, ts_step=3003)))
+RTPA = dict(small=dict(n=200, max_nal=500, times=True, prm=R.params(max_payload=1188, flags=RA.AGGREGATE, seq=65400, ts_base=0xFFFFFF00)),
+            large=dict(n=3 * RTP_NAL_BLOCK + 57, max_nal=500, times=True, prm=R.params(max_payload=1188, flags=RA.AGGREGATE, seq=65400, ts_base=0xFFFFFF00)),
+            odd=dict(n=RTP_NAL_BLOCK + 100, max_nal=120, times=False,
+                     prm=R.params(max_payload=100, framing=2, flags=RA.AGGREGATE | R.OPEN_END, seq=7, ts_step=3003)))
+
+
+def make_rtp(which, seed, table=RTP, call="rtp"):
+    p = table[which]
+    rng = np.random.default_rng(seed + (300 if call == "rtp" else 400))
+    stream, index, nal_au, n_aus, pts = R.random_case(rng, p["n"], max_nal=p["max_nal"], times=p["times"])
+    return finish(Case(call, which, dict(stream=stream, index=index, nal_au=nal_au, n_aus=n_aus, pts=pts, prm=p["prm"])))
+
+
+def make_rtpa(which, seed):
+    return make_rtp(which, seed, RTPA, "rtpa")
+
+
+# packets of the hbs_rtp_unpack cases (single NALs and whole FU chains; the odd case also aggregation packets, CSRC entries,
+# header extensions, padding, 3-byte start codes and HBS_RTPU_MATCH_SSRC)
+RTPU = dict(small=dict(n=200, hi=60, aps=False, odd_headers=False, prm=RU.params()),
+            large=dict(n=3 * RTPU_PACKET_BLOCK + 57, hi=600, aps=False, odd_headers=False, prm=RU.params()),
+            odd=dict(n=RTPU_PACKET_BLOCK + 100, hi=200, aps=True, odd_headers=True, prm=RU.params(startcode_bytes=3, flags=RU.MATCH_SSRC)))
+
+
+def make_rtpu(which, seed):
+    p = RTPU[which]
+    rng = np.random.default_rng(seed + 500)
+    packets, _, _, _ = RU.random_packets(rng, p["n"], lo=4, hi=p["hi"], odd_headers=p["odd_headers"], aps=p["aps"])
+    data, off, size = RU.lay_out(packets, rng)
+    return finish(Case("rtpu", which, dict(data=data, off=off, size=size, prm=p["prm"])))
+
+
+# packets sent of the hbs_rtp_order cases, a tenth of them lost, shuffled inside a window, five arriving twice, one in twenty
+# entries another stream's; the large case wraps its sequence numbers and has two packets displaced across workgroups; the odd
+# case continues behind after_ext (its first eleven packets are late) and tells the other stream by its SSRC
+RTPO = dict(small=dict(n=200, seq0=100, flags=0), large=dict(n=4 * RTPO_BLOCK + 91, seq0=65000, flags=0),
+            odd=dict(n=400, seq0=65500, flags=RO.MATCH_SSRC | RO.AFTER))
+RTPO_LATE = 11
+
+
+def make_rtpo(which, seed):
+    p = RTPO[which]
+    rng = np.random.default_rng(seed + 600)
+    n, seq0, W = p["n"], p["seq0"], RTPO_BLOCK
+    packets = [RU.packet(RU.random_nal(rng, int(rng.integers(2, 29))), (seq0 + k) & 0xFFFF, 90 * k) for k in range(n)]
+    lose = sorted(int(x) for x in rng.choice(np.arange(RTPO_LATE + 1, n - 1), size=n // 10, replace=False))
+    arrived, _ = RO.arrive(packets, rng, window=8, duplicates=5, lose=lose, others=0.05, other_kind="ssrc" if p["flags"] & RO.MATCH_SSRC else "pt")
+    if which == "large":                           # tests/test_gpu_rtp_order.py::test_displacement_across_workgroups
+        arrived.insert(2 * W + 5, arrived.pop(5))
+        arrived.insert(7, arrived.pop(3 * W + 9))
+    data, off, size = RU.lay_out(arrived, rng)
+    if p["flags"] & RO.AFTER:
+        after = RO.START + 2 * 65536 + seq0 + RTPO_LATE - 1
+        prm = RO.params(flags=p["flags"], after_ext=after, max_span=n - RTPO_LATE)
+    else:                                          # one workgroup of slots; the span and part of a ragged workgroup more
+        prm = RO.params(max_span=W if which == "small" else n + 37)
+    return finish(Case("rtpo", which, dict(data=data, off=off, size=size, prm=prm)))
+
+
+# AUs of the hbs_mp4_fragment cases (one to three or four NALs each): one workgroup of NALs and of AUs; four of AUs and more of
+# NALs, both ragged, the output across three copy tiles and more; between them with 2-byte lengths, fragments of at most seven
+# samples instead of a cut at every IRAP, and the caller's times
+MP4F = dict(small=dict(aus=80, per_au=3, times=False, prm=MF.params(length_size=4, flags=MF.CUT_AT_IRAP, track_id=3, sequence=40, base_time=1 << 33)),
+            large=dict(aus=3 * MP4_AU_BLOCK + 57, per_au=4, times=False,
+                       prm=MF.params(length_size=4, flags=MF.CUT_AT_IRAP, track_id=3, sequence=40, base_time=1 << 33)),
+            odd=dict(aus=MP4_AU_BLOCK + 100, per_au=2, times=True, prm=MF.params(length_size=2, max_samples=7, track_id=5, sequence=(1 << 32) - 2)))
+
+
+def make_mp4f(which, seed):
+    p = MP4F[which]
+    rng = np.random.default_rng(seed + 700)
+    stream, index, keep, nal_au, au, dts, pts = MF.random_case(rng, p["aus"], max_nal=300, max_nals_per_au=p["per_au"], times=p["times"], irap_every=30)
+    return finish(Case("mp4f", which, dict(stream=stream, index=index, keep=keep, nal_au=nal_au, au=au, dts=dts, pts=pts, prm=p["prm"])))
+
+
+# moofs of the hbs_mp4_samples cases, one to three samples in one trun each (the last moof: three samples, their sizes in the
+# entries, a data_offset); the odd case is a table of segments of two moofs each, records of 24 bytes, other trex defaults
+MP4S = dict(small=dict(moofs=100, per_seg=None, stride=16, prm=MR.read_params(track_id=1, trex_duration=7, trex_size=3, trex_flags=0x01010000)),
+            large=dict(moofs=3 * MP4RD_BLOCK + 57, per_seg=None, stride=16,
+                       prm=MR.read_params(track_id=1, trex_duration=7, trex_size=3, trex_flags=0x01010000)),
+            odd=dict(moofs=MP4RD_BLOCK + 100, per_seg=2, stride=24, prm=MR.read_params(track_id=2, trex_duration=1000, trex_size=9)))
+
+
+def make_mp4s(which, seed):
+    p = MP4S[which]
+    rng = np.random.default_rng(seed + 800)
+    shapes = [[int(c)] for c in rng.integers(1, 4, size=p["moofs"] - 1)] + [[3]]
+    tflags = [None] * (p["moofs"] - 1) + [[0x201]]
+    buf, _, frags = moofs_of(rng, p["prm"], shapes, tflags, per_seg=p["per_seg"])
+    segs = None
+    if p["per_seg"]:                               # tests/test_gpu_mp4_read.py::test_moof_counts_around_a_workgroup
+        cut = [int(f["out_off"]) for f in frags[::p["per_seg"]]] + [len(buf)]
+        segs = [(a, b - a) for a, b in zip(cut, cut[1:])]
+    moof_off = [int(f["out_off"]) for f in frags]
+    return finish(Case("mp4s", which, dict(data=np.frombuffer(buf, dtype=np.uint8), segs=segs, stride=p["stride"], prm=p["prm"], moof_off=moof_off)))
+
+
+# samples of the hbs_mp4_stbl_samples cases; the odd case has a co64, one sample size in the stsz and no stss
+STBL = dict(small=dict(n=200, co64=False, constant=None, sync=True), large=dict(n=5000, co64=False, constant=None, sync=True),
+            odd=dict(n=2200, co64=True, constant=33, sync=False))
+
+
+def make_stbl(which, seed):
+    p = STBL[which]
+    t = stbl_track(np.random.default_rng(seed + 900), p["n"], constant=p["constant"])
+    if not p["sync"]:
+        t["sync"] = None
+    buf, rec = stbl_case(t, co64=p["co64"], constant=p["constant"], first=(1 << 33) + 5 if p["co64"] else 0, lead=5)
+    return finish(Case("stbl", which, dict(data=np.frombuffer(buf, dtype=np.uint8), rec=rec, t=t, co64=p["co64"], constant=p["constant"])))
+
+
+# samples of the hbs_mp4_stbl_write cases; the odd case writes a co64 for offsets above 4 GiB and cuts its chunks every three samples
+STBLW = dict(small=dict(n=200, params=dict()), large=dict(n=2600, params=dict()),
+             odd=dict(n=900, params=dict(co64=True, max_chunk_samples=3, data_offset=(1 << 33) + 4)))
+
+
+def make_stblw(which, seed):
+    p = STBLW[which]
+    t, _, dur = MW.random_tables(np.random.default_rng(seed + 1000), p["n"])
+    return finish(Case("stblw", which, MW.case("%s %d" % (which, seed), t, sample_duration=dur, **p["params"])))
+
+
+MAKERS = dict(a2l=make_a2l, l2a=make_l2a, tsd=make_tsd, tsm=make_tsm, ins=make_ins, rtp=make_rtp, rtpa=make_rtpa, rtpu=make_rtpu,
+              rtpo=make_rtpo, mp4f=make_mp4f, mp4s=make_mp4s, stbl=make_stbl, stblw=make_stblw)
 PACKET_CALLS = ("tsd", "tsm")                        # their cases take a packet size
 _cases = {}
 
@@ -231,13 +461,79 @@ def demux_of(mux):
     return _cases[key]
 
 
+def order_of(pack):
+    """hbs_rtp_order of the packets the hbs_rtp_pack case puts out (by the reference), their table shuffled inside a window of
+    eight on the host; max_span is the packets' number"""
+    key = (id(pack), "order")
+    if key not in _cases:
+        out, nal_off, nal_packet, _ = want(pack)
+        prm = pack.a["prm"]
+        at = RA.packet_offsets(nal_off, nal_packet, prm)
+        off, size = at[:-1] + np.uint64(prm["framing"]), np.diff(at) - np.uint64(prm["framing"])
+        seen = RO.arrival_order(len(off), 8, np.random.default_rng(len(off)))
+        _cases[key] = finish(Case("rtpo", "of the %s %s" % (pack.name, pack.call), dict(data=out, off=off[seen], size=size[seen],
+                                                                                         prm=RO.params(flags=RO.MATCH_SSRC, max_span=len(off)))))
+    return _cases[key]
+
+
+def unpack_of(order):
+    """hbs_rtp_unpack of the table the hbs_rtp_order case puts out (by the reference)"""
+    key = (id(order), "unpack")
+    if key not in _cases:
+        off, size, _, _, _ = want(order)
+        _cases[key] = finish(Case("rtpu", order.name, dict(data=order.a["data"], off=off, size=size, prm=RU.params(flags=RU.MATCH_SSRC))))
+    return _cases[key]
+
+
+def samples_of(frag):
+    """hbs_mp4_samples of what the hbs_mp4_fragment case puts out (by the reference), as one segment"""
+    key = (id(frag), "samples")
+    if key not in _cases:
+        out, _, _, frags, _ = want(frag)
+        a = dict(data=out, segs=None, stride=16, prm=MR.read_params(track_id=frag.a["prm"]["track_id"]), moof_off=[int(x) for x in frags["out_off"]])
+        _cases[key] = finish(Case("mp4s", "of the %s fragments" % frag.name, a))
+    return _cases[key]
+
+
+STBL_FILE_BYTES = 1 << 40                          # of the file the boxes of an hbs_mp4_stbl_write case describe: above every sample
+
+
+def stbl_of(write):
+    """hbs_mp4_stbl_samples of the boxes the hbs_mp4_stbl_write case puts out (by the reference), by the record it gives"""
+    key = (id(write), "stbl")
+    if key not in _cases:
+        blob, rec, _ = want(write)
+        rec = rec.view(MS.STBL).copy()
+        rec["file_bytes"] = STBL_FILE_BYTES
+        _cases[key] = finish(Case("stbl", "of the %s boxes" % write.name, dict(data=blob, rec=rec)))
+    return _cases[key]
+
+
 def empty(call, B=188):
     """no NALs, samples, packets or AUs"""
     key = (call, "empty", B if call in PACKET_CALLS else None)
     if key in _cases:
         return _cases[key]
-    z8 = np.zeros(0, dtype=np.uint8)
-    if call == "a2l":
+    z8, z64 = np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint64)
+    if call in ("rtp", "rtpa"):
+        a = dict(stream=z8, index=np.zeros(0, dtype=R.NAL_ENTRY), nal_au=np.zeros(0, dtype=np.uint32), n_aus=0, pts=z64,
+                 prm=(RTP if call == "rtp" else RTPA)["small"]["prm"])
+    elif call == "rtpu":
+        a = dict(data=z8, off=z64, size=z64, prm=RU.params())
+    elif call == "rtpo":
+        a = dict(data=z8, off=z64, size=z64, prm=RO.params(max_span=RTPO_BLOCK))
+    elif call == "mp4f":
+        a = dict(stream=z8, index=np.zeros(0, dtype=MF.NAL_ENTRY), keep=None, nal_au=np.zeros(0, dtype=np.uint32), au=np.zeros(0, dtype=MF.ACCESS_UNIT),
+                 dts=None, pts=None, prm=MP4F["small"]["prm"])
+    elif call == "mp4s":                           # an empty buffer as one segment
+        a = dict(data=z8, segs=None, stride=16, prm=MP4S["small"]["prm"], moof_off=[])
+    elif call == "stbl":                           # tests/test_gpu_mp4_stbl.py::test_sample_counts_around_a_workgroup: boxes of no entry
+        t = stbl_track(np.random.default_rng(0), 0)
+        buf, rec = stbl_case(t, lead=5)
+        a = dict(data=np.frombuffer(buf, dtype=np.uint8), rec=rec, t=t, co64=False, constant=None)
+    elif call == "stblw":
+        a = MW.case("empty", MW.random_tables(np.random.default_rng(0), 0)[0])
+    elif call == "a2l":
         a = dict(s=z8, idx=np.zeros(0, dtype=F.NAL_ENTRY), keep=None, L=4, nal_au=np.zeros(0, dtype=np.uint32), n_aus=0)
     elif call == "l2a":
         a = dict(data=z8, off=np.zeros(0, dtype=np.uint64), size=np.zeros(0, dtype=np.uint64), L=4, sc=4)
@@ -257,17 +553,85 @@ def empty(call, B=188):
 
 def edited_entry(good, late):
     """the entry a malformed variant edits: in the first plan workgroup, or in the last one (of the AU side for hbs_au_insert)"""
-    n, per = items(good)[-1]
+    n, per = edited_table(good, late)
     if not late:
         return min(5, n - 1)
     return max(n - 3, (blocks(n, per) - 1) * per)
+
+
+def edited_table(good, late):
+    """(items, items per workgroup) of the table a malformed variant edits: the NALs of hbs_rtp_pack and hbs_mp4_fragment, the
+    packets of hbs_rtp_unpack and hbs_rtp_order, a moof (early) or a sample (late) of hbs_mp4_samples, a sample (early) or an
+    stsc entry (late) of hbs_mp4_stbl_samples, a sample of hbs_mp4_stbl_write; of the five older calls the last side"""
+    if good.call == "mp4s":
+        return items(good)[1 if late else 0]
+    if good.call == "stbl" and late:
+        return stbl_entries(good.a["rec"])["stsc"], STBL_BLOCK
+    return items(good)[0 if good.call in CALLS2 else -1]
 
 
 def malformed(good, late):
     """one entry edited as the calls' own tests edit theirs"""
     a = dict(good.a)
     at = edited_entry(good, late)
-    if good.call == "a2l":                         # test_gpu_lenpref.py: an inconsistent index
+    word, value, in_plan = 0, None, True
+    if good.call == "mp4f":                        # test_gpu_mp4.py::test_nal_errors: "start_gt_end", "overlap"
+        index = a["index"].copy()
+        index["start"][at] = index["end"][at - 1] - 1 if late else index["end"][at] + 1
+        a["index"] = index
+    elif good.call == "mp4s":                      # test_gpu_mp4_read.py::test_errors_at_the_stated_segment_moof_and_sample
+        data = a["data"].copy()
+        raw = data.tobytes()
+        if late:                                   # a negative data begin in the last moof: a sample error at its first sample
+            at, word = summary_of(good)["nal_count"] - 3, 2
+            i = raw.index(b"trun", a["moof_off"][-1])
+            data[i + 12:i + 16] = np.frombuffer((-(1 << 31)).to_bytes(4, "big", signed=True), dtype=np.uint8)
+        else:                                      # no tfdt in moof `at`: a moof error
+            word = 1
+            i = raw.index(b"tfdt", a["moof_off"][at])
+            assert i < a["moof_off"][at + 1]
+            data[i:i + 4] = np.frombuffer(b"free", dtype=np.uint8)
+        a["data"] = data
+    elif good.call == "stbl":                      # test_gpu_mp4_stbl.py: a sample behind file_bytes; "a broken entry far down a table"
+        rec = a["rec"].copy()
+        if late:                                   # entry `at` of the stsc repeats the first_chunk of the entry in front: box 3
+            assert at >= 1
+            data = a["data"].copy()
+            o = int(rec["stsc"][0][0]) + 8 + 12 * at
+            data[o:o + 4] = data[o - 12:o - 8]
+            a["data"], value = data, 3
+        else:                                      # (a plan does not look for sample errors)
+            off, size = want(good)[0], want(good)[1]
+            at = int(np.flatnonzero(size[at:] > 0)[0]) + at
+            rec["file_bytes"] = int(off[at]) + int(size[at]) - 1
+            word, in_plan = 2, False
+        a["rec"] = rec
+    elif good.call == "stblw":                     # _mp4_stbl_write_ref.py::error_cases: "a size above 2^32 - 1", "a pts of 2^62"
+        t = {k: (None if v is None else list(v)) for k, v in a["t"].items()}
+        if late:
+            t["pts"][at] = 1 << 62
+        else:
+            t["size"][at] = 1 << 32
+        a["t"], word = t, 2
+    elif good.call in ("rtp", "rtpa"):               # test_gpu_rtp.py::test_malformed_nals: "one byte", "type 48"
+        if late:
+            stream = a["stream"].copy()
+            stream[int(a["index"]["start"][at])] = 48 << 1
+            a["stream"] = stream
+        else:
+            index = a["index"].copy()
+            index["end"][at] = index["start"][at] + 1
+            a["index"] = index
+    elif good.call in ("rtpu", "rtpo"):            # test_gpu_rtp_unpack.py, test_gpu_rtp_order.py: "version 1", a packet that leaves the buffer
+        if late:
+            data = a["data"].copy()
+            data[int(a["off"][at])] = 0x40
+            a["data"] = data
+        else:
+            size = a["size"].copy()
+            size[at] = len(a["data"]) - int(a["off"][at]) + 1
+            a["size"] = size
+    elif good.call == "a2l":                       # test_gpu_lenpref.py: an inconsistent index
         idx = a["idx"].copy()
         if late:
             idx["start"][at] = idx["end"][at - 1] - 1
@@ -308,20 +672,51 @@ def malformed(good, late):
             a["au"] = au
     v = Case(good.call, good.name + (" bad-late" if late else " bad-early"), a, bad=at)
     v.caps, v.room = dict(good.caps), dict(good.room)
+    if good.call in CALLS2:
+        v.named, v.in_plan, v.among = (word, at + 1 if value is None else value), in_plan, edited_table(good, late)
     return v
 
 
-def short(good):
-    """the good case with room for one byte less than it puts out"""
-    v = Case(good.call, good.name + " short", good.a)
-    v.caps, v.room = dict(good.caps, out_cap=good.caps["out_cap"] - 1), dict(good.room)
+def short(good, what="short"):
+    """the good case with room for one byte, or one entry, less than it puts out: in out_cap, or in the capacity `what` names"""
+    v = Case(good.call, good.name + " " + what.replace("_", " "), good.a)
+    v.caps, v.room = dict(good.caps), dict(good.room)
+    if what == "short_span":
+        v.a = dict(good.a, prm=dict(good.a["prm"], max_span=summary_of(good)["stream_bytes"] - 1))
+    else:
+        v.caps[SHORT_CAP[what]] -= 1
+    return v
+
+
+def roomy(good):
+    """the good case with every capacity the caller gives well above the need: ROOM_BYTES more in a byte capacity, ROOM_ITEMS more
+    in a counted one, a max_span of more than twice the large case's; the outputs are as large as the capacities"""
+    v = Case(good.call, good.name + " roomy", good.a)
+    per = dict(rtp=dict(out_cap=("out", 1)), rtpa=dict(out_cap=("out", 1)),
+               rtpu=dict(out_cap=("out", 1), nal_cap=("io", 32, "nau", 4), au_cap=("ats", 8)),
+               rtpo=dict(out_cap=("ooff", 8, "osize", 8, "src", 4, "ext", 8)),
+               mp4f=dict(out_cap=("out", 1), frag_cap=("fr", MF.FRAG.itemsize)),
+               mp4s=dict(moof_cap=("fr", MF.FRAG.itemsize), sample_cap=("so", 8, "ss", 8, "dts", 8, "pts", 8, "sfl", 4)),
+               stbl=dict(sample_cap=("so", 8, "ss", 8, "dts", 8, "pts", 8, "sfl", 4)), stblw=dict(out_cap=("out", 1)))[good.call]
+    v.caps, v.room = dict(good.caps), dict(good.room)
+    for cap, outs in per.items():
+        more = ROOM_BYTES if outs[1] == 1 else ROOM_ITEMS
+        v.caps[cap] += more
+        for name, width in zip(outs[::2], outs[1::2]):
+            v.room[name] += more * width
+            v.spare[name] = more * width
+    if good.call == "rtpo":
+        v.a = dict(good.a, prm=dict(good.a["prm"], max_span=2 * case("rtpo", "large").a["prm"]["max_span"] + RTPO_BLOCK + 1))
     return v
 
 
 def variant(good, what):
     key = (id(good), what)
     if key not in _cases:
-        _cases[key] = short(good) if what == "short" else malformed(good, what == "bad_late")
+        if what == "roomy":
+            _cases[key] = roomy(good)
+        else:
+            _cases[key] = short(good, what) if what.startswith("short") else malformed(good, what == "bad_late")
     return _cases[key]
 
 
@@ -329,7 +724,21 @@ def names_the_entry(call):
     """does the call's summary name the lowest entry in error?  The header gives reserved[0] = 1 + that entry to
     hbs_lenpref_to_annexb, hbs_ts_demux and hbs_ts_mux; hbs_annexb_to_lenpref leaves it 0, and hbs_au_insert's reserved[]
     counts what it inserted, so both are 0 under HBS_E_ARG."""
-    return call in ("l2a", "tsd", "tsm")
+    if call in RTP_CALLS:                          # "reserved[0] = 1 + the lowest offending NAL", "... faulty packet", "... faulty entry"
+        return True
+    # hbs_mp4_fragment: reserved[0] = 1 + the lowest offending NAL (and reserved[1] the AU); hbs_mp4_samples: reserved[0] the segment,
+    # reserved[1] the moof, reserved[2] the sample; the two sample table calls name a box in reserved[0] and the sample in
+    # reserved[2].  A malformed variant of these calls carries the word and the value the header promises it (Case.named)
+    return call in ("l2a", "tsd", "tsm", "mp4f", "mp4s")
+
+
+def writes_nothing_when_refused(call):
+    """does the header promise that a call that reports an error writes nothing but the summary?  hbs_rtp_pack: "On either error
+    nothing is written but the summary"; hbs_rtp_unpack: "On either error nothing but the summary is written"; hbs_rtp_order: "On
+    any error nothing but the summary is written"; hbs_mp4_fragment and hbs_mp4_samples: "On any error nothing but the summary is
+    written"; hbs_mp4_stbl_samples: "on any error only the summary is written"; hbs_mp4_stbl_write: "On any error nothing but the
+    summary is written"."""
+    return call in CALLS2
 
 
 def sequence(call, seed=1, B=188):
@@ -337,3 +746,13 @@ def sequence(call, seed=1, B=188):
     small, large, odd = (case(call, w, seed, B) for w in SIZES)
     return [(large, False), (small, False), (variant(large, "bad_late"), False), (small, False), (variant(small, "bad_early"), False),
             (odd, False), (empty(call, B), False), (variant(large, "short"), False), (large, True), (large, False)]
+
+
+def sequence2(call, seed=1):
+    """the steps of a CALLS2 sequence on one context: the ten steps, a roomy call behind the first large one and behind the short
+    ones, and a step for each capacity a byte or an entry short -> [(case, plan only?)]"""
+    small, large, odd = (case(call, w, seed) for w in SIZES)
+    steps = [(large, False), (variant(large, "roomy"), False), (small, False), (variant(large, "bad_late"), False), (small, False),
+             (variant(small, "bad_early"), False), (odd, False), (empty(call), False)]
+    steps += [(variant(large, what), False) for what in SHORTS[call]]
+    return steps + [(variant(small, "roomy"), False), (large, True), (large, False)]

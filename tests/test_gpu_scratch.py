@@ -2,7 +2,7 @@
 call's arguments): what a context holds after one call of each kind, to the byte; a context whose buffers all grow under it
 answers as a fresh one does; every timed call takes its slot of the timing ring.  The five framing and transport calls
 (tests/test_gpu_sequences.py holds them against their reference loops) are in the last two, and their scratch is held by relations
-between readings."""
+between readings; so is that of the RTP and MP4 calls (tests/test_gpu_sequences_rtp_mp4.py)."""
 import ctypes as C
 
 import numpy as np
@@ -310,6 +310,19 @@ def test_scratch_relations_of_the_framing_calls(call):
     """device_bytes() after the five newer calls, as relations between readings (see SCRATCH_BYTES): a plan in front of a run
     adds nothing to what the run alone holds; a small call, or the same call again, leaves it as it is; a context that only
     ever sees the small case holds strictly less.  Every call is held against the reference loop on the way."""
+    scratch_relations(call)
+
+
+@pytest.mark.parametrize("call", S.CALLS2)
+def test_scratch_relations_of_the_rtp_and_mp4_calls(call):
+    """the same relations for the calls whose layout functions take capacities of the caller as well (lay_rtp, lay_rtpu, lay_rtpo,
+    lay_mp4, lay_mp4rd, lay_mp4stbl, lay_mp4stblw): they follow from those functions, each of which carves at least as much
+    for a run as for a plan of the same case, and strictly more for the large case's counts and capacities than for the small
+    one's"""
+    scratch_relations(call)
+
+
+def scratch_relations(call):
     small, large = S.case(call, "small"), S.case(call, "large")
     planned, alone, little = new_ctx(), new_ctx(), new_ctx()
     try:

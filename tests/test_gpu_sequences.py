@@ -3,14 +3,26 @@ of the context that nothing clears between calls (hbs_capi.hip: carve, grow), so
 written it is the previous call's, in that call's layout.  Here calls of different sizes, layouts and outcomes follow each other
 on one context, and every one of them is held, byte for byte and field for field, against the plain loops of tests/_*_ref.py:
 never against a fresh context, which could be wrong in the same way.  The cases are tests/_seq_cases.py's; tests/test_seq_cases.py
-holds on the CPU that they are what the sequences need."""
+holds on the CPU that they are what the sequences need.  alloc, launch, verify and step also serve the RTP and MP4 calls, whose
+sequences are in tests/test_gpu_sequences_rtp_mp4.py."""
 import numpy as np
 import pytest
 
+from tests import _mp4_ref as MF
+from tests import _rtp_order_ref as RO
+from tests import _rtp_ref as R
+from tests import _rtp_unpack_ref as RU
 from tests import _seq_cases as S
 from tests import _tsmux_ref as TSM
 from tests import test_gpu_auins as AI
 from tests import test_gpu_lenpref as LP
+from tests import test_gpu_mp4 as TF
+from tests import test_gpu_mp4_read as TQ
+from tests import test_gpu_mp4_stbl as TB
+from tests import test_gpu_mp4_stbl_write as TW
+from tests import test_gpu_rtp as TR
+from tests import test_gpu_rtp_order as TO
+from tests import test_gpu_rtp_unpack as TU
 from tests import test_gpu_ts as TS
 from tests import test_gpu_tsmux as TM
 
@@ -20,8 +32,14 @@ PAD = 4096
 PACKET_SIZES = (188, 192, 204)
 # what a run writes: (buffer, its place in the reference's result)
 OUTPUTS = dict(a2l=(("out", 0), ("io", 1), ("so", 2)), l2a=(("out", 0), ("so", 1)), tsd=(("out", 0), ("pes", 1)), tsm=(("out", 0), ("ap", 1)),
-               ins=(("out", 0), ("io", 1), ("src", 2), ("nau", 3), ("auo", 4)))
+               ins=(("out", 0), ("io", 1), ("src", 2), ("nau", 3), ("auo", 4)),
+               rtp=(("out", 0), ("no", 1), ("npk", 2)), rtpa=(("out", 0), ("no", 1), ("npk", 2)), rtpu=(("out", 0), ("io", 1), ("nau", 2), ("ats", 3)),
+               rtpo=(("ooff", 0), ("osize", 1), ("src", 2), ("ext", 3)), mp4f=(("out", 0), ("so", 1), ("ss", 2), ("fr", 3)),
+               mp4s=(("so", 0), ("ss", 1), ("dts", 2), ("pts", 3), ("sfl", 4), ("fr", 5)), stbl=(("so", 0), ("ss", 1), ("dts", 2), ("pts", 3), ("sfl", 4)),
+               stblw=(("out", 0), ("tab", 1)))
 PER_NAL_TABLES = ("io", "src", "nau")                # of hbs_au_insert: d_index_out, d_nal_src, d_nal_au_out
+PLAN_WRITES = {"stblw": ("tab",)}                    # "d_out == NULL: plan only -- ... the summary and d_tables are written"
+SUMMARY_MATCHES = dict(a2l=LP, l2a=LP, tsd=TS, tsm=TM, ins=AI, rtp=TR, rtpa=TR, rtpu=TU, rtpo=TO, mp4f=TF, mp4s=TQ, stbl=TB, stblw=TW)
 
 
 def new_ctx():
@@ -44,13 +62,33 @@ def filled(n, byte):
     return torch.full((n,), byte, dtype=torch.uint8, device="cuda")
 
 
-def alloc(c, tables=True, ts=None):
+def opt(a):
+    return dev(a) if a is not None else None
+
+
+def alloc(c, tables=True, ts=None, given=None):
     """the case's inputs on the device, outputs of exactly c.room bytes with canaries behind them, a summary full of 0xEE.
-    tables False: hbs_au_insert without its per-NAL tables; ts: a device tensor that holds hbs_ts_demux's input already"""
+    tables False: hbs_au_insert without its per-NAL tables; ts: a device tensor that holds hbs_ts_demux's input already; given:
+    inputs that lie on the device already, by their names here (for hbs_mp4_stbl_samples also "rec", the host record)"""
     from hevcbitstream_amd.api import SUMMARY
     a = c.a
     b = dict(summary=filled(SUMMARY.itemsize, 0xEE))
-    if c.call == "a2l":
+    held = lambda name, make: given[name] if given and name in given else make()          # noqa: E731
+    if c.call in ("rtp", "rtpa"):
+        b.update(stream=dev(a["stream"]), index=dev(a["index"]), nal_au=opt(a["nal_au"]), pts=opt(a["pts"]), prm=R.params_record(a["prm"]))
+    elif c.call in ("rtpu", "rtpo"):
+        b.update(data=held("data", lambda: dev(a["data"])), off=held("off", lambda: dev(a["off"])), size=held("size", lambda: dev(a["size"])),
+                 prm=(RU if c.call == "rtpu" else RO).params_record(a["prm"]))
+    elif c.call == "mp4f":
+        b.update(stream=dev(a["stream"]), index=dev(a["index"]), keep=opt(a["keep"]), nal_au=dev(a["nal_au"]), au=dev(a["au"]), dts=opt(a["dts"]),
+                 pts=opt(a["pts"]), prm=MF.params_record(a["prm"]))
+    elif c.call == "mp4s":
+        b.update(data=held("data", lambda: dev(a["data"])), seg=None if a["segs"] is None else TQ.seg_table(a["segs"], a["stride"]))
+    elif c.call == "stbl":
+        b.update(data=held("data", lambda: dev(a["data"])), rec=held("rec", lambda: a["rec"]))
+    elif c.call == "stblw":
+        b.update({"in_" + k: v for k, v in TW.upload(a).items()})
+    elif c.call == "a2l":
         b.update(s=dev(a["s"]), idx=dev(a["idx"]), keep=dev(a["keep"]) if a["keep"] is not None else None, nal_au=dev(a["nal_au"]))
     elif c.call == "l2a":
         b.update(data=dev(a["data"]), off=dev(a["off"]), size=dev(a["size"]))
@@ -69,6 +107,31 @@ def launch(ctx, c, b, plan=False):
     """one call on the current torch stream -> its return code"""
     a, caps = c.a, c.caps
     o = {name: None if plan else b[name] for name, _ in OUTPUTS[c.call]}
+    cap = lambda name: 0 if plan else caps[name]          # noqa: E731
+    if c.call in ("rtp", "rtpa"):
+        return ctx.rtp_pack_async(b["stream"], len(a["stream"]), b["index"], len(a["index"]), b["nal_au"], a["n_aus"], b["pts"], b["prm"], o["out"],
+                                  o["no"], o["npk"], b["summary"], out_cap=cap("out_cap"))
+    if c.call == "rtpu":
+        return ctx.rtp_unpack_async(b["data"], len(a["data"]), b["off"], b["size"], len(a["off"]), b["prm"], o["out"], o["io"], o["nau"], o["ats"],
+                                    b["summary"], out_cap=cap("out_cap"), nal_cap=cap("nal_cap"), au_cap=cap("au_cap"))
+    if c.call == "rtpo":
+        return ctx.rtp_order_async(b["data"], len(a["data"]), b["off"], b["size"], len(a["off"]), b["prm"], o["ooff"], o["osize"], o["src"], o["ext"],
+                                   b["summary"], out_cap=cap("out_cap"))
+    if c.call == "mp4f":
+        return ctx.mp4_fragment_async(b["stream"], len(a["stream"]), b["index"], len(a["index"]), b["nal_au"], b["au"], len(a["au"]), b["prm"], o["out"],
+                                      b["summary"], keep=b["keep"], dts=b["dts"], pts=b["pts"], sample_off=o["so"], sample_size=o["ss"], frag=o["fr"],
+                                      frag_cap=cap("frag_cap"), out_cap=cap("out_cap"))
+    if c.call == "mp4s":                                  # (moof_cap sizes the plan's scratch as well)
+        import hevcbitstream_amd as hbs
+        return ctx.mp4_samples_async(b["data"], len(a["data"]), hbs.mp4_read_params(**a["prm"]), b["summary"], seg=b["seg"], seg_stride=a["stride"],
+                                     n_segs=0 if a["segs"] is None else len(a["segs"]), moof_cap=caps["moof_cap"], sample_cap=cap("sample_cap"),
+                                     sample_off=o["so"], sample_size=o["ss"], dts=o["dts"], pts=o["pts"], sample_flags=o["sfl"], frag=o["fr"])
+    if c.call == "stbl":
+        return ctx.mp4_stbl_samples_async(b["data"], len(a["data"]), b["rec"], b["summary"], sample_cap=cap("sample_cap"), sample_off=o["so"],
+                                          sample_size=o["ss"], dts=o["dts"], pts=o["pts"], sample_flags=o["sfl"])
+    if c.call == "stblw":                                 # (a plan writes d_tables)
+        return ctx.mp4_stbl_write_async(b["in_sample_off"], b["in_sample_size"], len(a["t"]["size"]), TW.params_of(a), b["summary"], dts=b["in_dts"],
+                                        pts=b["in_pts"], sample_flags=b["in_sample_flags"], out=o["out"], out_cap=cap("out_cap"), tables=b["tab"])
     out_cap = 0 if plan else caps["out_cap"]
     if c.call == "a2l":
         return ctx.annexb_to_lenpref_async(b["s"], len(a["s"]), b["idx"], len(a["idx"]), o["out"], o["io"], b["summary"], keep=b["keep"],
@@ -94,30 +157,37 @@ def verify(ctx, c, b, plan=False):
     s = ctx.read_summary(b["summary"])
     if c.call == "a2l" and ws["error"] == S.E_ARG:          # the header leaves the sizes open for HBS_E_ARG
         ws = {k: v for k, v in ws.items() if k not in ("nal_count", "rbsp_bytes", "stream_bytes")}
-    dict(a2l=LP, l2a=LP, tsd=TS, tsm=TM, ins=AI)[c.call].summary_matches(s, ws)
+    SUMMARY_MATCHES[c.call].summary_matches(s, ws)
     assert int(s["reserved"][0]) == S.reserved0(ws), (s, ws)
-    if c.bad is not None:                                   # this call's own entry plus one, where the call names it
+    if c.named is not None:                                 # the word the header gives this fault, where this kind of call looks for it
+        word, value = c.named
+        if c.in_plan or not plan:
+            assert int(s["error"]) == S.E_ARG and int(s["reserved"][word]) == value, (c, s)
+        else:
+            assert int(s["error"]) == 0, (c, s)
+    elif c.bad is not None:                                 # this call's own entry plus one, where the call names it
         assert int(s["error"]) == S.E_ARG and int(s["reserved"][0]) == (c.bad + 1 if S.names_the_entry(c.call) else 0), (c, s)
+    refused_writes_nothing = c.call in S.CALLS or S.writes_nothing_when_refused(c.call)          # (the header says so for every call here)
     for name, place in OUTPUTS[c.call]:
         if b[name] is None:
             continue
         g = b[name].cpu().numpy()
-        if plan or ws["error"]:
+        if (ws["error"] and refused_writes_nothing) or (plan and name not in PLAN_WRITES.get(c.call, ())):
             assert (g == CAN).all(), "%s written by %s" % (name, "a plan" if plan else "a call that reports error %d" % ws["error"])
             continue
         x = np.ascontiguousarray(w[place])
         item, want_bytes = x.itemsize, x.view(np.uint8).reshape(-1)
-        assert len(want_bytes) == c.room[name], (name, len(want_bytes), c.room[name])
+        assert len(want_bytes) == c.room[name] - c.spare.get(name, 0), (name, len(want_bytes), c.room[name], c.spare)
         bad = np.flatnonzero(g[: len(want_bytes)] != want_bytes)
         assert len(bad) == 0, "%s differs at entry %d (byte %d; %d bytes of %d differ)" % (name, bad[0] // item, bad[0], len(bad), len(want_bytes))
         assert (g[len(want_bytes):] == CAN).all(), "stored behind " + name
     return s
 
 
-def step(ctx, c, plan=False, tables=True, ts=None):
-    """one real call of the case into canary-backed outputs of exactly the needed capacity, held against the reference
+def step(ctx, c, plan=False, tables=True, ts=None, given=None):
+    """one real call of the case into canary-backed outputs of exactly the case's capacities, held against the reference
     -> the device buffers"""
-    b = alloc(c, tables, ts)
+    b = alloc(c, tables, ts, given)
     rc = launch(ctx, c, b, plan)
     assert rc == 0, (c, rc)
     verify(ctx, c, b, plan)
