@@ -28,6 +28,10 @@ ACCESS_UNIT = np.dtype([("first_nal", "<u8"), ("unit_begin", "<u8"), ("unit_end"
 AU_CARRY = np.dtype([("flags", "<u4"), ("anchor_poc_lsb", "<i4"), ("anchor_poc_msb", "<i4"), ("reserved", "<u4")])
 AU_IRAP, AU_IDR, AU_CVS_START, AU_ANCHOR, AU_NO_PICTURE, AU_DAMAGED, AU_PARAM_SETS, AU_END_OF_SEQ = 1, 2, 4, 8, 16, 32, 64, 128
 AUKEEP_PARAM_SETS = 1
+# layout of hbs_au_times_params, the flags and the span limit of hbs_au_times
+AU_TIMES_PARAMS = np.dtype([("flags", "<u4"), ("tick", "<u4"), ("base_time", "<u8"), ("delay", "<u4"), ("reserved", "<u4", (3,))])
+AUT_MAX_SPAN = 1024
+AUT_DELAY_GIVEN, AUT_WRAP33 = 1, 2
 # flags of hbs_au_insert
 AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST = 1, 2, 4
 # layout of hbs_ts_pes / hbs_ts_packet, the packet classes and the flags of hbs_ts_demux
@@ -109,7 +113,7 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_ctx_set_sequential_parse", "hbs_ctx_set_emit_path", "hbs_parse_extended",
            "hbs_comm_unique_id", "hbs_comm_create", "hbs_comm_adopt", "hbs_comm_destroy", "hbs_comm_rank", "hbs_comm_world", "hbs_comm_reserve_hint", "hbs_parse_headers_compact", "hbs_parse_materialize", "hbs_index_parse_compact", "hbs_gather_parts", "hbs_index_parse", "hbs_ctx_reserve_workgroups",
            "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
-           "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset",
+           "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset", "hbs_au_times",
            "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb",
            "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
@@ -278,6 +282,8 @@ def load_library():
     lib.hbs_rtp_frames_host.restype = C.c_uint64
     lib.hbs_rtp_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.hbs_au_times.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hbs_au_times.restype = C.c_int
     lib.hbs_mp4_fragment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_void_p]
@@ -429,6 +435,14 @@ def rtp_order_params(payload_type=96, flags=0, ssrc=0, max_span=1 << 20, after_e
     """an hbs_rtp_order_params record (ndarray[RTP_ORDER_PARAMS] of one, host memory)"""
     p = np.zeros(1, dtype=RTP_ORDER_PARAMS)
     p[0] = (payload_type, flags, ssrc, 0, max_span, after_ext)
+    return p
+
+
+def au_times_params(tick=1, base_time=0, delay=None, flags=0):
+    """an hbs_au_times_params record (ndarray[AU_TIMES_PARAMS] of one, host memory); a delay sets HBS_AUT_DELAY_GIVEN"""
+    p = np.zeros(1, dtype=AU_TIMES_PARAMS)
+    p["flags"], p["tick"], p["base_time"] = flags | (AUT_DELAY_GIVEN if delay is not None else 0), tick, base_time
+    p["delay"] = 0 if delay is None else delay
     return p
 
 
@@ -1620,6 +1634,39 @@ class Context:
             raise HbsError("hbs_access_units: error %d" % int(s["error"]))
         return (au[: aus * ACCESS_UNIT.itemsize].cpu().numpy().view(ACCESS_UNIT).copy(), nal_au[:n_nals].cpu().numpy().view(np.uint32).copy(),
                 s, carry_out.cpu().numpy().view(AU_CARRY).copy())
+
+    def au_times_async(self, au, n_aus, params, summary, dts=None, pts=None, order=None, display=None):
+        """Enqueue hbs_au_times on the current torch stream.  au / summary / dts / pts / order / display are device tensors (each
+        of the four outputs may be None; all None: plan only), au may begin anywhere in an AU table (a GOP cut: a slice of the
+        tensor); params is an ndarray[AU_TIMES_PARAMS] of one in host memory.  Returns the call's return code (0, or HBS_E_ARG
+        for arguments it refuses)."""
+        self._bind_stream()
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=AU_TIMES_PARAMS)
+        return self.lib.hbs_au_times(self.h, p(au) if n_aus else None, int(n_aus),
+                                     params.ctypes.data_as(C.c_void_p) if params is not None else None,
+                                     p(dts), p(pts), p(order), p(display), p(summary))
+
+    def au_times(self, au, tick=1, base_time=0, delay=None, flags=0):
+        """Convenience: decode and presentation times of the access units `au` (ndarray[ACCESS_UNIT] or a device uint8 tensor of
+        the records).  Returns (dts, pts, order, display, summary): device tensors (int64 views of the uint64 times, int32 of the
+        uint32 slots) of one entry per AU, and the summary record."""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        n = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
+        if isinstance(au, np.ndarray):
+            au = t.from_numpy(np.ascontiguousarray(au).view(np.uint8).reshape(-1).copy()).to(dev) if n else None
+        prm = au_times_params(tick, base_time, delay, flags)
+        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        dts, pts = (t.empty(max(n, 1), dtype=t.int64, device=dev) for _ in range(2))
+        order, display = (t.empty(max(n, 1), dtype=t.int32, device=dev) for _ in range(2))
+        self._check(self.au_times_async(au, n, prm, summary, dts, pts, order, display), "hbs_au_times")
+        s = self.read_summary(summary)
+        if int(s["error"]) != 0:
+            raise HbsError("hbs_au_times: error %d (access unit %d reorders across more than %d others)"
+                           % (int(s["error"]), int(s["reserved"][0]) - 1, AUT_MAX_SPAN))
+        return dts[:n], pts[:n], order[:n], display[:n], s
 
     def au_insert_async(self, stream, stream_bytes, index, parsed, n_nals, au, nal_au, n_aus, first_au, au_count, flags,
                         out, index_out, nal_src, nal_au_out, au_out, summary, out_cap=None, index_cap=0):

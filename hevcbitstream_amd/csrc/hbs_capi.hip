@@ -20,6 +20,7 @@
 #include "hbs_filter.h"
 #include "hbs_lenpref.h"
 #include "hbs_au.h"
+#include "hbs_autimes.h"
 #include "hbs_ts.h"
 #include "hbs_tsmux.h"
 #include "hbs_auins.h"
@@ -53,8 +54,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kPws    hbs_mp4_fragment's scratch
  * kQws    hbs_mp4_samples' scratch
  * kSws    hbs_mp4_stbl_samples' scratch
- * kVws    hbs_mp4_stbl_write's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kBufs };
+ * kVws    hbs_mp4_stbl_write's scratch
+ * kXws    hbs_au_times' scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -1075,6 +1077,31 @@ int hbs_au_keep(hbs_ctx* c, const uint32_t* d_nal_au, const hbs_parsed_nal* d_pa
     a.sets = static_cast<uint32_t*>(c->buf[kAws].ptr);
     const hipError_t e = hbs::launch_au_keep(a, c->stream);
     return e == hipSuccess ? 0 : fail(c, e, "launch_au_keep");
+}
+
+int hbs_au_times(hbs_ctx* c, const hbs_access_unit* d_au, uint64_t n_aus, const hbs_au_times_params* params,
+                 uint64_t* d_dts, uint64_t* d_pts, uint32_t* d_order, uint32_t* d_display, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_au_times_params) == 32 && sizeof(hbs_access_unit) == 64, "hbs_au_times layouts");
+    if (!c || !d_summary || !hbs::aut_params_ok(params, n_aus) || (n_aus && !d_au)) return HBS_E_ARG;
+    if (misaligned(d_au, 15) || misaligned(d_summary, 15) || misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_order, 3) ||
+        misaligned(d_display, 3)) {
+        snprintf(c->err, sizeof(c->err), "AU table/summary pointers must be 16-byte aligned, the times 8-byte, order and display 4-byte");
+        return HBS_E_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::AutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.au = d_au; a.n = n_aus;
+    a.flags = params->flags; a.tick = params->tick; a.base_time = params->base_time;
+    a.delay_given = (params->flags & HBS_AUT_DELAY_GIVEN) ? params->delay : 0u;
+    a.dts = reinterpret_cast<unsigned long long*>(d_dts); a.pts = reinterpret_cast<unsigned long long*>(d_pts);
+    a.order = d_order; a.display = d_display; a.summary = d_summary;
+    const int rc = carve(c, c->buf[kXws], "hipMalloc(AU times scratch)", [&](hbs::Carver& w) { hbs::lay_au_times(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
+    const hipError_t e = hbs::launch_au_times(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, "launch_au_times");
 }
 
 int hbs_synth_rbsp(hbs_ctx* c, uint64_t seed, uint64_t n_nals, int mode,

@@ -56,7 +56,8 @@ extern "C" {
 #define HBS_E_CAPACITY    (-4)   /* index / arena / output capacity too small    */
 #define HBS_E_TIMEOUT     (-5)   /* in-kernel look-back wait gave up (bug guard) */
 #define HBS_E_DEPTH       (-6)   /* hbs_parse_headers_compact / _materialize on an out-of-spec stream whose answer needs the
-                                    sequential parse (a chain of slice-own RPS sets deeper than 3): take hbs_parse_headers */
+                                    sequential parse (a chain of slice-own RPS sets deeper than 3): take hbs_parse_headers;
+                                    hbs_au_times on a table that reorders an AU across more than HBS_AUT_MAX_SPAN others */
 
 /* per-NAL status flags */
 #define HBS_ST_ERROR        1    /* nal_to_rbsp() would return -1 (h264_nal.c:156-167) */
@@ -113,10 +114,10 @@ typedef struct hbs_ctx hbs_ctx;
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
  *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples,
- *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write.
+ *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write, hbs_au_times.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
  * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py,
- * tests/test_gpu_mp4_stbl.py and tests/test_gpu_mp4_stbl_write.py replay, no
+ * tests/test_gpu_mp4_stbl.py, tests/test_gpu_mp4_stbl_write.py and tests/test_gpu_au_times.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -1528,6 +1529,72 @@ uint64_t hbs_au_sps_poc_offset(void);   /* offsetof(hevc_sps_t, log2_max_pic_ord
 #define HBS_AUKEEP_PARAM_SETS 1
 int hbs_au_keep(hbs_ctx* ctx, const uint32_t* d_nal_au, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
                 uint64_t first_au, uint64_t au_count, int flags, uint8_t* d_keep /* n_nals bytes */);
+
+/*
+ * ---- decode and presentation times of access units ------------------------------------------------------------------
+ * hbs_au_times turns the picture order counts that hbs_access_units wrote into the d_dts / d_pts tables that hbs_ts_mux,
+ * hbs_mp4_fragment, hbs_mp4_stbl_write and hbs_rtp_pack read, on the device: a raw Annex-B stream carries no
+ * times, and "pts = dts = base_time + a * duration" (what those calls do without tables) is wrong for every stream with
+ * reordered pictures.  The AUs of each coded video sequence are ranked by picture order count; an AU is presented in the slot
+ * of its rank.  Of d_au[a] only `flags` and `pic_order_cnt` are read; a GOP cut is passed as d_au + first_au.  This comment is
+ * the specification; tests/_au_times_ref.py restates it with one sort per segment.  Out-of-spec input has no special case: the
+ * formulas are the definition.
+ *
+ * SEGMENTS.  AU a begins a segment iff a == 0 or d_au[a].flags holds HBS_AU_CVS_START.  s(a) = the first AU of a's segment.
+ *
+ * KEY.  p(a) = the nearest AU at or in front of a without HBS_AU_NO_PICTURE; key(a) = d_au[p(a)].pic_order_cnt as a signed
+ * 32-bit value, -2^31 when the call holds no such AU.  (A segment start other than AU 0 has a picture in every table that
+ * hbs_access_units wrote, so p(a) lies in a's segment but for the -2^31 case; a table where it does not is ranked by the same
+ * formula.)
+ *
+ * OUTPUT SLOT.  o(a) = s(a) + #{ b in a's segment : (key(b), b) < (key(a), a) } in lexicographic order: equal keys go in decode
+ * order.  o is a permutation of [0, n_aus) that maps every segment onto itself.  Equivalently
+ *   o(a) = a + #{ b > a in the segment : key(b) < key(a) } - #{ b < a in the segment : key(b) > key(a) }.
+ *
+ * SPAN (a stated limit).  back(a) = a - min{ b < a in the segment : key(b) > key(a) } and fwd(a) = max{ b > a in the segment :
+ * key(b) < key(a) } - a, each 0 when there is no such b.  An AU with back(a) or fwd(a) above HBS_AUT_MAX_SPAN offends: the
+ * summary's error is HBS_E_DEPTH, reserved[0] = 1 + the lowest offending AU, every other count 0, and nothing but the summary
+ * is written.  H.265 bounds the number of reordered pictures (15), not their distance, but a B-pyramid of GOP 64 has span 63;
+ * the limit bounds the work on any table at 2 * HBS_AUT_MAX_SPAN steps an AU.
+ *
+ * TIMES.  R = max over a of (a - o(a)), the smallest delay that keeps pts >= dts; 0 <= R <= HBS_AUT_MAX_SPAN.
+ *   delay = params->delay with HBS_AUT_DELAY_GIVEN, else R
+ *   dts(a) = base_time + a * tick                pts(a) = base_time + (o(a) + delay) * tick
+ * both exact, and with HBS_AUT_WRAP33 both then reduced modulo 2^33 (what hbs_ts_mux takes).  With delay >= R, pts(a) >= dts(a)
+ * for every AU.  A stream cut into batches (at segment starts) uses one delay for all of them through HBS_AUT_DELAY_GIVEN.
+ * d_order[a] = o(a); d_display[o(a)] = a.
+ *
+ * d_summary on success: nal_count = n_aus, nal_found = segments, rbsp_bytes = the first AU of the last segment (where a caller
+ * who works in batches cuts), stream_bytes = 0, stop_reason = 0, reserved[0] = the delay used, reserved[1] = R, reserved[2] =
+ * AUs with exact pts < dts (only possible with a given delay < R), error = 0.
+ *
+ * All four output pointers NULL: plan only, the summary alone is written.  n_aus == 0 is valid: all counts 0, reserved[0] =
+ * params->delay when given, else 0.  Refused with HBS_E_ARG at once, nothing touched: unknown flags, non-zero `reserved`,
+ * tick == 0, base_time >= 2^62, n_aus > 2^32 - 1, base_time + (n_aus + D) * tick >= 2^62 with D = params->delay when given, else
+ * HBS_AUT_MAX_SPAN (this bounds every time on the host: the device has no time error), a missing ctx, params or d_summary, a
+ * missing d_au with n_aus > 0, a misaligned pointer.
+ * Alignment: d_au, d_summary 16 bytes; d_dts, d_pts 8 bytes; d_order, d_display 4 bytes.
+ * Nothing is stored outside the first n_aus entries of the tables given and the summary; no load goes past d_au[n_aus).  No
+ * host wait (HIP graphs, above).  Scratch: the context's workspace, sized by n_aus alone -- 17 bytes an AU (key, prefix maximum,
+ * suffix minimum and slot, 4 bytes each, and a byte of flags) and 32 bytes per 256 AUs.
+ */
+#define HBS_AUT_MAX_SPAN     1024u /* stated limit, see SPAN */
+#define HBS_AUT_DELAY_GIVEN  1u    /* use params->delay instead of the smallest delay that keeps pts >= dts */
+#define HBS_AUT_WRAP33       2u    /* both outputs modulo 2^33 (what hbs_ts_mux takes) */
+
+typedef struct hbs_au_times_params {   /* HOST memory, 32 bytes */
+    uint32_t flags;        /* HBS_AUT_* */
+    uint32_t tick;         /* duration of one AU in the caller's timescale, >= 1 */
+    uint64_t base_time;    /* dts of AU 0, below 2^62 */
+    uint32_t delay;        /* with HBS_AUT_DELAY_GIVEN: output slots the presentation lags the decode by */
+    uint32_t reserved[3];  /* 0 */
+} hbs_au_times_params;
+
+int hbs_au_times(hbs_ctx* ctx, const hbs_access_unit* d_au, uint64_t n_aus,
+                 const hbs_au_times_params* params,
+                 uint64_t* d_dts, uint64_t* d_pts,        /* optional, each on its own, n_aus */
+                 uint32_t* d_order, uint32_t* d_display,  /* optional, each on its own, n_aus */
+                 hbs_summary* d_summary);
 
 /*
  * ---- access-unit delimiters and parameter sets in front of access units ---------------------------------------------
