@@ -566,6 +566,32 @@ def rtp_frames(data, cap=None):
     return off[:filled], size[:filled], int(used.value), frames
 
 
+# ---- what the device-call wrappers share ("adding a device call") ---------------------------------------------------
+
+def _p(x):
+    """a device tensor, or None, as the pointer argument of a foreign call"""
+    return C.c_void_p(x.data_ptr()) if x is not None else None
+
+
+def _rec(params, dtype):
+    """a host parameter record, or None -> (the record's array, its pointer argument).  The pointer is good while the array
+    lives: the caller keeps both in locals until the foreign call has returned."""
+    if params is None:
+        return None, None
+    a = np.ascontiguousarray(params, dtype=dtype)
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
+def _holds(x, width=1):
+    """what the tensor x holds, in records of `width` bytes (None holds nothing): the default of a capacity"""
+    return x.numel() * x.element_size() // width if x is not None else 0
+
+
+def _host(x, n, dtype):
+    """the first n records of a device tensor of bytes as a host array of `dtype`"""
+    return x[: n * np.dtype(dtype).itemsize].cpu().numpy().view(dtype).copy()
+
+
 class Context:
     """One per GPU (per rank).  Device buffers are torch uint8 CUDA tensors; the
     library runs on torch's current stream so that ordering with torch ops is
@@ -602,6 +628,42 @@ class Context:
     def _check(self, rc, what):
         if rc != 0:
             raise HbsError("%s failed: %d (%s)" % (what, rc, self.lib.hbs_last_error(self.h).decode()))
+
+    # ---- plan, allocate, run: what the convenience wrappers of the device calls share ----
+
+    def _empty(self, nbytes):
+        return self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.torch.device("cuda", self.device))
+
+    def _zeros(self, nbytes=SUMMARY.itemsize):
+        """zeroed device bytes: by default the summary a call is given"""
+        return self.torch.zeros(nbytes, dtype=self.torch.uint8, device=self.torch.device("cuda", self.device))
+
+    def _dv(self, x, dtype=None, empty=True):
+        """an ndarray (of `dtype`; None: its bytes as they are) or a device tensor of its bytes -> (device tensor of the bytes,
+        entries).  None stays None: the C calls read a null pointer as "absent".  A table of no entries becomes 16 zeroed
+        bytes, so that the call still gets a pointer (empty=False: None)."""
+        if x is None:
+            return None, 0
+        if not isinstance(x, np.ndarray):
+            return x, _holds(x, np.dtype(dtype).itemsize if dtype is not None else 1)
+        b = np.ascontiguousarray(x, dtype=dtype).view(np.uint8).reshape(-1)
+        if not b.size:
+            return (self._zeros(16) if empty else None), 0
+        return self.torch.from_numpy(b.copy()).to(self.torch.device("cuda", self.device)), len(x)
+
+    def _raise_on(self, name, s, where=""):
+        """HbsError for a summary that reports an error.  where: what follows "<name>: error %d", with {0} {1} {2} for the
+        entries reserved[0..2] name (each is 1 + the entry), or a function of the summary that gives that text"""
+        if int(s["error"]) != 0:
+            where = where(s) if callable(where) else where
+            raise HbsError("%s: error %d%s" % (name, int(s["error"]), where.format(*[int(r) - 1 for r in s["reserved"]])))
+
+    def _run(self, name, rc, summary, where=""):
+        """behind an enqueue (a plan or a run): its return code checked, the summary read -> the summary record"""
+        self._check(rc, name)
+        s = self.read_summary(summary)
+        self._raise_on(name, s, where)
+        return s
 
     def set_sequential_parse(self, on=True):
         """parse batches NAL after NAL with ONE set of derived RPS tables, as the reference does (slow, exact on any input)"""
@@ -904,7 +966,7 @@ class Context:
         """hbs_parse_headers_compact (want is None) / hbs_parse_materialize (want: int64 / uint64 device tensor of NAL numbers).
         structs None: plan only."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
+        p = _p
         common = [self.h, p(rbsp), p(index), n_nals, p(parsed), p(compact), p(structs), structs.numel() if structs is not None else 0,
                   p(initial_sps_slot), p(initial_pps)]
         if want is None:
@@ -998,16 +1060,13 @@ class Context:
     def filter_annexb_async(self, stream, stream_bytes, index, n_nals, out, index_out, summary, rule=None, keep=None, out_cap=None):
         """Enqueue hbs_filter_annexb on the current torch stream.  stream / index / out / index_out / summary / keep are device
         tensors (out None: plan only; index_out may be None); rule is an ndarray[NAL_FILTER] of one (host memory).  Exactly one of
-        rule and keep is given."""
+        rule and keep is given.  Raises HbsError for arguments the call refuses (the later _async wrappers return the code)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
-        if rule is not None:
-            rule = np.ascontiguousarray(rule, dtype=NAL_FILTER)
+        rule, rule_p = _rec(rule, NAL_FILTER)
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
-        rc = self.lib.hbs_filter_annexb(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None,
-                                        int(n_nals), rule.ctypes.data_as(C.c_void_p) if rule is not None else None, p(keep),
-                                        p(out), int(out_cap), p(index_out), p(summary))
+            out_cap = _holds(out)
+        rc = self.lib.hbs_filter_annexb(self.h, _p(stream) if stream_bytes else None, int(stream_bytes), _p(index) if n_nals else None,
+                                        int(n_nals), rule_p, _p(keep), _p(out), int(out_cap), _p(index_out), _p(summary))
         self._check(rc, "hbs_filter_annexb")
 
     def filter_annexb(self, stream, index_entries, keep_types=NALMASK_ALL, max_temporal_id_plus1=7, max_layer_id=63,
@@ -1016,37 +1075,18 @@ class Context:
         byte in `keep` (array of n_nals, non-zero = keep; host or device) is set.  index_entries: ndarray[NAL_ENTRY] (host) or a
         device uint8 tensor of its entries.  Plans first, allocates the exact output, runs.  Returns (out device tensor,
         entries_out ndarray[NAL_ENTRY], summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-        if isinstance(index_entries, np.ndarray):
-            n = len(index_entries)
-            d_idx = t.from_numpy(np.ascontiguousarray(index_entries).view(np.uint8).copy()).to(dev) if n else None
-        else:
-            n = index_entries.numel() // NAL_ENTRY.itemsize
-            d_idx = index_entries
+        d_idx, n = self._dv(index_entries, NAL_ENTRY, empty=False)
         nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
-        rule = None
-        d_keep = None
-        if keep is None:
-            rule = self.nal_filter(keep_types, max_temporal_id_plus1, max_layer_id, keep_short)
-        elif isinstance(keep, np.ndarray):
-            d_keep = t.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8).copy()).to(dev) if n else t.zeros(16, dtype=t.uint8, device=dev)
-        else:
-            d_keep = keep
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        rule = self.nal_filter(keep_types, max_temporal_id_plus1, max_layer_id, keep_short) if keep is None else None
+        d_keep, _ = self._dv(keep, np.uint8)
+        summary = self._zeros()
         self.filter_annexb_async(stream, nbytes, d_idx, n, None, None, summary, rule=rule, keep=d_keep)
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_filter_annexb: error %d" % int(s["error"]))
-        need = int(s["stream_bytes"])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        d_out_idx = t.empty(max(n, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
+        need = int(self._run("hbs_filter_annexb", 0, summary)["stream_bytes"])
+        out = self._empty(max(need, 16))
+        d_out_idx = self._empty(max(n, 1) * NAL_ENTRY.itemsize)
         self.filter_annexb_async(stream, nbytes, d_idx, n, out, d_out_idx, summary, rule=rule, keep=d_keep, out_cap=need)
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_filter_annexb: error %d" % int(s["error"]))
-        kept = int(s["nal_count"])
-        return out[:need], d_out_idx[: kept * NAL_ENTRY.itemsize].cpu().numpy().view(NAL_ENTRY).copy(), s
+        s = self._run("hbs_filter_annexb", 0, summary)
+        return out[:need], _host(d_out_idx, int(s["nal_count"]), NAL_ENTRY), s
 
     # ---- length-prefixed NAL units (MP4 samples) ---------------------------------------
 
@@ -1056,25 +1096,23 @@ class Context:
         sample_off are device tensors (out None: plan only; index_out, keep, nal_au, sample_off may be None).  Returns the
         call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
-        return self.lib.hbs_annexb_to_lenpref(self.h, p(stream) if stream_bytes else None, int(stream_bytes),
-                                              p(index) if n_nals else None, int(n_nals), p(keep), int(length_size),
-                                              p(nal_au), int(n_aus), p(sample_off), p(out), int(out_cap), p(index_out), p(summary))
+            out_cap = _holds(out)
+        return self.lib.hbs_annexb_to_lenpref(self.h, _p(stream) if stream_bytes else None, int(stream_bytes),
+                                              _p(index) if n_nals else None, int(n_nals), _p(keep), int(length_size),
+                                              _p(nal_au), int(n_aus), _p(sample_off), _p(out), int(out_cap), _p(index_out), _p(summary))
 
     def lenpref_to_annexb_async(self, data, in_bytes, sample_off, sample_size, n_samples, out, sample_off_out, summary,
                                 length_size=4, startcode_bytes=4, nal_cap=0, out_cap=None):
         """Enqueue hbs_lenpref_to_annexb on the current torch stream.  data / sample_off / sample_size / out / sample_off_out /
         summary are device tensors (out None: plan only; sample_off_out may be None).  Returns the call's return code."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
-        return self.lib.hbs_lenpref_to_annexb(self.h, p(data) if in_bytes else None, int(in_bytes), int(length_size),
-                                              p(sample_off) if n_samples else None, p(sample_size) if n_samples else None,
-                                              int(n_samples), int(startcode_bytes), int(nal_cap), p(out), int(out_cap),
-                                              p(sample_off_out), p(summary))
+            out_cap = _holds(out)
+        return self.lib.hbs_lenpref_to_annexb(self.h, _p(data) if in_bytes else None, int(in_bytes), int(length_size),
+                                              _p(sample_off) if n_samples else None, _p(sample_size) if n_samples else None,
+                                              int(n_samples), int(startcode_bytes), int(nal_cap), _p(out), int(out_cap),
+                                              _p(sample_off_out), _p(summary))
 
     def annexb_to_lenpref(self, stream, index_entries, keep=None, length_size=4, nal_au=None, n_aus=0, stream_bytes=None):
         """Convenience: the kept NAL units of `stream` (device uint8 tensor) as length-prefixed records.  index_entries:
@@ -1082,72 +1120,47 @@ class Context:
         nal_au: None or the AU number of every NAL (uint32, host or device) with n_aus, for the sample table.  Plans first,
         allocates the exact output, runs.  Returns (out device tensor, entries_out ndarray[NAL_ENTRY], sample_off ndarray[uint64]
         of n_aus + 1 or None, summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-        if isinstance(index_entries, np.ndarray):
-            n = len(index_entries)
-            d_idx = t.from_numpy(np.ascontiguousarray(index_entries).view(np.uint8).copy()).to(dev) if n else None
-        else:
-            n = index_entries.numel() // NAL_ENTRY.itemsize
-            d_idx = index_entries
+        name = "hbs_annexb_to_lenpref"
+        d_idx, n = self._dv(index_entries, NAL_ENTRY, empty=False)
         nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
-        d_keep = keep
-        if isinstance(keep, np.ndarray):
-            d_keep = t.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8).copy()).to(dev) if n else t.zeros(16, dtype=t.uint8, device=dev)
-        d_au = nal_au
-        if isinstance(nal_au, np.ndarray):
-            d_au = t.from_numpy(np.ascontiguousarray(nal_au, dtype=np.uint32).view(np.uint8).copy()).to(dev) if n else t.zeros(16, dtype=t.uint8, device=dev)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        d_keep, _ = self._dv(keep, np.uint8)
+        d_au, _ = self._dv(nal_au, np.uint32)
+        summary = self._zeros()
         args = dict(keep=d_keep, length_size=length_size, nal_au=d_au, n_aus=n_aus)
-        self._check(self.annexb_to_lenpref_async(stream, nbytes, d_idx, n, None, None, summary, **args), "hbs_annexb_to_lenpref")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_annexb_to_lenpref: error %d" % int(s["error"]))
+        s = self._run(name, self.annexb_to_lenpref_async(stream, nbytes, d_idx, n, None, None, summary, **args), summary)
         need = int(s["stream_bytes"])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        d_out_idx = t.empty(max(n, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
-        d_so = t.empty((int(n_aus) + 1) * 8, dtype=t.uint8, device=dev) if d_au is not None else None
-        self._check(self.annexb_to_lenpref_async(stream, nbytes, d_idx, n, out, d_out_idx, summary, sample_off=d_so, out_cap=need, **args),
-                    "hbs_annexb_to_lenpref")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_annexb_to_lenpref: error %d" % int(s["error"]))
-        kept = int(s["nal_count"])
-        return (out[:need], d_out_idx[: kept * NAL_ENTRY.itemsize].cpu().numpy().view(NAL_ENTRY).copy(),
+        out = self._empty(max(need, 16))
+        d_out_idx = self._empty(max(n, 1) * NAL_ENTRY.itemsize)
+        d_so = self._empty((int(n_aus) + 1) * 8) if d_au is not None else None
+        s = self._run(name, self.annexb_to_lenpref_async(stream, nbytes, d_idx, n, out, d_out_idx, summary, sample_off=d_so, out_cap=need, **args),
+                      summary)
+        return (out[:need], _host(d_out_idx, int(s["nal_count"]), NAL_ENTRY),
                 d_so.cpu().numpy().view(np.uint64).copy() if d_so is not None else None, s)
+
+    def _offsets_and_sizes(self, name, off, size, what):
+        """two uint64 tables of one length, host or device -> (offsets on the device, sizes on the device, entries)"""
+        d_off, n = self._dv(off, np.uint64)
+        d_size, n2 = self._dv(size, np.uint64)
+        if n != n2:
+            raise HbsError("%s: %d %s offsets, %d sizes" % (name, n, what, n2))
+        return d_off, d_size, n
 
     def lenpref_to_annexb(self, data, sample_off, sample_size, length_size=4, startcode_bytes=4, in_bytes=None):
         """Convenience: the samples data[off_s, off_s + size_s) (sample_off / sample_size: uint64 arrays, host or device
         tensors of their bytes) as one Annex-B stream.  Plans first, allocates the exact output, runs.  Returns (out device
         tensor, sample_off_out ndarray[uint64] of n_samples + 1, summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x):
-            if isinstance(x, np.ndarray):
-                a = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8)
-                return (t.from_numpy(a.copy()).to(dev) if a.size else t.zeros(16, dtype=t.uint8, device=dev)), len(x)
-            return x, x.numel() * x.element_size() // 8
-        d_off, n = dv(sample_off)
-        d_size, n2 = dv(sample_size)
-        if n != n2:
-            raise HbsError("hbs_lenpref_to_annexb: %d sample offsets, %d sizes" % (n, n2))
+        name = "hbs_lenpref_to_annexb"
+        d_off, d_size, n = self._offsets_and_sizes(name, sample_off, sample_size, "sample")
         nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        summary = self._zeros()
         args = dict(length_size=length_size, startcode_bytes=startcode_bytes)
-        self._check(self.lenpref_to_annexb_async(data, nbytes, d_off, d_size, n, None, None, summary, nal_cap=(1 << 64) - 1, **args),
-                    "hbs_lenpref_to_annexb")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_lenpref_to_annexb: error %d (sample %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        s = self._run(name, self.lenpref_to_annexb_async(data, nbytes, d_off, d_size, n, None, None, summary, nal_cap=(1 << 64) - 1, **args),
+                      summary, " (sample {0})")
         need, recs = int(s["stream_bytes"]), int(s["nal_count"])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        d_so = t.empty((n + 1) * 8, dtype=t.uint8, device=dev)
-        self._check(self.lenpref_to_annexb_async(data, nbytes, d_off, d_size, n, out, d_so, summary, nal_cap=recs, out_cap=need, **args),
-                    "hbs_lenpref_to_annexb")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_lenpref_to_annexb: error %d" % int(s["error"]))
+        out = self._empty(max(need, 16))
+        d_so = self._empty((n + 1) * 8)
+        s = self._run(name, self.lenpref_to_annexb_async(data, nbytes, d_off, d_size, n, out, d_so, summary, nal_cap=recs, out_cap=need, **args),
+                      summary)
         return out[:need], d_so.cpu().numpy().view(np.uint64).copy(), s
 
     # ---- MPEG transport stream -----------------------------------------------------------
@@ -1156,77 +1169,53 @@ class Context:
         """Enqueue hbs_ts_demux on the current torch stream.  ts / out / pes / summary are device tensors (out None: plan only;
         pes may be None).  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
+            out_cap = _holds(out)
         if pes_cap is None:
-            pes_cap = pes.numel() * pes.element_size() // TS_PES.itemsize if pes is not None else 0
-        return self.lib.hbs_ts_demux(self.h, p(ts) if ts_bytes else None, int(ts_bytes), int(packet_bytes), int(pid),
-                                     p(out), int(out_cap), p(pes), int(pes_cap), p(summary))
+            pes_cap = _holds(pes, TS_PES.itemsize)
+        return self.lib.hbs_ts_demux(self.h, _p(ts) if ts_bytes else None, int(ts_bytes), int(packet_bytes), int(pid),
+                                     _p(out), int(out_cap), _p(pes), int(pes_cap), _p(summary))
 
     def ts_demux(self, ts, pid, packet_bytes=188, ts_bytes=None):
         """Convenience: the elementary stream of `pid` in the transport stream `ts` (device uint8 tensor).  Plans first,
         allocates the exact outputs, runs.  Returns (out device tensor, pes ndarray[TS_PES], summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
+        name = "hbs_ts_demux"
         nbytes = int(ts.numel()) if ts_bytes is None else int(ts_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.ts_demux_async(ts, nbytes, packet_bytes, pid, None, None, summary), "hbs_ts_demux")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_ts_demux: error %d (packet %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        summary = self._zeros()
+        s = self._run(name, self.ts_demux_async(ts, nbytes, packet_bytes, pid, None, None, summary), summary, " (packet {0})")
         need, n_pes = int(s["stream_bytes"]), int(s["nal_count"])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        pes = t.empty(max(n_pes, 1) * TS_PES.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.ts_demux_async(ts, nbytes, packet_bytes, pid, out, pes, summary, out_cap=need, pes_cap=n_pes), "hbs_ts_demux")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_ts_demux: error %d" % int(s["error"]))
-        return out[:need], pes[: n_pes * TS_PES.itemsize].cpu().numpy().view(TS_PES).copy(), s
+        out = self._empty(max(need, 16))
+        pes = self._empty(max(n_pes, 1) * TS_PES.itemsize)
+        s = self._run(name, self.ts_demux_async(ts, nbytes, packet_bytes, pid, out, pes, summary, out_cap=need, pes_cap=n_pes), summary)
+        return out[:need], _host(pes, n_pes, TS_PES), s
 
     def ts_mux_async(self, stream, stream_bytes, au, n_aus, pts, dts, params, out, au_packet, summary, out_cap=None):
         """Enqueue hbs_ts_mux on the current torch stream.  stream / au / pts / dts / out / au_packet / summary are device
         tensors (pts, dts, au_packet may be None; out None: plan only); params is an ndarray[TS_MUX_PARAMS] of one in host
         memory.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=TS_MUX_PARAMS)
-        return self.lib.hbs_ts_mux(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(au) if n_aus else None, int(n_aus),
-                                   p(pts), p(dts), params.ctypes.data_as(C.c_void_p) if params is not None else None,
-                                   p(out), int(out_cap), p(au_packet), p(summary))
+            out_cap = _holds(out)
+        params, params_p = _rec(params, TS_MUX_PARAMS)
+        return self.lib.hbs_ts_mux(self.h, _p(stream) if stream_bytes else None, int(stream_bytes), _p(au) if n_aus else None, int(n_aus),
+                                   _p(pts), _p(dts), params_p, _p(out), int(out_cap), _p(au_packet), _p(summary))
 
     def ts_mux(self, stream, au, pts=None, dts=None, stream_bytes=None, **params):
         """Convenience: the access units `au` (ndarray[ACCESS_UNIT] or a device uint8 tensor of the records) of `stream` (device
         uint8 tensor) as transport packets.  pts / dts: None or one uint64 per AU (TS_NO_TIME: absent), host arrays or device
         tensors; params: the keywords of ts_mux_params.  Plans first, allocates the exact output, runs.  Returns (out device
         tensor, au_packet ndarray[uint32] of n_aus + 1, summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x, dtype):
-            if isinstance(x, np.ndarray):
-                b = np.ascontiguousarray(x, dtype=dtype).view(np.uint8).reshape(-1)
-                return t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
-            return x
-        n = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
-        au, pts, dts = dv(au, ACCESS_UNIT), dv(pts, np.uint64), dv(dts, np.uint64)
+        name = "hbs_ts_mux"
+        au, n = self._dv(au, ACCESS_UNIT)
+        pts, dts = self._dv(pts, np.uint64)[0], self._dv(dts, np.uint64)[0]
         prm = ts_mux_params(**params)
         nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.ts_mux_async(stream, nbytes, au, n, pts, dts, prm, None, None, summary), "hbs_ts_mux")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_ts_mux: error %d (access unit %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        summary = self._zeros()
+        s = self._run(name, self.ts_mux_async(stream, nbytes, au, n, pts, dts, prm, None, None, summary), summary, " (access unit {0})")
         need = int(s["stream_bytes"])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        au_packet = t.empty(n + 1, dtype=t.int32, device=dev)
-        self._check(self.ts_mux_async(stream, nbytes, au, n, pts, dts, prm, out, au_packet, summary, out_cap=need), "hbs_ts_mux")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_ts_mux: error %d" % int(s["error"]))
+        out = self._empty(max(need, 16))
+        au_packet = self.torch.empty(n + 1, dtype=self.torch.int32, device=out.device)
+        s = self._run(name, self.ts_mux_async(stream, nbytes, au, n, pts, dts, prm, out, au_packet, summary, out_cap=need), summary)
         return out[:need], au_packet.cpu().numpy().view(np.uint32).copy(), s
 
     # ---- RTP ------------------------------------------------------------------------------
@@ -1236,49 +1225,34 @@ class Context:
         are device tensors (nal_au, pts, nal_off, nal_packet may be None; out None: plan only); params is an
         ndarray[RTP_PARAMS] of one in host memory.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=RTP_PARAMS)
-        return self.lib.hbs_rtp_pack(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None, int(n_nals),
-                                     p(nal_au), int(n_aus), p(pts), params.ctypes.data_as(C.c_void_p) if params is not None else None,
-                                     p(out), int(out_cap), p(nal_off), p(nal_packet), p(summary))
+            out_cap = _holds(out)
+        params, params_p = _rec(params, RTP_PARAMS)
+        return self.lib.hbs_rtp_pack(self.h, _p(stream) if stream_bytes else None, int(stream_bytes), _p(index) if n_nals else None, int(n_nals),
+                                     _p(nal_au), int(n_aus), _p(pts), params_p, _p(out), int(out_cap), _p(nal_off), _p(nal_packet), _p(summary))
 
     def rtp_pack(self, stream, index, n_nals=None, nal_au=None, n_aus=None, pts=None, stream_bytes=None, **params):
         """Convenience: the NALs `index` (ndarray[NAL_ENTRY] or a device uint8 tensor of the records) of `stream` (device uint8
         tensor) as RTP packets.  nal_au: None or one uint32 per NAL; pts: None or one uint64 per AU; host arrays or device
         tensors; params: the keywords of rtp_params.  Plans first, allocates the exact output, runs.  Returns (out device
         tensor, packet_off ndarray[uint64] of packets + 1: where every packet begins and the total, summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x, dtype):
-            if isinstance(x, np.ndarray):
-                b = np.ascontiguousarray(x, dtype=dtype).view(np.uint8).reshape(-1)
-                return t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
-            return x
-        n = n_nals if n_nals is not None else (len(index) if isinstance(index, np.ndarray) else index.numel() * index.element_size() // NAL_ENTRY.itemsize)
-        if n_aus is None:
-            n_aus = 0 if pts is None else (len(pts) if isinstance(pts, np.ndarray) else pts.numel() * pts.element_size() // 8)
-            if pts is None and nal_au is not None:
-                n_aus = 1 << 32
-        index, nal_au, pts = dv(index, NAL_ENTRY), dv(nal_au, np.uint32), dv(pts, np.uint64)
+        name = "hbs_rtp_pack"
+        index, n = self._dv(index, NAL_ENTRY)
+        if n_nals is not None:
+            n = n_nals
+        nal_au, pts_given = self._dv(nal_au, np.uint32)[0], pts is not None
+        pts, n_pts = self._dv(pts, np.uint64)
+        if n_aus is None:                                   # the times say how many AUs there are; AU numbers without times: any
+            n_aus = n_pts if pts_given or nal_au is None else 1 << 32
         prm = rtp_params(**params)
         nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        summary = self._zeros()
         args = (stream, nbytes, index, n, nal_au, n_aus, pts, prm)
-        self._check(self.rtp_pack_async(*args, None, None, None, summary), "hbs_rtp_pack")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_rtp_pack: error %d (NAL %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        s = self._run(name, self.rtp_pack_async(*args, None, None, None, summary), summary, " (NAL {0})")
         need = int(s["stream_bytes"])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        nal_off, nal_packet = (t.empty((n + 1) * 8, dtype=t.uint8, device=dev) for _ in range(2))
-        self._check(self.rtp_pack_async(*args, out, nal_off, nal_packet, summary, out_cap=need), "hbs_rtp_pack")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_rtp_pack: error %d" % int(s["error"]))
+        out = self._empty(max(need, 16))
+        nal_off, nal_packet = (self._empty((n + 1) * 8) for _ in range(2))
+        s = self._run(name, self.rtp_pack_async(*args, out, nal_off, nal_packet, summary, out_cap=need), summary)
         tabs = [x.cpu().numpy().view(np.uint64) for x in (nal_off, nal_packet)]
         return out[:need], rtp_packet_offsets(tabs[0], tabs[1], int(prm["max_payload"][0]), int(prm["framing"][0])), s
 
@@ -1289,57 +1263,37 @@ class Context:
         an ndarray[RTP_UNPACK_PARAMS] of one in host memory.  nal_cap / au_cap default to what the tensors hold.  Returns the
         call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
+            out_cap = _holds(out)
         if nal_cap is None:
-            caps = [x.numel() * x.element_size() // w for x, w in ((index_out, NAL_ENTRY.itemsize), (nal_au_out, 4)) if x is not None]
+            caps = [_holds(x, w) for x, w in ((index_out, NAL_ENTRY.itemsize), (nal_au_out, 4)) if x is not None]
             nal_cap = min(caps) if caps else (1 << 64) - 1
         if au_cap is None:
-            au_cap = au_ts_out.numel() * au_ts_out.element_size() // 8 if au_ts_out is not None else 0
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=RTP_UNPACK_PARAMS)
-        return self.lib.hbs_rtp_unpack(self.h, p(data) if in_bytes else None, int(in_bytes), p(pkt_off) if n_packets else None,
-                                       p(pkt_size) if n_packets else None, int(n_packets),
-                                       params.ctypes.data_as(C.c_void_p) if params is not None else None, p(out), int(out_cap),
-                                       p(index_out), p(nal_au_out), int(nal_cap), p(au_ts_out), int(au_cap), p(summary))
+            au_cap = _holds(au_ts_out, 8)
+        params, params_p = _rec(params, RTP_UNPACK_PARAMS)
+        return self.lib.hbs_rtp_unpack(self.h, _p(data) if in_bytes else None, int(in_bytes), _p(pkt_off) if n_packets else None,
+                                       _p(pkt_size) if n_packets else None, int(n_packets), params_p, _p(out), int(out_cap),
+                                       _p(index_out), _p(nal_au_out), int(nal_cap), _p(au_ts_out), int(au_cap), _p(summary))
 
     def rtp_unpack(self, data, pkt_off, pkt_size, in_bytes=None, **params):
         """Convenience: the RTP packets data[off_p, off_p + size_p) (data: device uint8 tensor; pkt_off / pkt_size: uint64 arrays,
         host or device tensors of their bytes) as one Annex-B stream; params: the keywords of rtp_unpack_params.  Plans first,
         allocates the exact outputs, runs.  Returns (out device tensor, index device tensor of NAL_ENTRY records, nal_au
         ndarray[uint32], au_ts ndarray[uint64], summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x):
-            if isinstance(x, np.ndarray):
-                a = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8)
-                return (t.from_numpy(a.copy()).to(dev) if a.size else t.zeros(16, dtype=t.uint8, device=dev)), len(x)
-            return x, x.numel() * x.element_size() // 8
-        d_off, n = dv(pkt_off)
-        d_size, n2 = dv(pkt_size)
-        if n != n2:
-            raise HbsError("hbs_rtp_unpack: %d packet offsets, %d sizes" % (n, n2))
+        name = "hbs_rtp_unpack"
+        d_off, d_size, n = self._offsets_and_sizes(name, pkt_off, pkt_size, "packet")
         prm = rtp_unpack_params(**params)
         nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        summary = self._zeros()
         args = (data, nbytes, d_off, d_size, n, prm)
-        self._check(self.rtp_unpack_async(*args, None, None, None, None, summary), "hbs_rtp_unpack")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_rtp_unpack: error %d (packet %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        s = self._run(name, self.rtp_unpack_async(*args, None, None, None, None, summary), summary, " (packet {0})")
         need, nals, aus = int(s["stream_bytes"]), int(s["nal_count"]), int(s["reserved"][1])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        index = t.empty(max(nals, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
-        nal_au = t.empty(max(nals, 1) * 4, dtype=t.uint8, device=dev)
-        au_ts = t.empty(max(aus, 1) * 8, dtype=t.uint8, device=dev)
-        self._check(self.rtp_unpack_async(*args, out, index, nal_au, au_ts, summary, out_cap=need, nal_cap=nals, au_cap=aus), "hbs_rtp_unpack")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_rtp_unpack: error %d" % int(s["error"]))
-        return (out[:need], index[: nals * NAL_ENTRY.itemsize], nal_au[: nals * 4].cpu().numpy().view(np.uint32).copy(),
-                au_ts[: aus * 8].cpu().numpy().view(np.uint64).copy(), s)
+        out = self._empty(max(need, 16))
+        index = self._empty(max(nals, 1) * NAL_ENTRY.itemsize)
+        nal_au = self._empty(max(nals, 1) * 4)
+        au_ts = self._empty(max(aus, 1) * 8)
+        s = self._run(name, self.rtp_unpack_async(*args, out, index, nal_au, au_ts, summary, out_cap=need, nal_cap=nals, au_cap=aus), summary)
+        return out[:need], index[: nals * NAL_ENTRY.itemsize], _host(nal_au, nals, np.uint32), _host(au_ts, aus, np.uint64), s
 
     def rtp_order_async(self, data, in_bytes, pkt_off, pkt_size, n_packets, params, off_out, size_out, src_out, ext_out, summary,
                         out_cap=None):
@@ -1348,16 +1302,13 @@ class Context:
         ndarray[RTP_ORDER_PARAMS] of one in host memory.  out_cap (entries) defaults to what the tensors hold.  Returns the
         call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            caps = [x.numel() * x.element_size() // w for x, w in ((off_out, 8), (size_out, 8), (src_out, 4), (ext_out, 8)) if x is not None]
+            caps = [_holds(x, w) for x, w in ((off_out, 8), (size_out, 8), (src_out, 4), (ext_out, 8)) if x is not None]
             out_cap = min(caps) if caps else 0
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=RTP_ORDER_PARAMS)
-        return self.lib.hbs_rtp_order(self.h, p(data) if in_bytes else None, int(in_bytes), p(pkt_off) if n_packets else None,
-                                      p(pkt_size) if n_packets else None, int(n_packets),
-                                      params.ctypes.data_as(C.c_void_p) if params is not None else None, p(off_out), p(size_out),
-                                      p(src_out), p(ext_out), int(out_cap), p(summary))
+        params, params_p = _rec(params, RTP_ORDER_PARAMS)
+        return self.lib.hbs_rtp_order(self.h, _p(data) if in_bytes else None, int(in_bytes), _p(pkt_off) if n_packets else None,
+                                      _p(pkt_size) if n_packets else None, int(n_packets), params_p, _p(off_out), _p(size_out),
+                                      _p(src_out), _p(ext_out), int(out_cap), _p(summary))
 
     def rtp_order(self, data, pkt_off, pkt_size, in_bytes=None, **params):
         """Convenience: the table of the RTP packets data[off_p, off_p + size_p) in arrival order (data: device uint8 tensor;
@@ -1365,38 +1316,22 @@ class Context:
         the keywords of rtp_order_params (max_span defaults to n_packets + 65536).  Plans first, allocates the exact outputs,
         runs.  Returns (off device tensor, size device tensor -- the bytes of uint64 tables, what rtp_unpack takes --, src
         ndarray[uint32], ext ndarray[uint64], summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x):
-            if isinstance(x, np.ndarray):
-                a = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8)
-                return (t.from_numpy(a.copy()).to(dev) if a.size else t.zeros(16, dtype=t.uint8, device=dev)), len(x)
-            return x, x.numel() * x.element_size() // 8
-        d_off, n = dv(pkt_off)
-        d_size, n2 = dv(pkt_size)
-        if n != n2:
-            raise HbsError("hbs_rtp_order: %d packet offsets, %d sizes" % (n, n2))
+        name = "hbs_rtp_order"
+        d_off, d_size, n = self._offsets_and_sizes(name, pkt_off, pkt_size, "packet")
         params.setdefault("max_span", n + 65536)
         prm = rtp_order_params(**params)
         nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        summary = self._zeros()
         args = (data, nbytes, d_off, d_size, n, prm)
-        self._check(self.rtp_order_async(*args, None, None, None, None, summary), "hbs_rtp_order")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            if int(s["reserved"][0]):
-                raise HbsError("hbs_rtp_order: error %d (packet %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
-            raise HbsError("hbs_rtp_order: error %d (span %d, max_span %d)" % (int(s["error"]), int(s["stream_bytes"]), int(prm["max_span"][0])))
+
+        def where(s):                                       # a faulty packet is named; otherwise the span was too long
+            return " (packet {0})" if int(s["reserved"][0]) else " (span %d, max_span %d)" % (int(s["stream_bytes"]), int(prm["max_span"][0]))
+        s = self._run(name, self.rtp_order_async(*args, None, None, None, None, summary), summary, where)
         kept = int(s["nal_count"])
-        off, size, ext = (t.empty(max(kept, 1) * 8, dtype=t.uint8, device=dev) for _ in range(3))
-        src = t.empty(max(kept, 1) * 4, dtype=t.uint8, device=dev)
-        self._check(self.rtp_order_async(*args, off, size, src, ext, summary, out_cap=kept), "hbs_rtp_order")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_rtp_order: error %d" % int(s["error"]))
-        return (off[: kept * 8], size[: kept * 8], src[: kept * 4].cpu().numpy().view(np.uint32).copy(),
-                ext[: kept * 8].cpu().numpy().view(np.uint64).copy(), s)
+        off, size, ext = (self._empty(max(kept, 1) * 8) for _ in range(3))
+        src = self._empty(max(kept, 1) * 4)
+        s = self._run(name, self.rtp_order_async(*args, off, size, src, ext, summary, out_cap=kept), summary)
+        return off[: kept * 8], size[: kept * 8], _host(src, kept, np.uint32), _host(ext, kept, np.uint64), s
 
     # ---- fragmented MP4 -----------------------------------------------------------------
 
@@ -1407,17 +1342,15 @@ class Context:
         frag may be None); params is an ndarray[MP4_PARAMS] of one in host memory.  frag_cap (records) and out_cap (bytes)
         default to what the tensors hold.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
+            out_cap = _holds(out)
         if frag_cap is None:
-            frag_cap = frag.numel() * frag.element_size() // MP4_FRAG.itemsize if frag is not None else 0
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=MP4_PARAMS)
-        return self.lib.hbs_mp4_fragment(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None,
-                                         int(n_nals), p(keep), p(nal_au) if n_nals else None, p(au) if n_aus else None, int(n_aus),
-                                         p(dts), p(pts), params.ctypes.data_as(C.c_void_p) if params is not None else None,
-                                         p(out), int(out_cap), p(sample_off), p(sample_size), p(frag), int(frag_cap), p(summary))
+            frag_cap = _holds(frag, MP4_FRAG.itemsize)
+        params, params_p = _rec(params, MP4_PARAMS)
+        return self.lib.hbs_mp4_fragment(self.h, _p(stream) if stream_bytes else None, int(stream_bytes), _p(index) if n_nals else None,
+                                         int(n_nals), _p(keep), _p(nal_au) if n_nals else None, _p(au) if n_aus else None, int(n_aus),
+                                         _p(dts), _p(pts), params_p, _p(out), int(out_cap), _p(sample_off), _p(sample_size), _p(frag),
+                                         int(frag_cap), _p(summary))
 
     def mp4_fragment(self, stream, index, nal_au, au, keep=None, dts=None, pts=None, stream_bytes=None, **params):
         """Convenience: the access units of `stream` (device uint8 tensor) as fMP4 fragments.  index: ndarray[NAL_ENTRY], nal_au:
@@ -1425,39 +1358,24 @@ class Context:
         arrays or device uint8 tensors of their bytes; params: the keywords of mp4_params.  Plans first, allocates the exact
         output, runs.  Returns (out device tensor, sample_off ndarray[uint64], sample_size ndarray[uint64],
         frags ndarray[MP4_FRAG], summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x, dtype):
-            if isinstance(x, np.ndarray):
-                b = np.ascontiguousarray(x, dtype=dtype).view(np.uint8).reshape(-1)
-                return t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
-            return x
-        n = len(index) if isinstance(index, np.ndarray) else index.numel() * index.element_size() // NAL_ENTRY.itemsize
-        n_aus = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
-        index, nal_au, au = dv(index, NAL_ENTRY), dv(nal_au, np.uint32), dv(au, ACCESS_UNIT)
-        keep, dts, pts = dv(keep, np.uint8), dv(dts, np.uint64), dv(pts, np.uint64)
+        name = "hbs_mp4_fragment"
+        index, n = self._dv(index, NAL_ENTRY)
+        au, n_aus = self._dv(au, ACCESS_UNIT)
+        nal_au, keep = self._dv(nal_au, np.uint32)[0], self._dv(keep, np.uint8)[0]
+        dts, pts = self._dv(dts, np.uint64)[0], self._dv(pts, np.uint64)[0]
         prm = mp4_params(**params)
         nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        summary = self._zeros()
         args = (stream, nbytes, index, n, nal_au, au, n_aus, prm)
         kw = dict(keep=keep, dts=dts, pts=pts)
-        self._check(self.mp4_fragment_async(*args, None, summary, **kw), "hbs_mp4_fragment")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_fragment: error %d (NAL %d, access unit %d)"
-                           % (int(s["error"]), int(s["reserved"][0]) - 1, int(s["reserved"][1]) - 1))
+        s = self._run(name, self.mp4_fragment_async(*args, None, summary, **kw), summary, " (NAL {0}, access unit {1})")
         need, frags = int(s["stream_bytes"]), int(s["nal_count"])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        so, ss = (t.empty(max(n_aus, 1) * 8, dtype=t.uint8, device=dev) for _ in range(2))
-        fr = t.empty(max(frags, 1) * MP4_FRAG.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.mp4_fragment_async(*args, out, summary, sample_off=so, sample_size=ss, frag=fr, frag_cap=frags, out_cap=need, **kw),
-                    "hbs_mp4_fragment")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_fragment: error %d" % int(s["error"]))
-        return (out[:need], so[: n_aus * 8].cpu().numpy().view(np.uint64).copy(), ss[: n_aus * 8].cpu().numpy().view(np.uint64).copy(),
-                fr[: frags * MP4_FRAG.itemsize].cpu().numpy().view(MP4_FRAG).copy(), s)
+        out = self._empty(max(need, 16))
+        so, ss = (self._empty(max(n_aus, 1) * 8) for _ in range(2))
+        fr = self._empty(max(frags, 1) * MP4_FRAG.itemsize)
+        s = self._run(name, self.mp4_fragment_async(*args, out, summary, sample_off=so, sample_size=ss, frag=fr, frag_cap=frags, out_cap=need, **kw),
+                      summary)
+        return out[:need], _host(so, n_aus, np.uint64), _host(ss, n_aus, np.uint64), _host(fr, frags, MP4_FRAG), s
 
     def mp4_samples_async(self, data, in_bytes, params, summary, seg=None, seg_stride=16, n_segs=0, moof_cap=0, sample_cap=0,
                           sample_off=None, sample_size=None, dts=None, pts=None, sample_flags=None, frag=None):
@@ -1466,13 +1384,10 @@ class Context:
         dts, pts, sample_flags, frag may be None); params is an ndarray[MP4_READ_PARAMS] of one in host memory.  Returns the
         call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=MP4_READ_PARAMS)
-        return self.lib.hbs_mp4_samples(self.h, p(data) if in_bytes else None, int(in_bytes), p(seg), int(seg_stride), int(n_segs),
-                                        params.ctypes.data_as(C.c_void_p) if params is not None else None, int(moof_cap),
-                                        int(sample_cap), p(sample_off), p(sample_size), p(dts), p(pts), p(sample_flags), p(frag),
-                                        p(summary))
+        params, params_p = _rec(params, MP4_READ_PARAMS)
+        return self.lib.hbs_mp4_samples(self.h, _p(data) if in_bytes else None, int(in_bytes), _p(seg), int(seg_stride), int(n_segs),
+                                        params_p, int(moof_cap), int(sample_cap), _p(sample_off), _p(sample_size), _p(dts), _p(pts),
+                                        _p(sample_flags), _p(frag), _p(summary))
 
     def mp4_samples(self, data, seg=None, seg_stride=None, in_bytes=None, moof_cap=None, **params):
         """Convenience: the sample table of the fMP4 segments in `data` (device uint8 tensor).  seg: None (one segment, the
@@ -1481,47 +1396,37 @@ class Context:
         is run again with the count when that was too few); params: the keywords of mp4_read_params.  Plans, allocates the
         exact tables, runs.  Returns (sample_off, sample_size, dts, pts, flags, frags ndarray[MP4_FRAG], summary record), host
         arrays."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
+        name = "hbs_mp4_samples"
         nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
         n_segs = 0
         if isinstance(seg, np.ndarray):
             if seg.dtype == MP4_FRAG:
-                seg_stride, n_segs = MP4_FRAG.itemsize, len(seg)
+                seg_stride = MP4_FRAG.itemsize
             else:
-                seg = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1, 2)
-                seg_stride, n_segs = 16, len(seg)
-            b = seg.view(np.uint8).reshape(-1)
-            seg = t.from_numpy(b.copy()).to(dev) if b.size else t.zeros(64, dtype=t.uint8, device=dev)
+                seg, seg_stride = np.ascontiguousarray(seg, dtype=np.uint64).reshape(-1, 2), 16
+            seg, n_segs = self._dv(seg)
         elif seg is not None:
             seg_stride = 16 if seg_stride is None else int(seg_stride)
-            n_segs = seg.numel() * seg.element_size() // seg_stride
+            n_segs = _holds(seg, seg_stride)
         prm = mp4_read_params(**params)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        summary = self._zeros()
         kw = dict(seg=seg, seg_stride=seg_stride or 16, n_segs=n_segs)
         cap = min(nbytes // 8, 4096) if moof_cap is None else int(moof_cap)
         for _ in range(2):
-            self._check(self.mp4_samples_async(data, nbytes, prm, summary, moof_cap=cap, **kw), "hbs_mp4_samples")
+            self._check(self.mp4_samples_async(data, nbytes, prm, summary, moof_cap=cap, **kw), name)
             s = self.read_summary(summary)
             if int(s["error"]) == -4 and int(s["nal_found"]) > cap:          # HBS_E_CAPACITY: the default was too small
                 cap = int(s["nal_found"])
                 continue
             break
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_samples: error %d (segment %d, moof %d, sample %d)"
-                           % (int(s["error"]), int(s["reserved"][0]) - 1, int(s["reserved"][1]) - 1, int(s["reserved"][2]) - 1))
+        self._raise_on(name, s, " (segment {0}, moof {1}, sample {2})")
         n, m = int(s["nal_count"]), int(s["nal_found"])
-        so, ss, dt, pt = (t.empty(max(n, 1) * 8, dtype=t.uint8, device=dev) for _ in range(4))
-        fl = t.empty(max(n, 1) * 4, dtype=t.uint8, device=dev)
-        fr = t.empty(max(m, 1) * MP4_FRAG.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.mp4_samples_async(data, nbytes, prm, summary, moof_cap=m, sample_cap=n, sample_off=so, sample_size=ss, dts=dt,
-                                           pts=pt, sample_flags=fl, frag=fr, **kw), "hbs_mp4_samples")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_samples: error %d" % int(s["error"]))
-        u64 = lambda x: x[: n * 8].cpu().numpy().view(np.uint64).copy()          # noqa: E731
-        return (u64(so), u64(ss), u64(dt), u64(pt), fl[: n * 4].cpu().numpy().view(np.uint32).copy(),
-                fr[: m * MP4_FRAG.itemsize].cpu().numpy().view(MP4_FRAG).copy(), s)
+        so, ss, dt, pt = (self._empty(max(n, 1) * 8) for _ in range(4))
+        fl = self._empty(max(n, 1) * 4)
+        fr = self._empty(max(m, 1) * MP4_FRAG.itemsize)
+        s = self._run(name, self.mp4_samples_async(data, nbytes, prm, summary, moof_cap=m, sample_cap=n, sample_off=so, sample_size=ss, dts=dt,
+                                                   pts=pt, sample_flags=fl, frag=fr, **kw), summary)
+        return (*(_host(x, n, np.uint64) for x in (so, ss, dt, pt)), _host(fl, n, np.uint32), _host(fr, m, MP4_FRAG), s)
 
     def mp4_stbl_samples_async(self, data, in_bytes, tables, summary, sample_cap=0, sample_off=None, sample_size=None, dts=None, pts=None,
                                sample_flags=None):
@@ -1530,36 +1435,26 @@ class Context:
         is an ndarray[MP4_STBL] of one in host memory (mp4_stbl_find).  Returns the call's return code (0, or HBS_E_ARG for
         arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
-        if tables is not None:
-            tables = np.ascontiguousarray(tables, dtype=MP4_STBL)
-        return self.lib.hbs_mp4_stbl_samples(self.h, p(data), int(in_bytes), tables.ctypes.data_as(C.c_void_p) if tables is not None else None,
-                                             int(sample_cap), p(sample_off), p(sample_size), p(dts), p(pts), p(sample_flags), p(summary))
+        tables, tables_p = _rec(tables, MP4_STBL)
+        return self.lib.hbs_mp4_stbl_samples(self.h, _p(data), int(in_bytes), tables_p, int(sample_cap), _p(sample_off), _p(sample_size),
+                                             _p(dts), _p(pts), _p(sample_flags), _p(summary))
 
     def mp4_stbl_samples(self, data, tables, in_bytes=None):
         """Convenience: the sample table of the progressive MP4 whose table boxes lie in `data` (device uint8 tensor) where
         `tables` (mp4_stbl_find) says.  Plans, allocates the exact tables, runs.  Returns (sample_off, sample_size, dts, pts,
         flags, summary record), host arrays."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
+        name = "hbs_mp4_stbl_samples"
         nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.mp4_stbl_samples_async(data, nbytes, tables, summary), "hbs_mp4_stbl_samples")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_stbl_samples: error %d (box %d)" % (int(s["error"]), int(s["reserved"][0]) - 1))
+        summary = self._zeros()
+        s = self._run(name, self.mp4_stbl_samples_async(data, nbytes, tables, summary), summary, " (box {0})")
         n = int(s["nal_count"])
         if n > 0xFFFFFFFF:
             raise HbsError("hbs_mp4_stbl_samples: %d samples" % n)
-        so, ss, dt, pt = (t.empty(max(n, 1) * 8, dtype=t.uint8, device=dev) for _ in range(4))
-        fl = t.empty(max(n, 1) * 4, dtype=t.uint8, device=dev)
-        self._check(self.mp4_stbl_samples_async(data, nbytes, tables, summary, sample_cap=n, sample_off=so, sample_size=ss, dts=dt, pts=pt,
-                                                sample_flags=fl), "hbs_mp4_stbl_samples")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_stbl_samples: error %d (sample %d)" % (int(s["error"]), int(s["reserved"][2]) - 1))
-        u64 = lambda x: x[: n * 8].cpu().numpy().view(np.uint64).copy()          # noqa: E731
-        return u64(so), u64(ss), u64(dt), u64(pt), fl[: n * 4].cpu().numpy().view(np.uint32).copy(), s
+        so, ss, dt, pt = (self._empty(max(n, 1) * 8) for _ in range(4))
+        fl = self._empty(max(n, 1) * 4)
+        s = self._run(name, self.mp4_stbl_samples_async(data, nbytes, tables, summary, sample_cap=n, sample_off=so, sample_size=ss, dts=dt, pts=pt,
+                                                        sample_flags=fl), summary, " (sample {2})")
+        return (*(_host(x, n, np.uint64) for x in (so, ss, dt, pt)), _host(fl, n, np.uint32), s)
 
     def mp4_stbl_write_async(self, sample_off, sample_size, n_samples, params, summary, dts=None, pts=None, sample_flags=None, out=None,
                              out_cap=0, tables=None):
@@ -1568,32 +1463,22 @@ class Context:
         ndarray[MP4_STBL_WRITE_PARAMS] of one in host memory (mp4_stbl_write_params).  Returns the call's return code (0, or
         HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=MP4_STBL_WRITE_PARAMS)
-        return self.lib.hbs_mp4_stbl_write(self.h, p(sample_off), p(sample_size), int(n_samples), p(dts), p(pts), p(sample_flags),
-                                           params.ctypes.data_as(C.c_void_p) if params is not None else None, p(out), int(out_cap),
-                                           p(tables), p(summary))
+        params, params_p = _rec(params, MP4_STBL_WRITE_PARAMS)
+        return self.lib.hbs_mp4_stbl_write(self.h, _p(sample_off), _p(sample_size), int(n_samples), _p(dts), _p(pts), _p(sample_flags),
+                                           params_p, _p(out), int(out_cap), _p(tables), _p(summary))
 
     def mp4_stbl_write(self, sample_off, sample_size, n_samples, params, dts=None, pts=None, sample_flags=None):
         """Convenience: the sample table boxes of the samples in the device tables.  Plans, allocates the exact output, runs.
         Returns (boxes: device uint8 tensor of exactly T bytes, tables: ndarray[MP4_STBL] of one, summary record)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
-        rec = t.zeros(MP4_STBL.itemsize, dtype=t.uint8, device=dev)
+        name = "hbs_mp4_stbl_write"
+        summary = self._zeros()
+        rec = self._zeros(MP4_STBL.itemsize)
         kw = dict(dts=dts, pts=pts, sample_flags=sample_flags)
-        self._check(self.mp4_stbl_write_async(sample_off, sample_size, n_samples, params, summary, **kw), "hbs_mp4_stbl_write")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_stbl_write: error %d (sample %d, box %d)" % (int(s["error"]), int(s["reserved"][2]) - 1, int(s["reserved"][0]) - 1))
+        s = self._run(name, self.mp4_stbl_write_async(sample_off, sample_size, n_samples, params, summary, **kw), summary, " (sample {2}, box {0})")
         total = int(s["stream_bytes"])
-        out = t.empty(total, dtype=t.uint8, device=dev)
-        self._check(self.mp4_stbl_write_async(sample_off, sample_size, n_samples, params, summary, out=out, out_cap=total, tables=rec, **kw),
-                    "hbs_mp4_stbl_write")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_mp4_stbl_write: error %d" % int(s["error"]))
+        out = self._empty(total)
+        s = self._run(name, self.mp4_stbl_write_async(sample_off, sample_size, n_samples, params, summary, out=out, out_cap=total, tables=rec, **kw),
+                      summary)
         return out, rec.cpu().numpy().view(MP4_STBL).copy(), s
 
     # ---- access units -----------------------------------------------------------------
@@ -1603,37 +1488,24 @@ class Context:
         summary are device tensors (structs, nal_au, carry_out may be None; au None: plan only); carry is an ndarray[AU_CARRY]
         of one (host memory) or None.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
-        if carry is not None:
-            carry = np.ascontiguousarray(carry, dtype=AU_CARRY)
-        return self.lib.hbs_access_units(self.h, p(index), p(parsed), p(compact), p(structs), int(n_nals),
-                                         carry.ctypes.data_as(C.c_void_p) if carry is not None else None,
-                                         p(au), int(au_cap), p(nal_au), p(carry_out), p(summary))
+        carry, carry_p = _rec(carry, AU_CARRY)
+        return self.lib.hbs_access_units(self.h, _p(index), _p(parsed), _p(compact), _p(structs), int(n_nals), carry_p,
+                                         _p(au), int(au_cap), _p(nal_au), _p(carry_out), _p(summary))
 
     def access_units(self, index, parsed, compact, structs, n_nals, carry=None):
         """Plan, allocate, run.  index / parsed / compact: device uint8 tensors of the records (or host ndarrays of them),
         structs: the struct arena (device tensor) or None.  Returns (au ndarray[ACCESS_UNIT], nal_au ndarray[uint32],
         summary record, carry_out ndarray[AU_CARRY] of one)."""
-        t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x):
-            if isinstance(x, np.ndarray):
-                return t.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to(dev) if x.size else t.zeros(64, dtype=t.uint8, device=dev)
-            return x
-        index, parsed, compact = dv(index), dv(parsed), dv(compact)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.access_units_async(index, parsed, compact, structs, n_nals, None, 0, None, None, summary, carry), "hbs_access_units")
-        aus = int(self.read_summary(summary)["nal_count"])
-        au = t.empty(max(aus, 1) * ACCESS_UNIT.itemsize, dtype=t.uint8, device=dev)
-        nal_au = t.empty(max(n_nals, 1), dtype=t.int32, device=dev)
-        carry_out = t.zeros(AU_CARRY.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.access_units_async(index, parsed, compact, structs, n_nals, au, aus, nal_au, carry_out, summary, carry), "hbs_access_units")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_access_units: error %d" % int(s["error"]))
-        return (au[: aus * ACCESS_UNIT.itemsize].cpu().numpy().view(ACCESS_UNIT).copy(), nal_au[:n_nals].cpu().numpy().view(np.uint32).copy(),
-                s, carry_out.cpu().numpy().view(AU_CARRY).copy())
+        name = "hbs_access_units"
+        index, parsed, compact = (self._dv(x)[0] for x in (index, parsed, compact))
+        summary = self._zeros()
+        self._check(self.access_units_async(index, parsed, compact, structs, n_nals, None, 0, None, None, summary, carry), name)
+        aus = int(self.read_summary(summary)["nal_count"])          # (the run reports what the plan found wrong as well)
+        au = self._empty(max(aus, 1) * ACCESS_UNIT.itemsize)
+        nal_au = self.torch.empty(max(n_nals, 1), dtype=self.torch.int32, device=au.device)
+        carry_out = self._zeros(AU_CARRY.itemsize)
+        s = self._run(name, self.access_units_async(index, parsed, compact, structs, n_nals, au, aus, nal_au, carry_out, summary, carry), summary)
+        return _host(au, aus, ACCESS_UNIT), nal_au[:n_nals].cpu().numpy().view(np.uint32).copy(), s, carry_out.cpu().numpy().view(AU_CARRY).copy()
 
     def au_times_async(self, au, n_aus, params, summary, dts=None, pts=None, order=None, display=None):
         """Enqueue hbs_au_times on the current torch stream.  au / summary / dts / pts / order / display are device tensors (each
@@ -1641,31 +1513,22 @@ class Context:
         tensor); params is an ndarray[AU_TIMES_PARAMS] of one in host memory.  Returns the call's return code (0, or HBS_E_ARG
         for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
-        if params is not None:
-            params = np.ascontiguousarray(params, dtype=AU_TIMES_PARAMS)
-        return self.lib.hbs_au_times(self.h, p(au) if n_aus else None, int(n_aus),
-                                     params.ctypes.data_as(C.c_void_p) if params is not None else None,
-                                     p(dts), p(pts), p(order), p(display), p(summary))
+        params, params_p = _rec(params, AU_TIMES_PARAMS)
+        return self.lib.hbs_au_times(self.h, _p(au) if n_aus else None, int(n_aus), params_p, _p(dts), _p(pts), _p(order), _p(display),
+                                     _p(summary))
 
     def au_times(self, au, tick=1, base_time=0, delay=None, flags=0):
         """Convenience: decode and presentation times of the access units `au` (ndarray[ACCESS_UNIT] or a device uint8 tensor of
         the records).  Returns (dts, pts, order, display, summary): device tensors (int64 views of the uint64 times, int32 of the
         uint32 slots) of one entry per AU, and the summary record."""
         t = self.torch
-        dev = t.device("cuda", self.device)
-        n = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
-        if isinstance(au, np.ndarray):
-            au = t.from_numpy(np.ascontiguousarray(au).view(np.uint8).reshape(-1).copy()).to(dev) if n else None
+        au, n = self._dv(au, ACCESS_UNIT)
         prm = au_times_params(tick, base_time, delay, flags)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
-        dts, pts = (t.empty(max(n, 1), dtype=t.int64, device=dev) for _ in range(2))
-        order, display = (t.empty(max(n, 1), dtype=t.int32, device=dev) for _ in range(2))
-        self._check(self.au_times_async(au, n, prm, summary, dts, pts, order, display), "hbs_au_times")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_au_times: error %d (access unit %d reorders across more than %d others)"
-                           % (int(s["error"]), int(s["reserved"][0]) - 1, AUT_MAX_SPAN))
+        summary = self._zeros()
+        dts, pts = (t.empty(max(n, 1), dtype=t.int64, device=summary.device) for _ in range(2))
+        order, display = (t.empty(max(n, 1), dtype=t.int32, device=summary.device) for _ in range(2))
+        s = self._run("hbs_au_times", self.au_times_async(au, n, prm, summary, dts, pts, order, display), summary,
+                      " (access unit {0} reorders across more than %d others)" % AUT_MAX_SPAN)
         return dts[:n], pts[:n], order[:n], display[:n], s
 
     def au_insert_async(self, stream, stream_bytes, index, parsed, n_nals, au, nal_au, n_aus, first_au, au_count, flags,
@@ -1674,13 +1537,12 @@ class Context:
         plan only; index_out, nal_src, nal_au_out, au_out may be None); index_cap: entries each per-NAL table has room for.
         Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
         if out_cap is None:
-            out_cap = out.numel() if out is not None else 0
-        return self.lib.hbs_au_insert(self.h, p(stream) if stream_bytes else None, int(stream_bytes), p(index) if n_nals else None,
-                                      p(parsed) if n_nals else None, int(n_nals), p(au) if n_aus else None,
-                                      p(nal_au) if n_aus and n_nals else None, int(n_aus), int(first_au), int(au_count), int(flags),
-                                      p(out), int(out_cap), p(index_out), p(nal_src), p(nal_au_out), int(index_cap), p(au_out), p(summary))
+            out_cap = _holds(out)
+        return self.lib.hbs_au_insert(self.h, _p(stream) if stream_bytes else None, int(stream_bytes), _p(index) if n_nals else None,
+                                      _p(parsed) if n_nals else None, int(n_nals), _p(au) if n_aus else None,
+                                      _p(nal_au) if n_aus and n_nals else None, int(n_aus), int(first_au), int(au_count), int(flags),
+                                      _p(out), int(out_cap), _p(index_out), _p(nal_src), _p(nal_au_out), int(index_cap), _p(au_out), _p(summary))
 
     def au_insert(self, stream, index, parsed, n_nals, au, nal_au, first_au=0, au_count=None, flags=AUINS_AUD | AUINS_PARAM_SETS,
                   stream_bytes=None):
@@ -1688,45 +1550,33 @@ class Context:
         `stream` (device uint8 tensor).  index / parsed / au / nal_au: host ndarrays of the records or device tensors of them.
         Plans first, allocates the exact outputs, runs.  Returns (out, index_out, nal_src, nal_au_out, au_out, summary): device
         tensors (uint8 views of the records; int32 for the two number tables) cut to what was written, and the summary record."""
+        name = "hbs_au_insert"
         t = self.torch
-        dev = t.device("cuda", self.device)
-
-        def dv(x):
-            if isinstance(x, np.ndarray):
-                return t.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).to(dev) if x.size else t.zeros(64, dtype=t.uint8, device=dev)
-            return x
-        n_aus = len(au) if isinstance(au, np.ndarray) else au.numel() * au.element_size() // ACCESS_UNIT.itemsize
-        index, parsed, au, nal_au = dv(index), dv(parsed), dv(au), dv(nal_au)
+        au, n_aus = self._dv(au, ACCESS_UNIT)
+        index, parsed, nal_au = (self._dv(x)[0] for x in (index, parsed, nal_au))
         if au_count is None:
             au_count = max(n_aus - first_au, 0)
         nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
-        summary = t.zeros(SUMMARY.itemsize, dtype=t.uint8, device=dev)
+        summary = self._zeros()
         args = (stream, nbytes, index, parsed, n_nals, au, nal_au, n_aus, first_au, au_count, flags)
-        self._check(self.au_insert_async(*args, None, None, None, None, None, summary), "hbs_au_insert")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_au_insert: error %d" % int(s["error"]))
+        s = self._run(name, self.au_insert_async(*args, None, None, None, None, None, summary), summary)
         need, m, r = int(s["stream_bytes"]), int(s["nal_count"]), int(s["reserved"][2])
-        out = t.empty(max(need, 16), dtype=t.uint8, device=dev)
-        index_out = t.empty(max(m, 1) * NAL_ENTRY.itemsize, dtype=t.uint8, device=dev)
-        nal_src, nal_au_out = (t.empty(max(m, 1), dtype=t.int32, device=dev) for _ in range(2))
-        au_out = t.empty(max(r, 1) * ACCESS_UNIT.itemsize, dtype=t.uint8, device=dev)
-        self._check(self.au_insert_async(*args, out, index_out, nal_src, nal_au_out, au_out, summary, out_cap=need, index_cap=m), "hbs_au_insert")
-        s = self.read_summary(summary)
-        if int(s["error"]) != 0:
-            raise HbsError("hbs_au_insert: error %d" % int(s["error"]))
+        out = self._empty(max(need, 16))
+        index_out = self._empty(max(m, 1) * NAL_ENTRY.itemsize)
+        nal_src, nal_au_out = (t.empty(max(m, 1), dtype=t.int32, device=out.device) for _ in range(2))
+        au_out = self._empty(max(r, 1) * ACCESS_UNIT.itemsize)
+        s = self._run(name, self.au_insert_async(*args, out, index_out, nal_src, nal_au_out, au_out, summary, out_cap=need, index_cap=m), summary)
         return out[:need], index_out[: m * NAL_ENTRY.itemsize], nal_src[:m], nal_au_out[:m], au_out[: r * ACCESS_UNIT.itemsize], s
 
     def au_keep_async(self, nal_au, parsed, n_nals, first_au, au_count, keep, param_sets=False):
         """Enqueue hbs_au_keep: keep (device uint8 tensor of n_nals) becomes the mask hbs_filter_annexb takes as d_keep."""
         self._bind_stream()
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None          # noqa: E731
-        self._check(self.lib.hbs_au_keep(self.h, p(nal_au), p(parsed), int(n_nals), int(first_au), int(au_count),
-                                         AUKEEP_PARAM_SETS if param_sets else 0, p(keep)), "hbs_au_keep")
+        self._check(self.lib.hbs_au_keep(self.h, _p(nal_au), _p(parsed), int(n_nals), int(first_au), int(au_count),
+                                         AUKEEP_PARAM_SETS if param_sets else 0, _p(keep)), "hbs_au_keep")
 
     def au_keep(self, nal_au, parsed, n_nals, first_au, au_count, param_sets=False):
         """-> device uint8 tensor of n_nals: 1 for the NALs of AUs [first_au, first_au + au_count) (and the parameter sets in force)"""
-        t = self.torch
-        keep = t.empty(max(n_nals, 1), dtype=t.uint8, device=t.device("cuda", self.device))
+        keep = self._empty(max(n_nals, 1))
         self.au_keep_async(nal_au, parsed, n_nals, first_au, au_count, keep, param_sets)
         return keep[:n_nals]
+

@@ -89,9 +89,9 @@ struct hbs_ctx {
     Buf buf[kBufs];
     uint64_t ahead_tiles;               /* 192 KiB tiles buf[kAhead] is laid out for */
     /* optional timing of the dominant kernel */
-    int timing; hipEvent_t ev0, ev1; int ev_valid;        /* ev0 / ev1: the slot of the ring the last call used */
+    int timing; int ev_valid;                             /* ev_valid: a timed call has taken a slot since timing was switched on */
     hipEvent_t ring0[kTimingRing], ring1[kTimingRing];    /* event pairs of the last kTimingRing timed calls */
-    unsigned long long timed_calls;
+    unsigned long long timed_calls;                       /* the last one used slot (timed_calls - 1) % kTimingRing */
     char err[256];
 };
 
@@ -104,6 +104,19 @@ int fail(hbs_ctx* c, hipError_t e, const char* what)
 }
 
 bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+/* a call's pointers, grouped by the alignment they must have (null is aligned): true, with `msg` as the error's text, when one
+ * of them is not */
+using Ptrs = std::initializer_list<const void*>;
+bool misaligned_refused(hbs_ctx* c, const char* msg, Ptrs by16, Ptrs by8, Ptrs by4 = {})
+{
+    bool bad = false;
+    for (const void* p : by16) bad = bad || misaligned(p, 15);
+    for (const void* p : by8) bad = bad || misaligned(p, 7);
+    for (const void* p : by4) bad = bad || misaligned(p, 3);
+    if (bad) snprintf(c->err, sizeof(c->err), "%s", msg);
+    return bad;
+}
 
 /* a call whose out_cap sizes its scratch and grid: true, with the error's text, when it asks for more than kOutCapMax */
 bool out_cap_refused(hbs_ctx* c, const void* d_out, uint64_t out_cap)
@@ -150,9 +163,23 @@ int ensure_zeros(hbs_ctx* c)
 void take_timing_slot(hbs_ctx* c, hipEvent_t* begin, hipEvent_t* end)
 {
     const int slot = (int)(c->timed_calls % kTimingRing);
-    *begin = c->ev0 = c->ring0[slot]; *end = c->ev1 = c->ring1[slot];
+    *begin = c->ring0[slot]; *end = c->ring1[slot];
     c->timed_calls += 1;
     c->ev_valid = 1;
+}
+
+/* The tail of a plan-and-copy call, behind its argument checks and hipSetDevice: the scratch carved into `a` by the call's lay_*
+ * (a failed allocation returns at once and takes no slot), then a slot of the timing ring around all of the call's kernels, then
+ * the launch.  `name`: the launcher's, for hbs_last_error. */
+template <class Args>
+int carve_and_launch(hbs_ctx* c, Buf& scratch, const char* what, Args& a, void (*lay)(hbs::Carver&, Args&),
+                     hipError_t (*launch)(const Args&, hipStream_t), const char* name)
+{
+    const int rc = carve(c, scratch, what, [&](hbs::Carver& w) { lay(w, a); });
+    if (rc < 0) return rc;
+    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);
+    const hipError_t e = launch(a, c->stream);
+    return e == hipSuccess ? 0 : fail(c, e, name);
 }
 
 /* what each scan kernel launches: what the GPU holds less the slots left free, under the HBS_GRID_BLOCKS debugging cap (a ceiling
@@ -359,14 +386,7 @@ int hbs_ctx_kernel_ms_back(hbs_ctx* c, int back, float* ms)
     return e == hipSuccess ? 0 : fail(c, e, "hipEventElapsedTime");
 }
 
-int hbs_ctx_kernel_ms(hbs_ctx* c, float* ms)
-{
-    if (!c || !ms || !c->ev_valid) return HBS_E_ARG;
-    hipError_t e = hipEventSynchronize(c->ev1);
-    if (e != hipSuccess) return fail(c, e, "hipEventSynchronize");
-    e = hipEventElapsedTime(ms, c->ev0, c->ev1);
-    return e == hipSuccess ? 0 : fail(c, e, "hipEventElapsedTime");
-}
+int hbs_ctx_kernel_ms(hbs_ctx* c, float* ms) { return hbs_ctx_kernel_ms_back(c, 0, ms); }
 
 /* The scan kernels are persistent: their workgroups fill the GPU (the event-sparse kernel's 512 use every register), so a kernel
  * of another stream -- RCCL's, in the index gather of the multi-GPU path -- finds no CU until the scan ends, and a "pipelined"
@@ -610,10 +630,8 @@ int hbs_filter_annexb(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes
     static_assert(sizeof(hbs_nal_filter) == 24, "hbs_nal_filter layout");
     if (!c || !d_summary || (rule == nullptr) == (d_keep == nullptr)) return HBS_E_ARG;
     if (n_nals && (!d_index || (stream_bytes && !d_stream))) return HBS_E_ARG;
-    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_index, 7) || misaligned(d_index_out, 7)) {
-        snprintf(c->err, sizeof(c->err), "stream/output pointers must be 16-byte aligned, index pointers 8-byte aligned");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "stream/output pointers must be 16-byte aligned, index pointers 8-byte aligned",
+                           {d_stream, d_out}, {d_index, d_index_out})) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     const uint64_t reach = d_out ? (out_cap < stream_bytes ? out_cap : stream_bytes) : 0;    /* the output is at most this long */
     hbs::FilterArgs a;
@@ -623,11 +641,7 @@ int hbs_filter_annexb(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes
     a.keep = d_keep;
     a.out_cap = out_cap; a.index_out = d_index_out; a.summary = d_summary;
     a.t.src = d_stream; a.t.out = d_out; a.t.tiles = hbs::piece_tiles(reach);
-    const int rc = carve(c, c->buf[kFws], "hipMalloc(filter scratch)", [&](hbs::Carver& w) { hbs::lay_filter(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_filter_annexb(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_filter_annexb");
+    return carve_and_launch(c, c->buf[kFws], "hipMalloc(filter scratch)", a, hbs::lay_filter, hbs::launch_filter_annexb, "launch_filter_annexb");
 }
 
 int hbs_annexb_to_lenpref(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
@@ -637,11 +651,8 @@ int hbs_annexb_to_lenpref(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_b
 {
     if (!c || !d_summary || (length_size != 1 && length_size != 2 && length_size != 4)) return HBS_E_ARG;
     if (n_nals && (!d_index || (stream_bytes && !d_stream))) return HBS_E_ARG;
-    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_index, 7) ||
-        misaligned(d_index_out, 7) || misaligned(d_sample_off, 7) || misaligned(d_nal_au, 3)) {
-        snprintf(c->err, sizeof(c->err), "stream/output/summary pointers must be 16-byte aligned, index and sample table 8-byte, AU numbers 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "stream/output/summary pointers must be 16-byte aligned, index and sample table 8-byte, AU numbers 4-byte",
+                           {d_stream, d_out, d_summary}, {d_index, d_index_out, d_sample_off}, {d_nal_au})) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::A2lArgs a;
     memset(&a, 0, sizeof(a));
@@ -651,11 +662,7 @@ int hbs_annexb_to_lenpref(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_b
     a.t.src = d_stream; a.t.out = d_out; a.t.prefix = (uint32_t)length_size; a.t.prefix_is_length = 1;
     const uint64_t most = stream_bytes + n_nals * (uint64_t)length_size;                    /* the output is at most this long */
     a.t.tiles = d_out ? hbs::piece_tiles(out_cap < most ? out_cap : most) : 0;
-    const int rc = carve(c, c->buf[kLws], "hipMalloc(lenpref scratch)", [&](hbs::Carver& w) { hbs::lay_a2l(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_annexb_to_lenpref(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_annexb_to_lenpref");
+    return carve_and_launch(c, c->buf[kLws], "hipMalloc(lenpref scratch)", a, hbs::lay_a2l, hbs::launch_annexb_to_lenpref, "launch_annexb_to_lenpref");
 }
 
 int hbs_lenpref_to_annexb(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, int length_size,
@@ -666,11 +673,8 @@ int hbs_lenpref_to_annexb(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, in
     if (!c || !d_summary || (length_size != 1 && length_size != 2 && length_size != 4) ||
         (startcode_bytes != 3 && startcode_bytes != 4)) return HBS_E_ARG;
     if (n_samples && (!d_sample_off || !d_sample_size || (in_bytes && !d_in))) return HBS_E_ARG;
-    if (misaligned(d_in, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_sample_off, 7) ||
-        misaligned(d_sample_size, 7) || misaligned(d_sample_off_out, 7)) {
-        snprintf(c->err, sizeof(c->err), "input/output/summary pointers must be 16-byte aligned, sample tables 8-byte aligned");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "input/output/summary pointers must be 16-byte aligned, sample tables 8-byte aligned",
+                           {d_in, d_out, d_summary}, {d_sample_off, d_sample_size, d_sample_off_out})) return HBS_E_ARG;
     if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::L2aArgs a;
@@ -685,11 +689,7 @@ int hbs_lenpref_to_annexb(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, in
     a.sample_off_out = reinterpret_cast<unsigned long long*>(d_sample_off_out); a.summary = d_summary;
     a.t.src = d_in; a.t.out = d_out; a.t.prefix = (uint32_t)startcode_bytes; a.t.prefix_is_length = 0;
     a.t.tiles = d_out ? hbs::piece_tiles(out_cap) : 0;              /* (samples may overlap: the input's size bounds nothing; out_cap is bounded above) */
-    const int rc = carve(c, c->buf[kLws], "hipMalloc(lenpref scratch)", [&](hbs::Carver& w) { hbs::lay_l2a(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_lenpref_to_annexb(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_lenpref_to_annexb");
+    return carve_and_launch(c, c->buf[kLws], "hipMalloc(lenpref scratch)", a, hbs::lay_l2a, hbs::launch_lenpref_to_annexb, "launch_lenpref_to_annexb");
 }
 
 int hbs_ts_demux(hbs_ctx* c, const uint8_t* d_ts, uint64_t ts_bytes, int packet_bytes, int pid,
@@ -698,21 +698,15 @@ int hbs_ts_demux(hbs_ctx* c, const uint8_t* d_ts, uint64_t ts_bytes, int packet_
     static_assert(sizeof(hbs_ts_pes) == 32 && sizeof(hbs_ts_packet) == 48, "hbs_ts_pes / hbs_ts_packet layout");
     if (!c || !d_summary || !hbs::ts_packet_bytes_ok(packet_bytes) || pid < 0 || pid > 8191) return HBS_E_ARG;
     if (ts_bytes % (uint64_t)packet_bytes || ts_bytes / (uint64_t)packet_bytes > 0xFFFFFFFFull || (ts_bytes && !d_ts)) return HBS_E_ARG;
-    if (misaligned(d_ts, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_pes, 7)) {
-        snprintf(c->err, sizeof(c->err), "transport stream/output/summary pointers must be 16-byte aligned, the PES table 8-byte aligned");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "transport stream/output/summary pointers must be 16-byte aligned, the PES table 8-byte aligned",
+                           {d_ts, d_out, d_summary}, {d_pes})) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::TsArgs a;
     memset(&a, 0, sizeof(a));
     a.ts = d_ts; a.n = ts_bytes; a.packets = ts_bytes / (uint64_t)packet_bytes;
     a.B = (uint32_t)packet_bytes; a.lead = hbs::ts_lead(packet_bytes); a.pid = pid;
     a.out = d_out; a.out_cap = out_cap; a.pes = d_pes; a.pes_cap = pes_cap; a.summary = d_summary;
-    const int rc = carve(c, c->buf[kTws], "hipMalloc(transport stream scratch)", [&](hbs::Carver& w) { hbs::lay_ts(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_ts_demux(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_ts_demux");
+    return carve_and_launch(c, c->buf[kTws], "hipMalloc(transport stream scratch)", a, hbs::lay_ts, hbs::launch_ts_demux, "launch_ts_demux");
 }
 
 int hbs_ts_mux(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
@@ -722,11 +716,8 @@ int hbs_ts_mux(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     static_assert(sizeof(hbs_ts_mux_params) == 48 && sizeof(hbs_access_unit) == 64, "hbs_ts_mux_params / hbs_access_unit layout");
     if (!c || !d_summary || !hbs::tsm_params_ok(params) || n_aus > 0xFFFFFFFFull) return HBS_E_ARG;
     if (n_aus && (!d_au || (stream_bytes && !d_stream))) return HBS_E_ARG;
-    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_au, 15) || misaligned(d_summary, 15) ||
-        misaligned(d_pts, 7) || misaligned(d_dts, 7) || misaligned(d_au_packet, 3)) {
-        snprintf(c->err, sizeof(c->err), "stream/output/AU table/summary pointers must be 16-byte aligned, the times 8-byte, the packet numbers 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "stream/output/AU table/summary pointers must be 16-byte aligned, the times 8-byte, the packet numbers 4-byte",
+                           {d_stream, d_out, d_au, d_summary}, {d_pts, d_dts}, {d_au_packet})) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::TsmArgs a;
     memset(&a, 0, sizeof(a));
@@ -742,11 +733,7 @@ int hbs_ts_mux(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     const uint64_t fit = out_cap / a.B, most = hbs::tsm_packet_bound(n_aus, stream_bytes);
     const uint64_t reach = d_out && n_aus ? (fit < most ? fit : most) : 0;
     a.copy_blocks = (reach + hbs::kTsmPacketsPerBlock - 1) / hbs::kTsmPacketsPerBlock;
-    const int rc = carve(c, c->buf[kMws], "hipMalloc(transport mux scratch)", [&](hbs::Carver& w) { hbs::lay_tsm(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_ts_mux(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_ts_mux");
+    return carve_and_launch(c, c->buf[kMws], "hipMalloc(transport mux scratch)", a, hbs::lay_tsm, hbs::launch_ts_mux, "launch_ts_mux");
 }
 
 int hbs_rtp_pack(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
@@ -757,11 +744,8 @@ int hbs_rtp_pack(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     static_assert(sizeof(hbs_rtp_params) == 32 && sizeof(hbs_rtp_packet) == 72 && sizeof(hbs_nal_entry) == 32, "hbs_rtp_params / hbs_rtp_packet layout");
     if (!c || !d_summary || !hbs::rtp_params_ok(params) || n_nals > 0xFFFFFFFFull) return HBS_E_ARG;
     if (n_nals && (!d_index || !d_stream)) return HBS_E_ARG;
-    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_index, 7) ||
-        misaligned(d_pts, 7) || misaligned(d_nal_off, 7) || misaligned(d_nal_packet, 7) || misaligned(d_nal_au, 3)) {
-        snprintf(c->err, sizeof(c->err), "stream/output/summary pointers must be 16-byte aligned, index, times and the two tables 8-byte, AU numbers 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "stream/output/summary pointers must be 16-byte aligned, index, times and the two tables 8-byte, AU numbers 4-byte",
+                           {d_stream, d_out, d_summary}, {d_index, d_pts, d_nal_off, d_nal_packet}, {d_nal_au})) return HBS_E_ARG;
     if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::RtpArgs a;
@@ -774,11 +758,7 @@ int hbs_rtp_pack(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     /* the copy's grid: the tiles out_cap has room for, and no more than the call can make */
     const uint64_t most = hbs::rtp_output_bound(n_nals, stream_bytes, a.q);
     a.tiles = d_out && n_nals ? hbs::rtp_tiles(out_cap < most ? out_cap : most) : 0;
-    const int rc = carve(c, c->buf[kRws], "hipMalloc(RTP scratch)", [&](hbs::Carver& w) { hbs::lay_rtp(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_rtp_pack(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_pack");
+    return carve_and_launch(c, c->buf[kRws], "hipMalloc(RTP scratch)", a, hbs::lay_rtp, hbs::launch_rtp_pack, "launch_rtp_pack");
 }
 
 int hbs_rtp_unpack(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
@@ -790,11 +770,8 @@ int hbs_rtp_unpack(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
     static_assert(sizeof(hbs_rtp_unpack_params) == 16, "hbs_rtp_unpack_params layout");
     if (!c || !d_summary || !hbs::rtpu_params_ok(params) || n_packets > 0xFFFFFFFFull) return HBS_E_ARG;
     if (n_packets && (!d_pkt_off || !d_pkt_size || (in_bytes && !d_in))) return HBS_E_ARG;
-    if (misaligned(d_in, 15) || misaligned(d_out, 15) || misaligned(d_summary, 15) || misaligned(d_pkt_off, 7) || misaligned(d_pkt_size, 7) ||
-        misaligned(d_index_out, 7) || misaligned(d_au_ts_out, 7) || misaligned(d_nal_au_out, 3)) {
-        snprintf(c->err, sizeof(c->err), "input/output/summary pointers must be 16-byte aligned, packet tables, output index and AU times 8-byte, AU numbers 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "input/output/summary pointers must be 16-byte aligned, packet tables, output index and AU times 8-byte, AU numbers 4-byte",
+                           {d_in, d_out, d_summary}, {d_pkt_off, d_pkt_size, d_index_out, d_au_ts_out}, {d_nal_au_out})) return HBS_E_ARG;
     if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::RtpuArgs a;
@@ -807,11 +784,7 @@ int hbs_rtp_unpack(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
     if (d_out) { a.index_out = d_index_out; a.nal_au_out = d_nal_au_out; a.au_ts_out = reinterpret_cast<unsigned long long*>(d_au_ts_out); }
     a.t.src = d_in; a.t.out = d_out;
     a.t.tiles = d_out ? hbs::piece_tiles(out_cap) : 0;              /* (packets may overlap: the input's size bounds nothing; out_cap is bounded above) */
-    const int rc = carve(c, c->buf[kUws], "hipMalloc(RTP unpack scratch)", [&](hbs::Carver& w) { hbs::lay_rtpu(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_rtp_unpack(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_unpack");
+    return carve_and_launch(c, c->buf[kUws], "hipMalloc(RTP unpack scratch)", a, hbs::lay_rtpu, hbs::launch_rtp_unpack, "launch_rtp_unpack");
 }
 
 int hbs_rtp_order(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
@@ -823,11 +796,8 @@ int hbs_rtp_order(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
     if (!c || !d_summary || !hbs::rtpo_params_ok(params) || n_packets > hbs::kRtpoMaxPackets) return HBS_E_ARG;
     if (n_packets && (!d_pkt_off || !d_pkt_size || (in_bytes && !d_in))) return HBS_E_ARG;
     if ((d_off_out == nullptr) != (d_size_out == nullptr) || (!d_off_out && (d_src_out || d_ext_out))) return HBS_E_ARG;
-    if (misaligned(d_in, 15) || misaligned(d_summary, 15) || misaligned(d_pkt_off, 7) || misaligned(d_pkt_size, 7) ||
-        misaligned(d_off_out, 7) || misaligned(d_size_out, 7) || misaligned(d_ext_out, 7) || misaligned(d_src_out, 3)) {
-        snprintf(c->err, sizeof(c->err), "input/summary pointers must be 16-byte aligned, packet tables and 64-bit output tables 8-byte, table positions 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "input/summary pointers must be 16-byte aligned, packet tables and 64-bit output tables 8-byte, table positions 4-byte",
+                           {d_in, d_summary}, {d_pkt_off, d_pkt_size, d_off_out, d_size_out, d_ext_out}, {d_src_out})) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::RtpoArgs a;
     memset(&a, 0, sizeof(a));
@@ -838,11 +808,7 @@ int hbs_rtp_order(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes,
     a.off_out = reinterpret_cast<unsigned long long*>(d_off_out); a.size_out = reinterpret_cast<unsigned long long*>(d_size_out);
     a.src_out = d_src_out; a.ext_out = reinterpret_cast<unsigned long long*>(d_ext_out);
     a.out_cap = out_cap; a.summary = d_summary;
-    const int rc = carve(c, c->buf[kOws], "hipMalloc(RTP order scratch)", [&](hbs::Carver& w) { hbs::lay_rtpo(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_rtp_order(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_rtp_order");
+    return carve_and_launch(c, c->buf[kOws], "hipMalloc(RTP order scratch)", a, hbs::lay_rtpo, hbs::launch_rtp_order, "launch_rtp_order");
 }
 
 int hbs_mp4_fragment(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
@@ -857,12 +823,8 @@ int hbs_mp4_fragment(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     if (n_nals ? (!d_index || !d_nal_au || (stream_bytes && !d_stream)) : n_aus != 0) return HBS_E_ARG;
     if (n_aus && !d_au) return HBS_E_ARG;
     if ((d_sample_off == nullptr) != (d_sample_size == nullptr)) return HBS_E_ARG;
-    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_au, 15) || misaligned(d_frag, 15) || misaligned(d_summary, 15) ||
-        misaligned(d_index, 7) || misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_sample_off, 7) || misaligned(d_sample_size, 7) ||
-        misaligned(d_nal_au, 3)) {
-        snprintf(c->err, sizeof(c->err), "stream/output/AU table/fragment table/summary pointers must be 16-byte aligned, index, times and sample tables 8-byte, AU numbers 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "stream/output/AU table/fragment table/summary pointers must be 16-byte aligned, index, times and sample tables 8-byte, AU numbers 4-byte",
+                           {d_stream, d_out, d_au, d_frag, d_summary}, {d_index, d_dts, d_pts, d_sample_off, d_sample_size}, {d_nal_au})) return HBS_E_ARG;
     if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::Mp4Args a;
@@ -880,11 +842,7 @@ int hbs_mp4_fragment(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     /* the copy's grid: the tiles out_cap has room for, and no more than the call can make */
     const uint64_t most = hbs::mp4_output_bound(n_nals, n_aus, stream_bytes, a.L);
     a.tiles = d_out && n_nals ? hbs::mp4_tiles(out_cap < most ? out_cap : most) : 0;
-    const int rc = carve(c, c->buf[kPws], "hipMalloc(MP4 scratch)", [&](hbs::Carver& w) { hbs::lay_mp4(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_mp4_fragment(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_fragment");
+    return carve_and_launch(c, c->buf[kPws], "hipMalloc(MP4 scratch)", a, hbs::lay_mp4, hbs::launch_mp4_fragment, "launch_mp4_fragment");
 }
 
 int hbs_mp4_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const void* d_seg, uint64_t seg_stride, uint64_t n_segs,
@@ -898,11 +856,8 @@ int hbs_mp4_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const vo
     if ((d_sample_off == nullptr) != (d_sample_size == nullptr)) return HBS_E_ARG;
     if (!d_sample_off && (d_dts || d_pts || d_sample_flags || d_frag)) return HBS_E_ARG;
     if (moof_cap > 0xFFFFFFFFull || (d_sample_off && sample_cap > 0xFFFFFFFFull)) return HBS_E_ARG;
-    if (misaligned(d_in, 15) || misaligned(d_frag, 15) || misaligned(d_summary, 15) || misaligned(d_seg, 7) || misaligned(d_sample_off, 7) ||
-        misaligned(d_sample_size, 7) || misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_sample_flags, 3)) {
-        snprintf(c->err, sizeof(c->err), "input/fragment table/summary pointers must be 16-byte aligned, segment table and 64-bit sample tables 8-byte, sample flags 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "input/fragment table/summary pointers must be 16-byte aligned, segment table and 64-bit sample tables 8-byte, sample flags 4-byte",
+                           {d_in, d_frag, d_summary}, {d_seg, d_sample_off, d_sample_size, d_dts, d_pts}, {d_sample_flags})) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::Mp4RdArgs a;
     memset(&a, 0, sizeof(a));
@@ -916,11 +871,7 @@ int hbs_mp4_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const vo
         a.dts = reinterpret_cast<unsigned long long*>(d_dts); a.pts = reinterpret_cast<unsigned long long*>(d_pts);
         a.sample_flags = d_sample_flags; a.frag = d_frag;
     }
-    const int rc = carve(c, c->buf[kQws], "hipMalloc(MP4 read scratch)", [&](hbs::Carver& w) { hbs::lay_mp4rd(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_mp4_samples(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_samples");
+    return carve_and_launch(c, c->buf[kQws], "hipMalloc(MP4 read scratch)", a, hbs::lay_mp4rd, hbs::launch_mp4_samples, "launch_mp4_samples");
 }
 
 int hbs_mp4_stbl_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const hbs_mp4_stbl* tables, uint64_t sample_cap,
@@ -932,11 +883,8 @@ int hbs_mp4_stbl_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, con
     if ((d_sample_off == nullptr) != (d_sample_size == nullptr)) return HBS_E_ARG;
     if (!d_sample_off && (d_dts || d_pts || d_sample_flags)) return HBS_E_ARG;
     if (d_sample_off && sample_cap > 0xFFFFFFFFull) return HBS_E_ARG;
-    if (misaligned(d_in, 15) || misaligned(d_summary, 15) || misaligned(d_sample_off, 7) || misaligned(d_sample_size, 7) || misaligned(d_dts, 7) ||
-        misaligned(d_pts, 7) || misaligned(d_sample_flags, 3)) {
-        snprintf(c->err, sizeof(c->err), "input/summary pointers must be 16-byte aligned, the 64-bit sample tables 8-byte, sample flags 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "input/summary pointers must be 16-byte aligned, the 64-bit sample tables 8-byte, sample flags 4-byte",
+                           {d_in, d_summary}, {d_sample_off, d_sample_size, d_dts, d_pts}, {d_sample_flags})) return HBS_E_ARG;
     hbs::StblArgs a;
     memset(&a, 0, sizeof(a));
     const hbs_mp4_box_ref* ref[hbs::kStBoxes] = {&tables->stsz, &tables->stco, &tables->stsc, &tables->stts, &tables->ctts, &tables->stss};
@@ -960,11 +908,7 @@ int hbs_mp4_stbl_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, con
         a.dts = reinterpret_cast<unsigned long long*>(d_dts); a.pts = reinterpret_cast<unsigned long long*>(d_pts);
         a.sample_flags = d_sample_flags;
     }
-    const int rc = carve(c, c->buf[kSws], "hipMalloc(MP4 sample table scratch)", [&](hbs::Carver& w) { hbs::lay_mp4stbl(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_mp4_stbl_samples(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_stbl_samples");
+    return carve_and_launch(c, c->buf[kSws], "hipMalloc(MP4 sample table scratch)", a, hbs::lay_mp4stbl, hbs::launch_mp4_stbl_samples, "launch_mp4_stbl_samples");
 }
 
 int hbs_mp4_stbl_write(hbs_ctx* c, const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples, const uint64_t* d_dts,
@@ -974,11 +918,8 @@ int hbs_mp4_stbl_write(hbs_ctx* c, const uint64_t* d_sample_off, const uint64_t*
     static_assert(sizeof(hbs_mp4_stbl_write_params) == 32, "hbs_mp4_stbl_write_params layout");
     if (!c || !d_summary || !hbs::mp4_stbl_write_params_ok(params) || n_samples > 0xFFFFFFFFull) return HBS_E_ARG;
     if (n_samples && (!d_sample_off || !d_sample_size)) return HBS_E_ARG;
-    if (misaligned(d_out, 15) || misaligned(d_tables, 15) || misaligned(d_summary, 15) || misaligned(d_sample_off, 7) || misaligned(d_sample_size, 7) ||
-        misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_sample_flags, 3)) {
-        snprintf(c->err, sizeof(c->err), "output/box record/summary pointers must be 16-byte aligned, the 64-bit sample tables 8-byte, sample flags 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "output/box record/summary pointers must be 16-byte aligned, the 64-bit sample tables 8-byte, sample flags 4-byte",
+                           {d_out, d_tables, d_summary}, {d_sample_off, d_sample_size, d_dts, d_pts}, {d_sample_flags})) return HBS_E_ARG;
     if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::StblwArgs a;
@@ -987,11 +928,7 @@ int hbs_mp4_stbl_write(hbs_ctx* c, const uint64_t* d_sample_off, const uint64_t*
     a.in.sample_duration = params->sample_duration; a.in.base_time = params->base_time; a.in.data_offset = params->data_offset;
     a.co64 = (params->flags & HBS_MP4_STBL_CO64) != 0u; a.max_chunk = params->max_chunk_samples;
     a.out = d_out; a.out_cap = out_cap; a.tables = d_tables; a.summary = d_summary;
-    const int rc = carve(c, c->buf[kVws], "hipMalloc(MP4 sample table writer scratch)", [&](hbs::Carver& w) { hbs::lay_mp4stblw(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_mp4_stbl_write(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_mp4_stbl_write");
+    return carve_and_launch(c, c->buf[kVws], "hipMalloc(MP4 sample table writer scratch)", a, hbs::lay_mp4stblw, hbs::launch_mp4_stbl_write, "launch_mp4_stbl_write");
 }
 
 int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
@@ -1005,12 +942,8 @@ int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     if (!c || !d_summary || (flags & ~hbs::kAuinsFlags) || n_nals > 0xFFFFFFFFull || n_aus > 0xFFFFFFFFull) return HBS_E_ARG;
     if (n_nals && (!d_index || !d_parsed || (stream_bytes && !d_stream))) return HBS_E_ARG;
     if (n_aus && (!d_au || (n_nals && !d_nal_au))) return HBS_E_ARG;
-    if (misaligned(d_stream, 15) || misaligned(d_out, 15) || misaligned(d_index, 15) || misaligned(d_parsed, 15) || misaligned(d_au, 15) ||
-        misaligned(d_au_out, 15) || misaligned(d_summary, 15) || misaligned(d_index_out, 7) || misaligned(d_nal_au, 3) ||
-        misaligned(d_nal_src, 3) || misaligned(d_nal_au_out, 3)) {
-        snprintf(c->err, sizeof(c->err), "stream/output/index/parsed/AU table/summary pointers must be 16-byte aligned, the output index 8-byte, the per-NAL numbers 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "stream/output/index/parsed/AU table/summary pointers must be 16-byte aligned, the output index 8-byte, the per-NAL numbers 4-byte",
+                           {d_stream, d_out, d_index, d_parsed, d_au, d_au_out, d_summary}, {d_index_out}, {d_nal_au, d_nal_src, d_nal_au_out})) return HBS_E_ARG;
     if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::AuinsArgs a;
@@ -1023,11 +956,7 @@ int hbs_au_insert(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     a.flags = flags; a.out_cap = out_cap; a.index_cap = index_cap; a.summary = d_summary;
     if (d_out) { a.index_out = d_index_out; a.nal_src = d_nal_src; a.nal_au_out = d_nal_au_out; a.au_out = d_au_out; }
     a.t.src = d_stream; a.t.out = d_out; a.t.tiles = d_out && a.cnt ? hbs::piece_tiles(out_cap) : 0;
-    const int rc = carve(c, c->buf[kIws], "hipMalloc(AU insert scratch)", [&](hbs::Carver& w) { hbs::lay_auins(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_au_insert(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_au_insert");
+    return carve_and_launch(c, c->buf[kIws], "hipMalloc(AU insert scratch)", a, hbs::lay_auins, hbs::launch_au_insert, "launch_au_insert");
 }
 
 int hbs_aud_nal_host(int temporal_id_plus1, uint32_t slice_types, uint8_t out[7]) { return hbs::auins_aud_host(temporal_id_plus1, slice_types, out); }
@@ -1055,11 +984,7 @@ int hbs_access_units(hbs_ctx* c, const hbs_nal_entry* d_index, const hbs_parsed_
     a.n_nals = n_nals; a.sps_off = hbs_au_sps_poc_offset();
     if (initial) a.initial = *initial;
     a.au = d_au; a.au_cap = au_cap; a.nal_au = d_au ? d_nal_au : nullptr; a.carry_out = d_carry_out; a.summary = d_summary;
-    const int rc = carve(c, c->buf[kAws], "hipMalloc(access unit scratch)", [&](hbs::Carver& w) { hbs::lay_access_units(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_access_units(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_access_units");
+    return carve_and_launch(c, c->buf[kAws], "hipMalloc(access unit scratch)", a, hbs::lay_access_units, hbs::launch_access_units, "launch_access_units");
 }
 
 int hbs_au_keep(hbs_ctx* c, const uint32_t* d_nal_au, const hbs_parsed_nal* d_parsed, uint64_t n_nals,
@@ -1084,11 +1009,8 @@ int hbs_au_times(hbs_ctx* c, const hbs_access_unit* d_au, uint64_t n_aus, const 
 {
     static_assert(sizeof(hbs_au_times_params) == 32 && sizeof(hbs_access_unit) == 64, "hbs_au_times layouts");
     if (!c || !d_summary || !hbs::aut_params_ok(params, n_aus) || (n_aus && !d_au)) return HBS_E_ARG;
-    if (misaligned(d_au, 15) || misaligned(d_summary, 15) || misaligned(d_dts, 7) || misaligned(d_pts, 7) || misaligned(d_order, 3) ||
-        misaligned(d_display, 3)) {
-        snprintf(c->err, sizeof(c->err), "AU table/summary pointers must be 16-byte aligned, the times 8-byte, order and display 4-byte");
-        return HBS_E_ARG;
-    }
+    if (misaligned_refused(c, "AU table/summary pointers must be 16-byte aligned, the times 8-byte, order and display 4-byte",
+                           {d_au, d_summary}, {d_dts, d_pts}, {d_order, d_display})) return HBS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
     hbs::AutArgs a;
     memset(&a, 0, sizeof(a));
@@ -1097,11 +1019,7 @@ int hbs_au_times(hbs_ctx* c, const hbs_access_unit* d_au, uint64_t n_aus, const 
     a.delay_given = (params->flags & HBS_AUT_DELAY_GIVEN) ? params->delay : 0u;
     a.dts = reinterpret_cast<unsigned long long*>(d_dts); a.pts = reinterpret_cast<unsigned long long*>(d_pts);
     a.order = d_order; a.display = d_display; a.summary = d_summary;
-    const int rc = carve(c, c->buf[kXws], "hipMalloc(AU times scratch)", [&](hbs::Carver& w) { hbs::lay_au_times(w, a); });
-    if (rc < 0) return rc;
-    if (c->timing) take_timing_slot(c, &a.ev_begin, &a.ev_end);      /* all of the call's kernels */
-    const hipError_t e = hbs::launch_au_times(a, c->stream);
-    return e == hipSuccess ? 0 : fail(c, e, "launch_au_times");
+    return carve_and_launch(c, c->buf[kXws], "hipMalloc(AU times scratch)", a, hbs::lay_au_times, hbs::launch_au_times, "launch_au_times");
 }
 
 int hbs_synth_rbsp(hbs_ctx* c, uint64_t seed, uint64_t n_nals, int mode,

@@ -373,25 +373,47 @@ def test_every_timed_call_takes_a_slot(video):
         assert ctx.kernel_ms() == ms[0] and ctx.kernel_ms_back(0) == ms[0]
         with pytest.raises(Exception):
             ctx.kernel_ms_back(3)
-        # the five framing and transport calls take a slot each time, a plan and a call without input included: their
-        # launchers record both events around whatever they launch, be it the one-workgroup scan kernel alone
+        # the five framing and transport calls, the RTP and MP4 calls and hbs_au_times take a slot each time, a plan and a call
+        # without input included: their launchers record both events around whatever they launch, be it the one-workgroup scan
+        # kernel alone (hbs_capi.hip takes the slot in one place for all of them)
         history = list(ms)                                   # the last call first
 
-        def timed(c, plan=False):
-            step(ctx, c, plan)
+        def timed(what, call_it):
+            call_it()
             now = ctx.kernel_ms()
-            assert now >= 0 and ctx.kernel_ms_back(0) == now, (c, plan, now)
+            assert now >= 0 and ctx.kernel_ms_back(0) == now, (what, now)
             for back, m in enumerate(history):               # the earlier calls' values, one slot further back each
-                assert ctx.kernel_ms_back(back + 1) == m, (c, plan, back)
+                assert ctx.kernel_ms_back(back + 1) == m, (what, back)
             with pytest.raises(Exception):
                 ctx.kernel_ms_back(len(history) + 1)
             history.insert(0, now)
             return now
-        for call in S.CALLS:
-            assert timed(S.case(call, "small")) > 0, call
-        for call in S.CALLS:
-            timed(S.case(call, "small"), plan=True)
-            timed(S.empty(call))
-        print("framing and transport calls: ms", history[:-3])
+        calls = S.CALLS + S.CALLS2
+        for call in calls:
+            assert timed(call, lambda: step(ctx, S.case(call, "small"))) > 0, call
+        for call in calls:
+            timed((call, "plan"), lambda: step(ctx, S.case(call, "small"), plan=True))
+            timed((call, "empty"), lambda: step(ctx, S.empty(call)))
+        # hbs_au_times: one small call on the AU table hbs_access_units makes of the fabricated records (its plan and its run
+        # take a slot each), then a plan (no output) and a call of no AUs
+        import hevcbitstream_amd as hbs
+
+        def enqueued(rc):
+            assert rc == 0
+            sm = ctx.read_summary(summary)
+            assert int(sm["error"]) == 0, sm
+            return sm
+        found = []
+        timed(("access units", "plan"), lambda: found.append(enqueued(ctx.access_units_async(*records, n, None, 0, None, None, summary))))
+        n_aus = int(found[0]["nal_count"])
+        assert n_aus > 1
+        au = torch.empty(n_aus * hbs.ACCESS_UNIT.itemsize, dtype=torch.uint8, device="cuda")
+        assert timed("access units", lambda: enqueued(ctx.access_units_async(*records, n, au, n_aus, None, None, summary))) > 0
+        prm = hbs.au_times_params()
+        dts, pts = (torch.empty(n_aus, dtype=torch.int64, device="cuda") for _ in range(2))
+        for what, args in (("small", (n_aus, prm, summary, dts, pts)), ("plan", (n_aus, prm, summary)), ("empty", (0, prm, summary, dts, pts))):
+            ms = timed(("au_times", what), lambda: enqueued(ctx.au_times_async(au, *args)))
+            assert ms > 0 or what != "small"
+        print("device calls: ms", history[:-3])
     finally:
         ctx.close()
