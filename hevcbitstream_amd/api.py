@@ -32,6 +32,12 @@ AUKEEP_PARAM_SETS = 1
 AU_TIMES_PARAMS = np.dtype([("flags", "<u4"), ("tick", "<u4"), ("base_time", "<u8"), ("delay", "<u4"), ("reserved", "<u4", (3,))])
 AUT_MAX_SPAN = 1024
 AUT_DELAY_GIVEN, AUT_WRAP33 = 1, 2
+# layouts of hbs_cenc_subsample, hbs_cenc_plan_params and hbs_cenc_params; the flag and the scheme of the two hbs_cenc_* calls
+CENC_SUBSAMPLE = np.dtype([("clear", "<u4"), ("protect", "<u4")])
+CENC_PLAN_PARAMS = np.dtype([("length_size", "<i4"), ("flags", "<u4"), ("clear_lead", "<u4"), ("reserved", "<u4")])
+CENC_PARAMS = np.dtype([("key", "u1", (16,)), ("iv0", "u1", (16,)), ("scheme", "<u4"), ("iv_mode", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+CENC_ALIGN16 = 1
+CENC_SCHEME_CENC = 0x63656E63
 # flags of hbs_au_insert
 AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST = 1, 2, 4
 # layout of hbs_ts_pes / hbs_ts_packet, the packet classes and the flags of hbs_ts_demux
@@ -114,6 +120,7 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_comm_unique_id", "hbs_comm_create", "hbs_comm_adopt", "hbs_comm_destroy", "hbs_comm_rank", "hbs_comm_world", "hbs_comm_reserve_hint", "hbs_parse_headers_compact", "hbs_parse_materialize", "hbs_index_parse_compact", "hbs_gather_parts", "hbs_index_parse", "hbs_ctx_reserve_workgroups",
            "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
            "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset", "hbs_au_times",
+           "hbs_cenc_subsamples", "hbs_cenc_crypt",
            "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb",
            "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
@@ -284,6 +291,12 @@ def load_library():
                                   C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.hbs_au_times.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hbs_au_times.restype = C.c_int
+    lib.hbs_cenc_subsamples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.hbs_cenc_subsamples.restype = C.c_int
+    lib.hbs_cenc_crypt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+    lib.hbs_cenc_crypt.restype = C.c_int
     lib.hbs_mp4_fragment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_void_p]
@@ -443,6 +456,25 @@ def au_times_params(tick=1, base_time=0, delay=None, flags=0):
     p = np.zeros(1, dtype=AU_TIMES_PARAMS)
     p["flags"], p["tick"], p["base_time"] = flags | (AUT_DELAY_GIVEN if delay is not None else 0), tick, base_time
     p["delay"] = 0 if delay is None else delay
+    return p
+
+
+def cenc_plan_params(length_size=4, flags=0, clear_lead=96):
+    """an hbs_cenc_plan_params record (ndarray[CENC_PLAN_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=CENC_PLAN_PARAMS)
+    p[0] = (length_size, flags, clear_lead, 0)
+    return p
+
+
+def cenc_params(key, iv0=None, iv_mode=None, scheme=CENC_SCHEME_CENC):
+    """an hbs_cenc_params record (ndarray[CENC_PARAMS] of one, host memory).  key: 16 bytes; iv0: None, or 8 or 16 bytes (the
+    first 8 count), which sets iv_mode 1 unless iv_mode says otherwise"""
+    p = np.zeros(1, dtype=CENC_PARAMS)
+    p["key"][0] = np.frombuffer(bytes(key), dtype=np.uint8)
+    if iv0 is not None:
+        b = bytes(iv0)
+        p["iv0"][0][: len(b)] = np.frombuffer(b, dtype=np.uint8)
+    p["scheme"], p["iv_mode"] = scheme, (0 if iv0 is None else 1) if iv_mode is None else iv_mode
     return p
 
 
@@ -1530,6 +1562,71 @@ class Context:
         s = self._run("hbs_au_times", self.au_times_async(au, n, prm, summary, dts, pts, order, display), summary,
                       " (access unit {0} reorders across more than %d others)" % AUT_MAX_SPAN)
         return dts[:n], pts[:n], order[:n], display[:n], s
+
+    # ---- Common Encryption: the subsample table, AES-128-CTR in place ------------------------------
+
+    def cenc_subsamples_async(self, stream, stream_bytes, index, n_nals, nal_au, n_aus, params, sub_first, sub, summary, keep=None,
+                              payload_off=None, sub_cap=None):
+        """Enqueue hbs_cenc_subsamples on the current torch stream.  stream / index / nal_au / sub_first / sub / summary / keep /
+        payload_off are device tensors (sub None: plan only; keep, payload_off may be None); params is an
+        ndarray[CENC_PLAN_PARAMS] of one in host memory.  Returns the call's return code."""
+        self._bind_stream()
+        if sub_cap is None:
+            sub_cap = _holds(sub, CENC_SUBSAMPLE.itemsize)
+        params, params_p = _rec(params, CENC_PLAN_PARAMS)
+        return self.lib.hbs_cenc_subsamples(self.h, _p(stream) if stream_bytes else None, int(stream_bytes), _p(index) if n_nals else None,
+                                            int(n_nals), _p(keep), _p(nal_au) if n_nals else None, int(n_aus), _p(payload_off), params_p,
+                                            _p(sub_first), _p(sub), int(sub_cap), _p(summary))
+
+    def cenc_subsamples(self, stream, index, nal_au, n_aus, keep=None, payload_off=None, stream_bytes=None, **params):
+        """Convenience: the subsample table of the samples hbs_mp4_fragment / hbs_annexb_to_lenpref make of `stream` (device
+        uint8 tensor).  index / nal_au / keep / payload_off: host ndarrays or device tensors of their bytes; params: the
+        keywords of cenc_plan_params.  Plans first, allocates the exact table, runs.  Returns (sub_first device tensor of
+        (n_aus + 1) * 8 bytes, sub device tensor of the entries' bytes, summary record)."""
+        name = "hbs_cenc_subsamples"
+        d_idx, n = self._dv(index, NAL_ENTRY, empty=False)
+        d_au, _ = self._dv(nal_au, np.uint32, empty=False)
+        d_keep, _ = self._dv(keep, np.uint8)
+        d_po, _ = self._dv(payload_off, np.uint64)
+        nbytes = int(stream.numel()) if stream_bytes is None else int(stream_bytes)
+        prm = cenc_plan_params(**params)
+        summary = self._zeros()
+        sub_first = self._empty((int(n_aus) + 1) * 8)
+        args = (stream, nbytes, d_idx, n, d_au, n_aus, prm, sub_first)
+        s = self._run(name, self.cenc_subsamples_async(*args, None, summary, keep=d_keep, payload_off=d_po), summary, " (NAL {0})")
+        need = int(s["nal_count"])
+        sub = self._empty(max(need, 2) * CENC_SUBSAMPLE.itemsize)
+        s = self._run(name, self.cenc_subsamples_async(*args, sub, summary, keep=d_keep, payload_off=d_po, sub_cap=need), summary, " (NAL {0})")
+        return sub_first, sub[: need * CENC_SUBSAMPLE.itemsize], s
+
+    def cenc_crypt_async(self, data, data_bytes, sample_off, sample_size, n_samples, sub_first, sub, iv, params, summary):
+        """Enqueue hbs_cenc_crypt on the current torch stream: AES-128-CTR in place over the protected ranges of the samples of
+        `data`.  Everything but the counts and params (an ndarray[CENC_PARAMS] of one in host memory) is a device tensor; iv
+        may be None with iv_mode 1.  Returns the call's return code."""
+        self._bind_stream()
+        params, params_p = _rec(params, CENC_PARAMS)
+        on = bool(n_samples)
+        return self.lib.hbs_cenc_crypt(self.h, _p(data) if data_bytes else None, int(data_bytes), _p(sample_off) if on else None,
+                                       _p(sample_size) if on else None, int(n_samples), _p(sub_first) if on else None,
+                                       _p(sub) if on else None, _p(iv), params_p, _p(summary))
+
+    def cenc_crypt(self, data, sample_off, sample_size, sub_first, sub, key, iv=None, iv0=None, data_bytes=None):
+        """Convenience: encrypts or decrypts (the same thing) the samples of `data` (device uint8 tensor) in place.  The four
+        tables: host ndarrays (uint64, uint64, uint64, CENC_SUBSAMPLE) or device tensors of their bytes.  iv: n_samples x 16
+        bytes (host or device), read; or iv0 (8 bytes): sequential IVs, and the blocks used are returned.  Returns (iv device
+        tensor, summary record)."""
+        name = "hbs_cenc_crypt"
+        d_off, d_size, n = self._offsets_and_sizes(name, sample_off, sample_size, "sample")
+        d_first, _ = self._dv(sub_first, np.uint64)
+        d_sub, _ = self._dv(sub, CENC_SUBSAMPLE)
+        d_iv, _ = self._dv(iv, np.uint8)
+        if d_iv is None:
+            d_iv = self._empty(max(n, 1) * 16)
+        nbytes = int(data.numel()) if data_bytes is None else int(data_bytes)
+        summary = self._zeros()
+        prm = cenc_params(key, iv0=iv0 if iv is None else None)
+        s = self._run(name, self.cenc_crypt_async(data, nbytes, d_off, d_size, n, d_first, d_sub, d_iv, prm, summary), summary, " (sample {0})")
+        return d_iv[: n * 16], s
 
     def au_insert_async(self, stream, stream_bytes, index, parsed, n_nals, au, nal_au, n_aus, first_au, au_count, flags,
                         out, index_out, nal_src, nal_au_out, au_out, summary, out_cap=None, index_cap=0):

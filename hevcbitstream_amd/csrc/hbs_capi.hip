@@ -21,6 +21,7 @@
 #include "hbs_lenpref.h"
 #include "hbs_au.h"
 #include "hbs_autimes.h"
+#include "hbs_cenc.h"
 #include "hbs_ts.h"
 #include "hbs_tsmux.h"
 #include "hbs_auins.h"
@@ -55,8 +56,10 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kQws    hbs_mp4_samples' scratch
  * kSws    hbs_mp4_stbl_samples' scratch
  * kVws    hbs_mp4_stbl_write's scratch
- * kXws    hbs_au_times' scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kBufs };
+ * kXws    hbs_au_times' scratch
+ * kCws    hbs_cenc_subsamples' scratch
+ * kYws    hbs_cenc_crypt's scratch (tables about the samples and the entries; the key is never in it) */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kCws, kYws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -1020,6 +1023,52 @@ int hbs_au_times(hbs_ctx* c, const hbs_access_unit* d_au, uint64_t n_aus, const 
     a.dts = reinterpret_cast<unsigned long long*>(d_dts); a.pts = reinterpret_cast<unsigned long long*>(d_pts);
     a.order = d_order; a.display = d_display; a.summary = d_summary;
     return carve_and_launch(c, c->buf[kXws], "hipMalloc(AU times scratch)", a, hbs::lay_au_times, hbs::launch_au_times, "launch_au_times");
+}
+
+int hbs_cenc_subsamples(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                        const hbs_nal_entry* d_index, uint64_t n_nals, const uint8_t* d_keep,
+                        const uint32_t* d_nal_au, uint64_t n_aus, const uint64_t* d_payload_off,
+                        const hbs_cenc_plan_params* params,
+                        uint64_t* d_sub_first, hbs_cenc_subsample* d_sub, uint64_t sub_cap, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_cenc_plan_params) == 16 && sizeof(hbs_cenc_subsample) == 8 && sizeof(hbs_cenc_params) == 48, "hbs_cenc_* layouts");
+    if (!c || !d_summary || !d_sub_first || !hbs::cenc_plan_params_ok(params) || n_nals > 0xFFFFFFFFull || n_aus > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_nals ? (!d_index || !d_nal_au || (stream_bytes && !d_stream)) : n_aus != 0) return HBS_E_ARG;
+    if (misaligned_refused(c, "stream/summary pointers must be 16-byte aligned, index, payload offsets and the two subsample tables 8-byte, AU numbers 4-byte",
+                           {d_stream, d_summary}, {d_index, d_payload_off, d_sub_first, d_sub}, {d_nal_au})) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::CencPlanArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_stream; a.n = stream_bytes; a.index = d_index; a.n_nals = n_nals; a.keep = d_keep;
+    a.nal_au = d_nal_au; a.n_aus = n_aus; a.payload_off = reinterpret_cast<const unsigned long long*>(d_payload_off);
+    a.L = (uint32_t)params->length_size; a.flags = params->flags; a.clear_lead = params->clear_lead;
+    a.sub_first = reinterpret_cast<unsigned long long*>(d_sub_first); a.sub = d_sub; a.sub_cap = sub_cap; a.summary = d_summary;
+    return carve_and_launch(c, c->buf[kCws], "hipMalloc(CENC plan scratch)", a, hbs::lay_cenc_plan, hbs::launch_cenc_subsamples, "launch_cenc_subsamples");
+}
+
+int hbs_cenc_crypt(hbs_ctx* c, uint8_t* d_data, uint64_t data_bytes,
+                   const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
+                   const uint64_t* d_sub_first, const hbs_cenc_subsample* d_sub,
+                   uint8_t* d_iv, const hbs_cenc_params* params, hbs_summary* d_summary)
+{
+    if (!c || !d_summary || !hbs::cenc_params_ok(params) || n_samples > 0xFFFFFFFFull || (data_bytes && !d_data)) return HBS_E_ARG;
+    if (n_samples && (!d_sample_off || !d_sample_size || !d_sub_first || !d_sub || (params->iv_mode == 0 && !d_iv))) return HBS_E_ARG;
+    if (misaligned_refused(c, "data/IV/summary pointers must be 16-byte aligned, sample and subsample tables 8-byte aligned",
+                           {d_data, d_iv, d_summary}, {d_sample_off, d_sample_size, d_sub_first, d_sub})) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::CencCall a;
+    memset(&a, 0, sizeof(a));
+    a.data = d_data; a.n = data_bytes;
+    a.sample_off = reinterpret_cast<const unsigned long long*>(d_sample_off);
+    a.sample_size = reinterpret_cast<const unsigned long long*>(d_sample_size); a.n_samples = n_samples;
+    a.sub_first = reinterpret_cast<const unsigned long long*>(d_sub_first); a.sub = d_sub;
+    a.iv = d_iv; a.iv_mode = params->iv_mode; a.iv_base = hbs::cenc_be64(params->iv0); a.summary = d_summary;
+    a.tiles = hbs::piece_tiles(data_bytes);            /* the protected bytes are no more than the data (kCencTileBytes is a piece tile) */
+    static_assert(hbs::kCencTileBytes == hbs::kPieceTileBytes, "piece_tiles counts the crypt kernel's tiles");
+    hbs::cenc_expand_key(params->key, a.key);          /* on the host; the round keys travel with the launch */
+    const int rc = carve_and_launch(c, c->buf[kYws], "hipMalloc(CENC scratch)", a, hbs::lay_cenc, hbs::launch_cenc_crypt, "launch_cenc_crypt");
+    memset(&a.key, 0, sizeof(a.key));
+    return rc;
 }
 
 int hbs_synth_rbsp(hbs_ctx* c, uint64_t seed, uint64_t n_nals, int mode,

@@ -114,10 +114,12 @@ typedef struct hbs_ctx hbs_ctx;
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
  *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples,
- *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write, hbs_au_times.
+ *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write, hbs_au_times, hbs_cenc_subsamples, hbs_cenc_crypt.
+ * hbs_cenc_crypt takes its key and iv0 from host memory when it is called: a captured graph replays with the key and iv0 it was
+ * captured with.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
  * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py,
- * tests/test_gpu_mp4_stbl.py, tests/test_gpu_mp4_stbl_write.py and tests/test_gpu_au_times.py replay, no
+ * tests/test_gpu_mp4_stbl.py, tests/test_gpu_mp4_stbl_write.py, tests/test_gpu_au_times.py and tests/test_gpu_cenc.py replay, no
  * more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
@@ -470,7 +472,8 @@ int hbs_lenpref_to_annexb(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, 
  * Alignment: d_stream, d_out, d_au, d_frag, d_summary 16 bytes; d_index, d_dts, d_pts, d_sample_off, d_sample_size 8 bytes;
  * d_nal_au 4 bytes; d_keep any byte.
  * STATED LIMITS: one track; 32-bit mdat and moof sizes; no styp, sidx, prft, emsg, senc or encryption; no edit list (a stream
- * with reordering begins with a positive composition offset).  hbs_mp4_samples, below, reads fragments back.
+ * with reordering begins with a positive composition offset).  hbs_mp4_samples, below, reads fragments back.  (The samples can
+ * be encrypted in place behind this call -- hbs_cenc_subsamples and hbs_cenc_crypt, below -- but no box says so yet.)
  *
  * hbs_mp4_init_host (plain C, no GPU): the init segment for those fragments -- ftyp (iso6, 0, iso6, mp41), then moov with
  * mvhd (rate 0x00010000, volume 0x0100, unity matrix, next_track_ID = track_id + 1), one trak (tkhd flags 3 with
@@ -616,7 +619,8 @@ int64_t hbs_mp4_init_host(const hbs_mp4_init_params* p, int flags,
  * Alignment: d_in, d_frag, d_summary 16 bytes; d_seg and the four 64-bit tables 8 bytes; d_sample_flags 4 bytes.
  * STATED LIMITS: one track a call; a missing tfdt is an error; the "end of the previous traf's data" base is not supported;
  * no encryption (senc, saiz, saio are stepped over; the samples stay as they are); no sidx-driven access (pass the segments);
- * a file without fragments is read by hbs_mp4_stbl_samples, below; one lane walks a segment's chain.
+ * a file without fragments is read by hbs_mp4_stbl_samples, below; one lane walks a segment's chain.  (hbs_cenc_crypt, below,
+ * decrypts samples in place from the tables this call writes, given their subsample table and IVs from elsewhere.)
  *
  * hbs_mp4_init_read_host (plain C, no GPU): the counterpart of hbs_mp4_init_host.  It walks seg[0, n) by the box rule above:
  * moov; its trak boxes in order -- tkhd (version 0 or 1: track_id, width and height, the integer parts), mdia / mdhd (version
@@ -720,7 +724,8 @@ int64_t hbs_mp4_init_read_host(const uint8_t* seg, uint64_t n, uint32_t track_id
  * touches a 16-byte granule that holds no byte of d_in[0, in_bytes); no mdat byte is read; no host synchronisation and no
  * allocation once the scratch has its size.
  * STATED LIMITS: one track a call; no stz2 (compact sample sizes); the edit list is not applied; the sample description index
- * is ignored (one sample entry); no encryption (the samples stay as they are).
+ * is ignored (one sample entry); no encryption (the samples stay as they are; hbs_cenc_crypt, below, works on the tables
+ * this call writes, given the subsample table and IVs from elsewhere).
  */
 #define HBS_MP4_STBL_CO64 1u           /* hbs_mp4_stbl.flags: .stco refers to a co64 (64-bit entries) */
 typedef struct hbs_mp4_box_ref { uint64_t off, bytes; } hbs_mp4_box_ref;  /* the payload behind the box header; bytes == 0: no such box */
@@ -814,7 +819,8 @@ int hbs_mp4_stbl_samples(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
  *   ftyp + moov + mdat   plan first (d_out == NULL) and read T from the summary; the prefix has P bytes; then the real call
  *                        with data_offset = P + T + 8; the file is the prefix, the T bytes, the mdat header, the samples.
  * STATED LIMITS: one track; no edit list (a stream with reordering begins with a positive composition offset); no stz2; no
- * sdtp; one sample entry (every stsc entry names description 1); no encryption.
+ * sdtp; one sample entry (every stsc entry names description 1); no encryption (hbs_cenc_crypt, below, encrypts the samples
+ * in place, but no box written here says so).
  */
 typedef struct hbs_mp4_stbl_write_params {   /* HOST memory, 32 bytes */
     uint32_t flags;              /* HBS_MP4_STBL_CO64: write a co64; otherwise a stco */
@@ -1595,6 +1601,100 @@ int hbs_au_times(hbs_ctx* ctx, const hbs_access_unit* d_au, uint64_t n_aus,
                  uint64_t* d_dts, uint64_t* d_pts,        /* optional, each on its own, n_aus */
                  uint32_t* d_order, uint32_t* d_display,  /* optional, each on its own, n_aus */
                  hbs_summary* d_summary);
+
+/*
+ * ---- Common Encryption (ISO/IEC 23001-7, scheme `cenc`): subsample table and AES-128-CTR in place -------------------------
+ * Two device calls.  hbs_cenc_subsamples writes the subsample table of every sample from tables alone; hbs_cenc_crypt applies
+ * AES-128 in counter mode, in place, to the protected ranges of samples that lie anywhere in a buffer.  Encryption and
+ * decryption are the same call.  NOT written or read: senc, saiz, saio, sinf / tenc, pssh (the records below are in the senc
+ * entry form -- 16-bit clear, 32-bit protected -- so a writer can follow); the schemes cbcs, cens, cbc1 (params->scheme is there
+ * for them; anything but cenc is refused); key rotation (one key a call).
+ *
+ * hbs_cenc_subsamples.  The samples are exactly those of hbs_mp4_fragment / hbs_annexb_to_lenpref: sample a is the kept NALs
+ * k (d_keep NULL: all) with d_nal_au[k] - d_nal_au[0] == a, in index order, each a record of L = params->length_size length
+ * bytes and end - start payload bytes; the index and AU-number rules are hbs_mp4_fragment's (start <= end <= stream_bytes,
+ * start_k >= end_{k-1}, a kept payload fits L bytes, the AU numbers rise by 0 or 1 and the last is d_nal_au[0] + n_aus - 1).
+ * The only stream byte read is the first payload byte b of a kept, non-empty NAL: type = (b >> 1) & 63.
+ *   RULE, per sample: C = 0.  For each kept NAL in order, size = end - start:
+ *     type >= 32 or size == 0     C += L + size.
+ *     type < 32 (a VCL NAL)       its clear lead h = d_payload_off[k] - start with d_payload_off (as hbs_index_parse* wrote it:
+ *                                 the stream offset of the first slice data byte), else min(params->clear_lead, size);
+ *                                 P = size - h; with HBS_CENC_ALIGN16, P mod 16 bytes move from P to h; C += L + h; if P > 0,
+ *                                 emit (C, P) and C = 0.
+ *   At the sample's end a remaining C > 0 is emitted as (C, 0).
+ *   EMIT (C, P): q = max(ceil(C / 65535), 1) - 1 entries (65535, 0), then (C - 65535 q, P).  (0, P) is one entry; an empty sample
+ *   has none.
+ * d_sub_first[a] = the entries of all samples below a; d_sub_first[n_aus] = the total.  d_sub[0, total) are the entries.
+ * d_summary: nal_count = entries, nal_found = n_nals, rbsp_bytes = protected bytes in all, stream_bytes = sample bytes in all
+ * (hbs_mp4_fragment's B(n_aus)), reserved[2] = kept NALs, stop_reason = 0.  error = HBS_E_ARG with reserved[0] = 1 + the lowest
+ * offending NAL for a broken index or AU-number rule, or a kept, non-empty VCL NAL whose d_payload_off[k] is ~0, below start + 2
+ * or above end (a slice the parse did not read must not silently stay clear); the counts mean nothing then.  Else
+ * HBS_E_CAPACITY when, with a d_sub, sub_cap is below the total; the counts are right.  On an error only the summary is
+ * written.  d_sub == NULL: plan only -- the summary and d_sub_first are written.  n_nals == 0 with n_aus == 0 is valid.
+ * Refused with HBS_E_ARG at once, nothing touched: params NULL, a length_size other than 1, 2, 4, unknown flags, reserved != 0,
+ * clear_lead < 2, n_nals or n_aus above 2^32 - 1, n_nals == 0 with n_aus != 0, a missing d_index, d_nal_au or (stream_bytes > 0)
+ * d_stream with n_nals > 0, a missing d_sub_first or d_summary, a misaligned pointer.
+ * Alignment: d_stream, d_summary 16 bytes; d_index, d_payload_off, d_sub_first, d_sub 8 bytes; d_nal_au 4 bytes; d_keep any.
+ * No host synchronisation (HIP graphs, above).  Scratch: the context's workspace, 128 bytes per 2 048 NALs.  The work is
+ * parallel over NALs; the clear runs are a segmented scan, the entry numbers a plain one.
+ *
+ * hbs_cenc_crypt.  Sample s is d_data[off_s, off_s + size_s) with off_s = d_sample_off[s], size_s = d_sample_size[s]: the form
+ * hbs_mp4_fragment, hbs_mp4_samples and hbs_mp4_stbl_samples write.  Its subsamples are d_sub[d_sub_first[s], d_sub_first[s+1]),
+ * laid end to end from off_s: `clear` bytes untouched, then `protect` bytes.
+ *   KEYSTREAM: the protected bytes of a sample, concatenated, are XORed with one continuous keystream: byte j of the
+ *   concatenation with byte j mod 16 of AES-128_key(ctr_s + floor(j / 16)).  ctr_s is the sample's 16-byte counter block,
+ *   big-endian; the addition touches bytes 8..15 only and wraps from FF..FF to 0 with no carry into bytes 0..7.  A keystream
+ *   block may straddle two or more subsamples; no keystream is skipped at a subsample's start.
+ *   iv_mode 0: ctr_s = d_iv[16 s, 16 s + 16) (a caller with 8-byte IVs stores the IV followed by eight zero bytes).
+ *   iv_mode 1: ctr_s = (the big-endian 64-bit value of iv0[0, 8) + s mod 2^64) followed by eight zero bytes; iv0[8, 16) is
+ *   ignored; d_iv, when given, receives the n_samples blocks.
+ * CHECKS, each made before any byte of d_data changes: off_s + size_s <= data_bytes without a wrap; off_s + size_s <= off_(s+1)
+ * (ascending and disjoint: the call is in place); d_sub_first non-decreasing from 0 (and below 2^48); the entries of sample s add
+ * up to exactly size_s; clear <= 65535.  Else error = HBS_E_ARG with reserved[0] = 1 + the lowest offending sample, and nothing
+ * but the summary is written.  (The checks run in three groups -- offsets, sizes and d_sub_first; then clear; then the sums -- and
+ * the sample named is the lowest of the first group that fails: the entries are not read through a d_sub_first that is wrong.)  d_sub must hold d_sub_first[n_samples] entries: that is the caller's word.
+ * d_summary: nal_count = entries read, nal_found = n_samples, rbsp_bytes = bytes XORed, stream_bytes = data_bytes,
+ * stop_reason = 0.  n_samples == 0 is valid.
+ * Refused with HBS_E_ARG at once, nothing touched: params NULL, a scheme other than HBS_CENC_SCHEME_CENC, iv_mode above 1, flags
+ * or reserved != 0, iv_mode 0 without d_iv (n_samples > 0), n_samples above 2^32 - 1, missing tables with n_samples > 0, a
+ * missing d_data with data_bytes > 0, a missing d_summary, a misaligned pointer.
+ * Alignment: d_data, d_iv, d_summary 16 bytes; d_sample_off, d_sample_size, d_sub_first, d_sub 8 bytes.
+ * No byte outside the protected ranges is stored -- not the bytes that share a 16-byte granule with a range's first or last
+ * byte either -- beyond d_iv (iv_mode 1) and the summary; no load touches a granule that holds no byte of d_data[0, data_bytes);
+ * no host synchronisation.  The key is expanded on the host (176 bytes of round keys) and goes to the kernels by value: it is
+ * never stored in the context's scratch or any other device buffer.  Scratch: 16 bytes a sample, 64 per 256 samples, 65 KiB.
+ */
+#define HBS_CENC_ALIGN16      1u            /* hbs_cenc_plan_params.flags: protected ranges are whole 16-byte blocks */
+#define HBS_CENC_SCHEME_CENC  0x63656E63u   /* 'cenc' */
+
+typedef struct hbs_cenc_subsample { uint32_t clear /* <= 65535 */, protect; } hbs_cenc_subsample;   /* 8 bytes */
+
+typedef struct hbs_cenc_plan_params {   /* HOST memory, 16 bytes */
+    int32_t  length_size;   /* 1, 2, 4: as hbs_annexb_to_lenpref */
+    uint32_t flags;         /* HBS_CENC_ALIGN16 */
+    uint32_t clear_lead;    /* with d_payload_off == NULL: payload bytes of a VCL NAL that stay clear (>= 2) */
+    uint32_t reserved;      /* 0 */
+} hbs_cenc_plan_params;
+
+typedef struct hbs_cenc_params {        /* HOST memory, 48 bytes */
+    uint8_t  key[16];
+    uint8_t  iv0[16];       /* iv_mode 1 */
+    uint32_t scheme;        /* HBS_CENC_SCHEME_CENC; anything else: HBS_E_ARG */
+    uint32_t iv_mode;       /* 0: d_iv is read; 1: sequential, d_iv (nullable) is written */
+    uint32_t flags, reserved;   /* 0 */
+} hbs_cenc_params;
+
+int hbs_cenc_subsamples(hbs_ctx* ctx, const uint8_t* d_stream, uint64_t stream_bytes,
+                        const hbs_nal_entry* d_index, uint64_t n_nals, const uint8_t* d_keep /* nullable */,
+                        const uint32_t* d_nal_au, uint64_t n_aus,
+                        const uint64_t* d_payload_off /* nullable: as hbs_index_parse* wrote it */,
+                        const hbs_cenc_plan_params* params,
+                        uint64_t* d_sub_first /* n_aus + 1 */, hbs_cenc_subsample* d_sub /* NULL: plan only */, uint64_t sub_cap,
+                        hbs_summary* d_summary);
+int hbs_cenc_crypt(hbs_ctx* ctx, uint8_t* d_data, uint64_t data_bytes,
+                   const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
+                   const uint64_t* d_sub_first /* n_samples + 1 */, const hbs_cenc_subsample* d_sub,
+                   uint8_t* d_iv /* n_samples x 16 bytes */, const hbs_cenc_params* params, hbs_summary* d_summary);
 
 /*
  * ---- access-unit delimiters and parameter sets in front of access units ---------------------------------------------
