@@ -12,6 +12,7 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   AU_PARAM_SETS, AU_END_OF_SEQ, AUKEEP_PARAM_SETS,
                   AU_TIMES_PARAMS, AUT_MAX_SPAN, AUT_DELAY_GIVEN, AUT_WRAP33, au_times_params,
                   CENC_SUBSAMPLE, CENC_PLAN_PARAMS, CENC_PARAMS, CENC_ALIGN16, CENC_SCHEME_CENC, cenc_plan_params, cenc_params,
+                  CBCS_PARAMS, CBCS_DECRYPT, CBCS_WHOLE_RUNS, cbcs_params,
                   TS_PES, TS_PACKET, TS_FAULT, TS_OTHER, TS_SKIPPED, TS_NO_PAYLOAD, TS_PAYLOAD, TS_PES_START,
                   TS_F_PTS, TS_F_DTS, TS_F_RANDOM_ACCESS, TS_F_DISCONTINUITY, TS_F_DATA_ALIGNED, TS_NO_TIME,
                   STREAM_TYPE_HEVC, ts_packet, ts_find_pid,
@@ -33,6 +34,7 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "AU_PARAM_SETS", "AU_END_OF_SEQ", "AUKEEP_PARAM_SETS",
            "AU_TIMES_PARAMS", "AUT_MAX_SPAN", "AUT_DELAY_GIVEN", "AUT_WRAP33", "au_times_params",
            "CENC_SUBSAMPLE", "CENC_PLAN_PARAMS", "CENC_PARAMS", "CENC_ALIGN16", "CENC_SCHEME_CENC", "cenc_plan_params", "cenc_params",
+           "CBCS_PARAMS", "CBCS_DECRYPT", "CBCS_WHOLE_RUNS", "cbcs_params",
            "TS_PES", "TS_PACKET", "TS_FAULT", "TS_OTHER", "TS_SKIPPED", "TS_NO_PAYLOAD", "TS_PAYLOAD", "TS_PES_START",
            "TS_F_PTS", "TS_F_DTS", "TS_F_RANDOM_ACCESS", "TS_F_DISCONTINUITY", "TS_F_DATA_ALIGNED", "TS_NO_TIME",
            "STREAM_TYPE_HEVC", "ts_packet", "ts_find_pid",

@@ -38,6 +38,11 @@ CENC_PLAN_PARAMS = np.dtype([("length_size", "<i4"), ("flags", "<u4"), ("clear_l
 CENC_PARAMS = np.dtype([("key", "u1", (16,)), ("iv0", "u1", (16,)), ("scheme", "<u4"), ("iv_mode", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 CENC_ALIGN16 = 1
 CENC_SCHEME_CENC = 0x63656E63
+# layout of hbs_cbcs_params and the flags of hbs_cbcs_crypt
+CBCS_PARAMS = np.dtype([("key", "u1", (16,)), ("iv0", "u1", (16,)), ("iv_mode", "<u4"), ("flags", "<u4"), ("crypt_byte_block", "u1"),
+                        ("skip_byte_block", "u1"), ("reserved0", "<u2"), ("reserved1", "<u4")])
+CBCS_DECRYPT = 1
+CBCS_WHOLE_RUNS = 2
 # flags of hbs_au_insert
 AUINS_AUD, AUINS_PARAM_SETS, AUINS_PARAM_SETS_FIRST = 1, 2, 4
 # layout of hbs_ts_pes / hbs_ts_packet, the packet classes and the flags of hbs_ts_demux
@@ -120,7 +125,7 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_comm_unique_id", "hbs_comm_create", "hbs_comm_adopt", "hbs_comm_destroy", "hbs_comm_rank", "hbs_comm_world", "hbs_comm_reserve_hint", "hbs_parse_headers_compact", "hbs_parse_materialize", "hbs_index_parse_compact", "hbs_gather_parts", "hbs_index_parse", "hbs_ctx_reserve_workgroups",
            "hbs_gather_index", "hbs_ctx_device", "hbs_find_cut_host", "hbs_trim_part", "hbs_annexb_bound_gaps", "hbs_ctx_device_bytes", "hbs_ctx_set_ingest_window_max", "hbs_pair_alloc", "hbs_pair_free", "hbs_pair_pool_trim", "hbs_pair_pool_stats", "hbs_parse_headers_state", "hbs_ctx_last_emit_by_tiles", "hbs_ctx_set_device_exclusive",
            "hbs_filter_annexb", "hbs_access_units", "hbs_au_keep", "hbs_au_sps_poc_offset", "hbs_au_times",
-           "hbs_cenc_subsamples", "hbs_cenc_crypt",
+           "hbs_cenc_subsamples", "hbs_cenc_crypt", "hbs_cbcs_crypt",
            "hbs_annexb_to_lenpref", "hbs_lenpref_to_annexb",
            "hbs_ts_demux", "hbs_ts_packet_host", "hbs_ts_find_pid_host",
            "hbs_ts_mux", "hbs_ts_mux_psi_host", "hbs_ts_mux_au_packets_host",
@@ -297,6 +302,9 @@ def load_library():
     lib.hbs_cenc_crypt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]
     lib.hbs_cenc_crypt.restype = C.c_int
+    lib.hbs_cbcs_crypt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+    lib.hbs_cbcs_crypt.restype = C.c_int
     lib.hbs_mp4_fragment.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_void_p]
@@ -475,6 +483,19 @@ def cenc_params(key, iv0=None, iv_mode=None, scheme=CENC_SCHEME_CENC):
         b = bytes(iv0)
         p["iv0"][0][: len(b)] = np.frombuffer(b, dtype=np.uint8)
     p["scheme"], p["iv_mode"] = scheme, (0 if iv0 is None else 1) if iv_mode is None else iv_mode
+    return p
+
+
+def cbcs_params(key, iv0=None, iv_mode=None, flags=0, crypt_byte_block=1, skip_byte_block=9):
+    """an hbs_cbcs_params record (ndarray[CBCS_PARAMS] of one, host memory).  key: 16 bytes; iv0: None, or the 16-byte constant
+    IV, which sets iv_mode 1 unless iv_mode says otherwise; flags: CBCS_DECRYPT | CBCS_WHOLE_RUNS"""
+    p = np.zeros(1, dtype=CBCS_PARAMS)
+    p["key"][0] = np.frombuffer(bytes(key), dtype=np.uint8)
+    if iv0 is not None:
+        b = bytes(iv0)
+        p["iv0"][0][: len(b)] = np.frombuffer(b, dtype=np.uint8)
+    p["iv_mode"], p["flags"] = (0 if iv0 is None else 1) if iv_mode is None else iv_mode, flags
+    p["crypt_byte_block"], p["skip_byte_block"] = crypt_byte_block, skip_byte_block
     return p
 
 
@@ -1627,6 +1648,34 @@ class Context:
         prm = cenc_params(key, iv0=iv0 if iv is None else None)
         s = self._run(name, self.cenc_crypt_async(data, nbytes, d_off, d_size, n, d_first, d_sub, d_iv, prm, summary), summary, " (sample {0})")
         return d_iv[: n * 16], s
+
+    def cbcs_crypt_async(self, data, data_bytes, sample_off, sample_size, n_samples, sub_first, sub, iv, params, summary):
+        """Enqueue hbs_cbcs_crypt on the current torch stream: AES-128-CBC in place over the pattern of crypt blocks of the
+        protected ranges of the samples of `data`; the direction is in params.  Everything but the counts and params (an
+        ndarray[CBCS_PARAMS] of one in host memory) is a device tensor; iv may be None with iv_mode 1.  Returns the call's
+        return code."""
+        self._bind_stream()
+        params, params_p = _rec(params, CBCS_PARAMS)
+        on = bool(n_samples)
+        return self.lib.hbs_cbcs_crypt(self.h, _p(data) if data_bytes else None, int(data_bytes), _p(sample_off) if on else None,
+                                       _p(sample_size) if on else None, int(n_samples), _p(sub_first) if on else None,
+                                       _p(sub) if on else None, _p(iv), params_p, _p(summary))
+
+    def cbcs_crypt(self, data, sample_off, sample_size, sub_first, sub, key, iv=None, iv0=None, decrypt=False, crypt_byte_block=1,
+                   skip_byte_block=9, whole_runs=False, data_bytes=None):
+        """Convenience: encrypts (decrypt=True: decrypts) the samples of `data` (device uint8 tensor) in place, scheme cbcs.  The
+        four tables: host ndarrays (uint64, uint64, uint64, CENC_SUBSAMPLE) or device tensors of their bytes.  iv: n_samples x
+        16 bytes (host or device), or iv0: the constant 16-byte IV of every sample.  Returns the summary record."""
+        name = "hbs_cbcs_crypt"
+        d_off, d_size, n = self._offsets_and_sizes(name, sample_off, sample_size, "sample")
+        d_first, _ = self._dv(sub_first, np.uint64)
+        d_sub, _ = self._dv(sub, CENC_SUBSAMPLE)
+        d_iv, _ = self._dv(iv, np.uint8)
+        nbytes = int(data.numel()) if data_bytes is None else int(data_bytes)
+        summary = self._zeros()
+        prm = cbcs_params(key, iv0=iv0 if iv is None else None, flags=(CBCS_DECRYPT if decrypt else 0) | (CBCS_WHOLE_RUNS if whole_runs else 0),
+                          crypt_byte_block=crypt_byte_block, skip_byte_block=skip_byte_block)
+        return self._run(name, self.cbcs_crypt_async(data, nbytes, d_off, d_size, n, d_first, d_sub, d_iv, prm, summary), summary, " (sample {0})")
 
     def au_insert_async(self, stream, stream_bytes, index, parsed, n_nals, au, nal_au, n_aus, first_au, au_count, flags,
                         out, index_out, nal_src, nal_au_out, au_out, summary, out_cap=None, index_cap=0):

@@ -22,6 +22,7 @@
 #include "hbs_au.h"
 #include "hbs_autimes.h"
 #include "hbs_cenc.h"
+#include "hbs_cbcs.h"
 #include "hbs_ts.h"
 #include "hbs_tsmux.h"
 #include "hbs_auins.h"
@@ -58,7 +59,8 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kVws    hbs_mp4_stbl_write's scratch
  * kXws    hbs_au_times' scratch
  * kCws    hbs_cenc_subsamples' scratch
- * kYws    hbs_cenc_crypt's scratch (tables about the samples and the entries; the key is never in it) */
+ * kYws    hbs_cenc_crypt's scratch (tables about the samples and the entries; the key is never in it); hbs_cbcs_crypt's too: the
+ *         same tables, and the calls of a context are ordered by its one stream */
 enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kCws, kYws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
@@ -1068,6 +1070,34 @@ int hbs_cenc_crypt(hbs_ctx* c, uint8_t* d_data, uint64_t data_bytes,
     hbs::cenc_expand_key(params->key, a.key);          /* on the host; the round keys travel with the launch */
     const int rc = carve_and_launch(c, c->buf[kYws], "hipMalloc(CENC scratch)", a, hbs::lay_cenc, hbs::launch_cenc_crypt, "launch_cenc_crypt");
     memset(&a.key, 0, sizeof(a.key));
+    return rc;
+}
+
+int hbs_cbcs_crypt(hbs_ctx* c, uint8_t* d_data, uint64_t data_bytes,
+                   const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
+                   const uint64_t* d_sub_first, const hbs_cenc_subsample* d_sub,
+                   const uint8_t* d_iv, const hbs_cbcs_params* params, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_cbcs_params) == 48, "hbs_cbcs_params layout");
+    if (!c || !d_summary || !hbs::cbcs_params_ok(params) || n_samples > 0xFFFFFFFFull || (data_bytes && !d_data)) return HBS_E_ARG;
+    if (n_samples && (!d_sample_off || !d_sample_size || !d_sub_first || !d_sub || (params->iv_mode == 0 && !d_iv))) return HBS_E_ARG;
+    if (misaligned_refused(c, "data/IV/summary pointers must be 16-byte aligned, sample and subsample tables 8-byte aligned",
+                           {d_data, d_iv, d_summary}, {d_sample_off, d_sample_size, d_sub_first, d_sub})) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::CbcsCall a;
+    memset(&a, 0, sizeof(a));
+    a.data = d_data; a.n = data_bytes;
+    a.sample_off = reinterpret_cast<const unsigned long long*>(d_sample_off);
+    a.sample_size = reinterpret_cast<const unsigned long long*>(d_sample_size); a.n_samples = n_samples;
+    a.sub_first = reinterpret_cast<const unsigned long long*>(d_sub_first); a.sub = d_sub;
+    a.iv = const_cast<uint8_t*>(d_iv); a.iv_mode = params->iv_mode; a.summary = d_summary;      /* (only read) */
+    a.pattern = hbs::cbcs_pattern(params->crypt_byte_block, params->skip_byte_block, params->flags);
+    a.decrypt = (params->flags & HBS_CBCS_DECRYPT) ? 1u : 0u;
+    hbs::cbcs_load_be(params->iv0, a.iv0);
+    hbs::cenc_expand_key(params->key, a.ek);           /* on the host; the round keys travel with the launch */
+    hbs::cbcs_expand_dec_key(a.ek, a.dk);
+    const int rc = carve_and_launch(c, c->buf[kYws], "hipMalloc(CENC scratch)", a, hbs::lay_cbcs, hbs::launch_cbcs_crypt, "launch_cbcs_crypt");
+    memset(&a.ek, 0, sizeof(a.ek)); memset(&a.dk, 0, sizeof(a.dk));
     return rc;
 }
 

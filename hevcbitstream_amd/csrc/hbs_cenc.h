@@ -241,7 +241,7 @@ struct CencArgs {
 enum : int { kCencCErr = 0, kCencCEntries = 1, kCencCProt = 2, kCencCBad = 3 };
 /* what the host hands to the launcher: the round keys go with the crypt kernel's launch, by value, never into scratch */
 struct CencCall : CencArgs { CencKey key; };
-inline void lay_cenc(Carver& w, CencCall& a)
+inline void lay_cenc_args(Carver& w, CencArgs& a)       /* (hbs_cbcs_crypt carves the same: hbs_cbcs.h) */
 {
     a.at_b = w.take<unsigned long long>((a.n_samples + 1) * 8);
     a.at_k = w.take<unsigned long long>((a.n_samples + 1) * 8);
@@ -249,7 +249,11 @@ inline void lay_cenc(Carver& w, CencCall& a)
     a.part_r = w.take<unsigned long long>(((uint64_t)kCencRanges + 1) * 64);
     a.ctl = w.take<unsigned long long>(64);
 }
+inline void lay_cenc(Carver& w, CencCall& a) { lay_cenc_args(w, a); }
 hipError_t launch_cenc_crypt(const CencCall& c, hipStream_t st);
+/* the checks of hbs_cenc_crypt alone, k_cenc_samples to k_cenc_verdict: at_b, at_k, part_r, ctl and the summary (with rbsp_bytes
+ * = the protected bytes) are as the crypt kernel finds them; no events.  hbs_cbcs_crypt begins with them too */
+void enqueue_cenc_checks(const CencArgs& a, hipStream_t st);
 
 } // namespace hbs
 #endif

@@ -21,6 +21,7 @@
  *   k_cenc_at        a workgroup a range, 256 entries a step: B and K at each sample's first entry (at_b, at_k)
  *   k_cenc_sizes     a lane a sample: its entries add up to its size (at_b[s + 1] - at_b[s])
  *   k_cenc_verdict   one workgroup: the error, the summary
+ *                    (these seven are enqueue_cenc_checks: hbs_cbcs_crypt, hbs_cbcs.hip, begins with them too)
  *   k_cenc_iv        iv_mode 1 with a d_iv: the counter blocks
  *   k_cenc_crypt     a workgroup per 64 KiB of the protected bytes of all samples, numbered end to end (K).  It finds the range
  *                    its first byte lies in, walks that range's entries 256 a step to where its bytes begin -- their K and their
@@ -465,12 +466,9 @@ hipError_t launch_cenc_subsamples(const CencPlanArgs& a, hipStream_t st)
     return end_launches(a.ev_end, st);
 }
 
-hipError_t launch_cenc_crypt(const CencCall& c, hipStream_t st)
+void enqueue_cenc_checks(const CencArgs& a, hipStream_t st)
 {
-    const CencArgs& a = c;
     const uint64_t blocks = (a.n_samples + kT - 1) / kT;
-    const hipError_t e = begin_launches(a.ev_begin, st);
-    if (e != hipSuccess) return e;
     if (blocks) hipLaunchKernelGGL(k_cenc_samples, dim3((unsigned)blocks), dim3(kT), 0, st, a);
     hipLaunchKernelGGL(k_cenc_begin, dim3(1), dim3(kPlanLanes), 0, st, a);
     hipLaunchKernelGGL(k_cenc_range_sum, dim3(kCencRanges), dim3(kT), 0, st, a);
@@ -478,6 +476,15 @@ hipError_t launch_cenc_crypt(const CencCall& c, hipStream_t st)
     hipLaunchKernelGGL(k_cenc_at, dim3(kCencRanges), dim3(kT), 0, st, a);
     if (blocks) hipLaunchKernelGGL(k_cenc_sizes, dim3((unsigned)blocks), dim3(kT), 0, st, a);
     hipLaunchKernelGGL(k_cenc_verdict, dim3(1), dim3(kPlanLanes), 0, st, a);
+}
+
+hipError_t launch_cenc_crypt(const CencCall& c, hipStream_t st)
+{
+    const CencArgs& a = c;
+    const uint64_t blocks = (a.n_samples + kT - 1) / kT;
+    const hipError_t e = begin_launches(a.ev_begin, st);
+    if (e != hipSuccess) return e;
+    enqueue_cenc_checks(a, st);
     if (blocks && a.iv_mode && a.iv) hipLaunchKernelGGL(k_cenc_iv, dim3((unsigned)blocks), dim3(kT), 0, st, a);
     if (blocks && a.tiles) hipLaunchKernelGGL(k_cenc_crypt, dim3((unsigned)a.tiles), dim3(kT), 0, st, a, c.key);
     return end_launches(a.ev_end, st);

@@ -114,13 +114,14 @@ typedef struct hbs_ctx hbs_ctx;
  *   hbs_index_extract, hbs_emit_annexb, hbs_parse_headers, hbs_parse_extended, hbs_filter_annexb, hbs_annexb_to_lenpref,
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
  *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples,
- *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write, hbs_au_times, hbs_cenc_subsamples, hbs_cenc_crypt.
+ *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write, hbs_au_times, hbs_cenc_subsamples, hbs_cenc_crypt,
+ *   hbs_cbcs_crypt.
  * hbs_cenc_crypt takes its key and iv0 from host memory when it is called: a captured graph replays with the key and iv0 it was
- * captured with.
+ * captured with.  So does hbs_cbcs_crypt, and with the direction and the pattern of the capture.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
  * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py,
- * tests/test_gpu_mp4_stbl.py, tests/test_gpu_mp4_stbl_write.py, tests/test_gpu_au_times.py and tests/test_gpu_cenc.py replay, no
- * more: hbs_parse_headers_compact,
+ * tests/test_gpu_mp4_stbl.py, tests/test_gpu_mp4_stbl_write.py, tests/test_gpu_au_times.py, tests/test_gpu_cenc.py and
+ * tests/test_gpu_cbcs.py replay, no more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
  * A replay is the captured call on what the buffers hold then: every argument the host passed (counts, byte sizes, capacities,
@@ -1608,7 +1609,7 @@ int hbs_au_times(hbs_ctx* ctx, const hbs_access_unit* d_au, uint64_t n_aus,
  * AES-128 in counter mode, in place, to the protected ranges of samples that lie anywhere in a buffer.  Encryption and
  * decryption are the same call.  NOT written or read: senc, saiz, saio, sinf / tenc, pssh (the records below are in the senc
  * entry form -- 16-bit clear, 32-bit protected -- so a writer can follow); the schemes cbcs, cens, cbc1 (params->scheme is there
- * for them; anything but cenc is refused); key rotation (one key a call).
+ * for them; anything but cenc is refused -- cbcs is a call of its own, hbs_cbcs_crypt, below); key rotation (one key a call).
  *
  * hbs_cenc_subsamples.  The samples are exactly those of hbs_mp4_fragment / hbs_annexb_to_lenpref: sample a is the kept NALs
  * k (d_keep NULL: all) with d_nal_au[k] - d_nal_au[0] == a, in index order, each a record of L = params->length_size length
@@ -1695,6 +1696,76 @@ int hbs_cenc_crypt(hbs_ctx* ctx, uint8_t* d_data, uint64_t data_bytes,
                    const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
                    const uint64_t* d_sub_first /* n_samples + 1 */, const hbs_cenc_subsample* d_sub,
                    uint8_t* d_iv /* n_samples x 16 bytes */, const hbs_cenc_params* params, hbs_summary* d_summary);
+
+/*
+ * ---- Common Encryption, scheme `cbcs` (ISO/IEC 23001-7 10.4): AES-128-CBC over a pattern of blocks, in place ------------------
+ * hbs_cbcs_crypt is the call for the scheme that HLS / FairPlay and CMAF ask for: of every protected range, crypt_byte_block
+ * 16-byte blocks are enciphered in CBC mode, skip_byte_block blocks stay clear, and so on (video: 1 and 9).  It takes the tables
+ * of hbs_cenc_crypt, above -- the subsample table of hbs_cenc_subsamples is the same for every scheme -- and a params record of
+ * its own.  CBC is not its own inverse: HBS_CBCS_DECRYPT selects the way back.  NOT done: cens and cbc1; senc, saiz, saio,
+ * sinf / tenc, pssh; key rotation (one key a call).
+ *
+ * Sample s is d_data[off_s, off_s + size_s) with off_s = d_sample_off[s], size_s = d_sample_size[s]; its subsamples are
+ * d_sub[d_sub_first[s], d_sub_first[s+1]), laid end to end from off_s: `clear` bytes untouched, then `protect` bytes.
+ *   RULE, per entry (clear, protect) whose protected range begins at address p, with c = crypt_byte_block and
+ *   k = skip_byte_block (c = k = 0 means c = 1, k = 0: every block):
+ *     nb = floor(protect / 16); block i < nb is d_data[p + 16 i, p + 16 i + 16), r = i mod (c + k).
+ *     Block i is a CRYPT BLOCK iff r < c -- and, with HBS_CBCS_WHOLE_RUNS, i - r + c <= nb as well: a last run of fewer than c
+ *     whole blocks stays clear.  With f = floor(nb / (c + k)) and m = nb mod (c + k) an entry has f c + min(m, c) crypt blocks
+ *     without the flag and f c + (m >= c ? c : 0) with it; the j-th of them is block floor(j / c) (c + k) + j mod c.
+ *     The crypt blocks of ONE entry, in order, are one CBC chain that starts from the sample's IV:
+ *       encrypt   C_j = AES-128_key(P_j xor C_(j-1)),       C_(-1) = IV_s
+ *       decrypt   P_j = AES-128^-1_key(C_j) xor C_(j-1)
+ *     Chain and pattern restart at every entry: two entries of one sample with equal plaintext give equal ciphertext.
+ *     Every other byte is neither changed nor stored: skip blocks, the protect mod 16 bytes behind the last whole block, clear
+ *     bytes, the gaps between samples, and the bytes that share a 16-byte granule of memory with a crypt block (p is any
+ *     address).
+ *   The two readings of a truncated last run -- partly enciphered, or left clear -- exist in the field; they differ only for
+ *   c > 1.  1:9 and 1:0 (and 0:0) give the same bytes under both, and HBS_CBCS_WHOLE_RUNS selects between them otherwise.
+ *   iv_mode 0: IV_s = d_iv[16 s, 16 s + 16).  iv_mode 1: IV_s = params->iv0 for every sample (tenc's default_constant_IV, the
+ *   usual form of cbcs); d_iv is not read and may be NULL.
+ * CHECKS, each made before any byte of d_data changes: exactly those of hbs_cenc_crypt, in its three groups and with its
+ * words -- off_s + size_s <= data_bytes without a wrap; off_s + size_s <= off_(s+1); d_sub_first non-decreasing from 0 (and below
+ * 2^48); then clear <= 65535; then the entries of sample s add up to exactly size_s.  Else error = HBS_E_ARG with reserved[0] =
+ * 1 + the lowest offending sample (of the first group that fails), and nothing but the summary is written.  A protect that is
+ * no multiple of 16 is no error (no HBS_CENC_ALIGN16 is needed).  d_sub must hold d_sub_first[n_samples] entries.
+ * d_summary: nal_count = entries read, nal_found = n_samples, rbsp_bytes = 16 x the crypt blocks of all entries, stream_bytes =
+ * data_bytes, stop_reason = 0, reserved = 0.  n_samples == 0 is valid.
+ * Refused with HBS_E_ARG at once, nothing touched: params NULL, iv_mode above 1, unknown flags, crypt_byte_block or
+ * skip_byte_block above 15, crypt_byte_block == 0 with skip_byte_block != 0, a reserved field != 0, iv_mode 0 without d_iv
+ * (n_samples > 0), n_samples above 2^32 - 1, missing tables with n_samples > 0, a missing d_data with data_bytes > 0, a missing
+ * d_summary, a misaligned pointer.
+ * Alignment: d_data, d_iv, d_summary 16 bytes; d_sample_off, d_sample_size, d_sub_first, d_sub 8 bytes.
+ * No host synchronisation (HIP graphs, above: a replay uses the key, iv0, direction and pattern of the capture).  Both key
+ * schedules -- the cipher's and that of the equivalent inverse cipher -- are expanded on the host and go to the kernel by value
+ * with the launch; they are never in the context's scratch or any other device buffer, and the host copies are zeroed when the
+ * call returns.  Scratch: that of hbs_cenc_crypt, which the two calls share (16 bytes a sample, 64 per 256 samples, 65 KiB; it
+ * is sized without the entry count, which the host never learns).
+ * Work: the entries are walked in 1 024 equal ranges, a workgroup a range, 256 entries a step.  An entry of fewer than 64
+ * crypt blocks is one lane's serial loop in either direction.  A longer one is, when DECRYPTING, a wavefront's: 64 consecutive
+ * crypt blocks a step, each lane's previous ciphertext block taken from the lane below.  When ENCRYPTING it stays on its one
+ * lane, because C_j needs C_(j-1): that is CBC, not this library.  A sample of one 1 MiB NAL at 1:9 is about 6 500 dependent
+ * blocks on one lane; throughput of encryption comes from many entries, not from long ones.
+ */
+#define HBS_CBCS_DECRYPT     1u   /* flags: the inverse direction (CBC is not its own inverse) */
+#define HBS_CBCS_WHOLE_RUNS  2u   /* flags: a last run of fewer than crypt_byte_block whole blocks stays clear */
+
+typedef struct hbs_cbcs_params {      /* HOST memory, 48 bytes */
+    uint8_t  key[16];
+    uint8_t  iv0[16];                 /* iv_mode 1: the constant IV of every sample (tenc default_constant_IV) */
+    uint32_t iv_mode;                 /* 0: d_iv[16 s, 16 s + 16) is sample s's IV; 1: iv0 for every sample, d_iv not read */
+    uint32_t flags;                   /* HBS_CBCS_DECRYPT | HBS_CBCS_WHOLE_RUNS */
+    uint8_t  crypt_byte_block;        /* 0..15, as in tenc; video: 1 */
+    uint8_t  skip_byte_block;         /* 0..15; video: 9 */
+    uint16_t reserved0;               /* 0 */
+    uint32_t reserved1;               /* 0 */
+} hbs_cbcs_params;
+
+int hbs_cbcs_crypt(hbs_ctx* ctx, uint8_t* d_data, uint64_t data_bytes,
+                   const uint64_t* d_sample_off, const uint64_t* d_sample_size, uint64_t n_samples,
+                   const uint64_t* d_sub_first /* n_samples + 1 */, const hbs_cenc_subsample* d_sub,
+                   const uint8_t* d_iv /* n_samples x 16 bytes, iv_mode 0 */,
+                   const hbs_cbcs_params* params, hbs_summary* d_summary);
 
 /*
  * ---- access-unit delimiters and parameter sets in front of access units ---------------------------------------------
