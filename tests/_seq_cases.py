@@ -13,10 +13,18 @@ Their scratch is laid out by capacities of the caller as well, so they have a va
 a "roomy" variant with every capacity well above the need, whose outputs are as large as the capacities (`spare`: the room behind
 what is written).  A malformed variant of theirs says which summary word names the fault and with what (`named`), whether a plan
 looks for it (`in_plan`) and which table the edited entry lies in (`among`).  order_of, unpack_of, samples_of and stbl_of are the
-later stages of the pipelines, each on what the reference says the stage in front puts out."""
+later stages of the pipelines, each on what the reference says the stage in front puts out.
+
+CALLS3 are the timing and encryption calls, for tests/test_gpu_sequences_times_crypt.py: hbs_au_times, hbs_cenc_subsamples,
+hbs_cenc_crypt and hbs_cbcs_crypt in both directions.  Only hbs_cenc_subsamples takes a capacity, so only it has a short and a
+roomy variant; the crypt calls have no plan, one set of tables a size between them, and a fourth table in which no sample has an
+entry (hollow).  Their section is at the end of the file."""
 import numpy as np
 
+from tests import _au_times_ref as T
 from tests import _auins_ref as INS
+from tests import _cbcs_ref as CB
+from tests import _cenc_ref as CR
 from tests import _filter_ref as F
 from tests import _lenpref_ref as LP
 from tests import _mp4_read_ref as MR
@@ -62,6 +70,17 @@ SHORTS = dict(rtp=("short",), rtpa=("short",), rtpu=("short", "short_nal", "shor
 SHORT_CAP = dict(short="out_cap", short_nal="nal_cap", short_au="au_cap", short_frag="frag_cap", short_moof="moof_cap",
                  short_sample="sample_cap")
 PLAN_SHORT = ("short_span", "short_moof")             # capacities a plan looks at as well: max_span, moof_cap
+# the timing and encryption calls, for tests/test_gpu_sequences_times_crypt.py: hbs_au_times, hbs_cenc_subsamples, hbs_cenc_crypt,
+# hbs_cbcs_crypt encrypting and with HBS_CBCS_DECRYPT
+CRYPT_CALLS = ("cenc", "cbcs", "cbcsd")
+CALLS3 = ("aut", "csub") + CRYPT_CALLS
+# hbs_autimes.h: kAutLanes, kAutHalo; hbs_cenc.h: kCencNalsPerBlock, a lane a sample of kPlanLanes, kCencRanges; hbs_cbcs.h: kCbcsLaneBlocks
+AUT_BLOCK, AUT_HALO, CENC_NAL_BLOCK, CRYPT_SAMPLE_BLOCK, CRYPT_RANGES, CBCS_LANE_BLOCKS = 256, 64, 2048, 256, 1024, 64
+E_DEPTH = -6
+AUT_TABLES = (("dts", 8), ("pts", 8), ("order", 4), ("display", 4))          # d_dts, d_pts, d_order, d_display and their entries' bytes
+CRYPT_TAIL = 37                                       # bytes of the data buffer behind the last sample
+SHORTS["csub"] = ("short",)
+SHORT_CAP["csub"] = "sub_cap"                         # (hbs_cenc_subsamples' only capacity: by the call, not by the variant's name)
 
 
 class Case:
@@ -72,6 +91,7 @@ class Case:
         # a malformed variant: the summary word that names the fault and its value (1 + bad, or 1 + the box for a table error of
         # hbs_mp4_stbl_samples); does a plan find the fault; (items, items per workgroup) of the table the edited entry lies in
         self.named, self.in_plan, self.among = None, True, None
+        self.error = E_ARG                             # the error of a malformed variant (hbs_au_times: HBS_E_DEPTH)
         self._want = {}
 
     def __repr__(self):
@@ -85,6 +105,12 @@ def blocks(n, per):
 def items(case):
     """what the call's plan kernels count -> a tuple of (items, items per plan workgroup)"""
     a = case.a
+    if case.call == "aut":
+        return ((len(a["au"]), AUT_BLOCK),)
+    if case.call == "csub":
+        return ((len(a["index"]), CENC_NAL_BLOCK),)
+    if case.call in CRYPT_CALLS:                   # the samples, and the entries by the thousand: the kernels walk them in 1 024 ranges
+        return ((len(a["off"]), CRYPT_SAMPLE_BLOCK), (crypt_entries(a), CRYPT_RANGES))
     if case.call in ("rtp", "rtpa"):
         return ((len(a["index"]), RTP_NAL_BLOCK),)
     if case.call == "rtpu":
@@ -124,6 +150,8 @@ def plan_blocks(case):
 def reference(case, plan=False):
     """the plain loop on the case's arguments (a plan looks at no capacity)"""
     a, c = case.a, ({} if plan else case.caps)
+    if case.call in CALLS3:
+        return reference3(case, plan)
     if case.call in ("rtp", "rtpa"):
         return RA.pack(a["stream"], a["index"], a["nal_au"], a["n_aus"], a["pts"], a["prm"], c.get("out_cap"))
     if case.call == "rtpu":
@@ -171,6 +199,8 @@ def reserved0(s):
 
 def needs(case):
     """capacities of exactly what the good case puts out, from the reference's plan"""
+    if case.call in CALLS3:
+        return needs3(case)
     w = want(case, plan=True)
     s = w[-1]
     assert s["error"] == 0, (case, s)
@@ -440,6 +470,7 @@ def make_stblw(which, seed):
 
 MAKERS = dict(a2l=make_a2l, l2a=make_l2a, tsd=make_tsd, tsm=make_tsm, ins=make_ins, rtp=make_rtp, rtpa=make_rtpa, rtpu=make_rtpu,
               rtpo=make_rtpo, mp4f=make_mp4f, mp4s=make_mp4s, stbl=make_stbl, stblw=make_stblw)
+# (the makers of CALLS3 are added below, where they are defined)
 PACKET_CALLS = ("tsd", "tsm")                        # their cases take a packet size
 _cases = {}
 
@@ -515,7 +546,9 @@ def empty(call, B=188):
     if key in _cases:
         return _cases[key]
     z8, z64 = np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint64)
-    if call in ("rtp", "rtpa"):
+    if call in CALLS3:
+        a = empty3(call)
+    elif call in ("rtp", "rtpa"):
         a = dict(stream=z8, index=np.zeros(0, dtype=R.NAL_ENTRY), nal_au=np.zeros(0, dtype=np.uint32), n_aus=0, pts=z64,
                  prm=(RTP if call == "rtp" else RTPA)["small"]["prm"])
     elif call == "rtpu":
@@ -572,6 +605,8 @@ def edited_table(good, late):
 
 def malformed(good, late):
     """one entry edited as the calls' own tests edit theirs"""
+    if good.call in CALLS3:
+        return malformed3(good, late)
     a = dict(good.a)
     at = edited_entry(good, late)
     word, value, in_plan = 0, None, True
@@ -684,7 +719,7 @@ def short(good, what="short"):
     if what == "short_span":
         v.a = dict(good.a, prm=dict(good.a["prm"], max_span=summary_of(good)["stream_bytes"] - 1))
     else:
-        v.caps[SHORT_CAP[what]] -= 1
+        v.caps[SHORT_CAP[good.call if good.call in CALLS3 else what]] -= 1
     return v
 
 
@@ -697,7 +732,8 @@ def roomy(good):
                rtpo=dict(out_cap=("ooff", 8, "osize", 8, "src", 4, "ext", 8)),
                mp4f=dict(out_cap=("out", 1), frag_cap=("fr", MF.FRAG.itemsize)),
                mp4s=dict(moof_cap=("fr", MF.FRAG.itemsize), sample_cap=("so", 8, "ss", 8, "dts", 8, "pts", 8, "sfl", 4)),
-               stbl=dict(sample_cap=("so", 8, "ss", 8, "dts", 8, "pts", 8, "sfl", 4)), stblw=dict(out_cap=("out", 1)))[good.call]
+               stbl=dict(sample_cap=("so", 8, "ss", 8, "dts", 8, "pts", 8, "sfl", 4)), stblw=dict(out_cap=("out", 1)),
+               csub=dict(sub_cap=("sub", CR.SUBSAMPLE.itemsize)))[good.call]
     v.caps, v.room = dict(good.caps), dict(good.room)
     for cap, outs in per.items():
         more = ROOM_BYTES if outs[1] == 1 else ROOM_ITEMS
@@ -737,8 +773,11 @@ def writes_nothing_when_refused(call):
     nothing is written but the summary"; hbs_rtp_unpack: "On either error nothing but the summary is written"; hbs_rtp_order: "On
     any error nothing but the summary is written"; hbs_mp4_fragment and hbs_mp4_samples: "On any error nothing but the summary is
     written"; hbs_mp4_stbl_samples: "on any error only the summary is written"; hbs_mp4_stbl_write: "On any error nothing but the
-    summary is written"."""
-    return call in CALLS2
+    summary is written"; hbs_au_times: "the summary's error is HBS_E_DEPTH, ... and nothing but the summary is written";
+    hbs_cenc_subsamples: "On an error only the summary is written"; hbs_cenc_crypt: "nothing but the summary is written", and
+    hbs_cbcs_crypt has its checks (the buffer the crypt calls work in is no output in this sense: it holds what was uploaded, and
+    is compared with that)."""
+    return call in CALLS2 or call in CALLS3
 
 
 def sequence(call, seed=1, B=188):
@@ -756,3 +795,301 @@ def sequence2(call, seed=1):
              (variant(small, "bad_early"), False), (odd, False), (empty(call), False)]
     steps += [(variant(large, what), False) for what in SHORTS[call]]
     return steps + [(variant(small, "roomy"), False), (large, True), (large, False)]
+
+
+# ---- the timing and encryption calls (CALLS3) ------------------------------------------------------------------------------------
+# A case of hbs_au_times holds the AU table, the keywords of T.params_record and the tables it asks for (`outs`); one of
+# hbs_cenc_subsamples the stream, the index and the AU numbers with d_keep / d_payload_off or None; one of the crypt calls the
+# data, the four tables, the key, either the per-sample IVs (`iv`) or the constant / first one (`iv0`), for hbs_cenc_crypt whether
+# a d_iv receives the counter blocks (`ivo`), for hbs_cbcs_crypt the pattern.  The three crypt calls take one set of tables a
+# size; the data buffer is their output: a step uploads it fresh and compares all of it.
+
+def crypt_entries(a):
+    return int(a["first"][-1]) if len(a["off"]) else 0
+
+
+def reference3(case, plan):
+    a, c = case.a, ({} if plan else case.caps)
+    if case.call == "aut":                         # (a plan has all four tables NULL and writes the summary alone)
+        r = T.au_times(a["au"], **a["kw"])
+        return tuple(None if plan else r[name] for name, _ in AUT_TABLES) + (r["summary"],)
+    if case.call == "csub":                        # (a plan writes d_sub_first; under HBS_E_ARG "the counts mean nothing")
+        idx = a["index"]
+        r = CR.subsamples(a["stream"], idx["start"].astype(np.int64), idx["end"].astype(np.int64), a["nal_au"], a["n_aus"], a["L"], keep=a["keep"],
+                          payload_off=a["po"], flags=a["flags"], clear_lead=a["clear_lead"], sub_cap=c.get("sub_cap"))
+        if r["error"] == E_ARG:
+            return None, None, dict(error=E_ARG, nal_found=len(idx), stop_reason=0, reserved=[r["bad"], 0, None])
+        s = dict(error=r["error"], nal_count=len(r["sub"]), nal_found=len(idx), rbsp_bytes=r["protected"], stream_bytes=r["sample_bytes"],
+                 stop_reason=0, reserved=[0, 0, r["kept"]])
+        return (r["sub_first"] if not r["error"] else None), (r["sub"] if not r["error"] and not plan else None), s
+    n, cenc = len(a["off"]), case.call == "cenc"
+    s = dict(error=0, nal_count=crypt_entries(a), nal_found=n, rbsp_bytes=0, stream_bytes=len(a["data"]), stop_reason=0, reserved=[0, 0, 0])
+    bad = CR.crypt_check(len(a["data"]), a["off"], a["size"], a["first"], a["sub"]) if n else 0
+    if bad:                                        # counts 0, the data as it was
+        s.update(error=E_ARG, nal_count=0, reserved=[bad, 0, 0])
+        return (a["data"],) + ((None,) if cenc else ()) + (s,)
+    if cenc:
+        out, s["rbsp_bytes"], used = CR.crypt(a["data"], a["off"], a["size"], a["first"], a["sub"], a["key"], iv=a["iv"], iv0=a["iv0"])
+        return out, (used.reshape(-1) if a["ivo"] else None), s
+    out, s["rbsp_bytes"] = CB.crypt_many(a["data"], a["off"], a["size"], a["first"], a["sub"], a["key"], iv=a["iv"], iv0=a["iv0"], c=a["c"], k=a["k"],
+                                         whole=a["whole"], decrypt=case.call == "cbcsd")
+    return out, s
+
+
+def needs3(case):
+    a = case.a
+    if case.call == "aut":                         # no capacity: each table it asks for has n_aus entries
+        return {}, {name: len(a["au"]) * width for name, width in AUT_TABLES if name in a["outs"]}
+    if case.call == "csub":
+        s = want(case, plan=True)[-1]
+        assert s["error"] == 0, (case, s)
+        return dict(sub_cap=s["nal_count"]), dict(sf=(a["n_aus"] + 1) * 8, sub=s["nal_count"] * CR.SUBSAMPLE.itemsize)
+    return {}, dict(data=len(a["data"]), **(dict(ivo=16 * len(a["off"])) if a.get("ivo") else {}))
+
+
+def make_aut(which, seed):
+    """small: pyramids, two heads, AUs without a picture.  large: six workgroups, the last ragged; heads on the last AU of workgroup
+    0 and the first of workgroup 1; AUs without a picture across the edge of workgroups 1 and 2; the last AU of workgroup 2 has a
+    key above those of the 80 and more AUs behind it (its forward walk leaves the halo), and 80 AUs in front of the first AU of
+    workgroup 4 lies a key above that AU's (its backward walk does).  odd: HBS_AUT_WRAP33 across 2^33, a delay given below R, and
+    only d_pts and d_display asked for"""
+    rng = np.random.default_rng(seed + 1100)
+    B, outs = AUT_BLOCK, tuple(name for name, _ in AUT_TABLES)
+    if which == "small":
+        n = 200
+        au, kw = T.table(T.pyramid(8, n // 8 + 1)[:n], heads=[64, 130], nopic=[5, 70, 71], junk=rng), dict(tick=3003, base_time=90000)
+    elif which == "odd":
+        n = B + 100
+        au = T.table(T.pyramid(16, n // 16 + 1)[:n], heads=[B + 1], junk=rng)
+        R = T.au_times(au)["summary"]["reserved"][1]
+        kw, outs = dict(tick=3003, base_time=(1 << 33) - 3003 * 5 - 1, flags=T.WRAP33, delay=R - 2), ("pts", "display")
+    else:
+        n = 5 * B + 11
+        keys = 4 * np.asarray(T.pyramid(8, n // 8 + 1)[:n], dtype=np.int64)
+        keys[3 * B - 1] = 4 * (3 * B - 1 + 85)
+        keys[4 * B - 80] = 4 * (4 * B + 12)
+        au = T.table(keys.tolist(), heads=[B - 1, B], nopic=list(range(2 * B - 3, 2 * B + 4)), junk=rng)
+        kw = dict(tick=3003, base_time=90000)
+    return finish(Case("aut", which, dict(au=au, kw=kw, outs=outs)))
+
+
+def cenc_stream(rng, n_nals, n_aus, L, keep, po, edges=(), big=False):
+    """n_nals small NALs of types 1, 19, 32..34, 39, 35 behind 3-byte gaps in n_aus AUs, two of them with nothing kept; at every NAL
+    of `edges` four kept parameter sets of one AU, two on either side; with `big` a 70 000-byte SEI in front of a slice of its AU
+    (a clear run above 65 535) and an SEI that is alone in its AU and, with its four length bytes, 2 x 65 535 bytes long
+    -> (stream, index, nal_au, keep or None, payload_off or None)"""
+    types = rng.choice([1, 19, 32, 33, 34, 39, 35], n_nals)
+    sizes = rng.integers(0, 90 if L > 1 else 60, n_nals)
+    kept = (rng.integers(0, 5, n_nals) > 0).astype(np.uint8) if keep else np.ones(n_nals, dtype=np.uint8)
+    same, alone = {51} if big else set(), [200] if big else []          # NALs that continue their AU; NALs that are an AU
+    for e in edges:
+        types[e - 2:e + 2], sizes[e - 2:e + 2], kept[e - 2:e + 2] = 33, 20, 1
+        same |= {e - 1, e, e + 1}
+    if big:
+        assert L == 4
+        types[50], sizes[50], kept[50] = 39, 70000, 1
+        types[51], sizes[51], kept[51] = 1, 50, 1
+        types[200], sizes[200], kept[200] = 39, 2 * CR.MAX_CLEAR - L, 1
+    rises = {k for a in alone for k in (a, a + 1)}
+    free = [k for k in range(1, n_nals) if k not in same and k not in rises]
+    inc = np.zeros(n_nals, dtype=np.uint32)
+    inc[sorted(rises) + rng.permutation(free)[: n_aus - 1 - len(rises)].tolist()] = 1
+    nal_au = (np.cumsum(inc) + 3).astype(np.uint32)
+    sizes[(types < 32) & (sizes == 1)] = 2
+    if keep:
+        for a in (nal_au[30], nal_au[120]):
+            kept[nal_au == a] = 0
+    starts = np.cumsum(sizes + 3) - sizes
+    ends = starts + sizes
+    stream = rng.integers(0, 256, int(ends[-1]) + 9, dtype=np.uint8)
+    at = starts[sizes > 0]
+    stream[at] = (types[sizes > 0] << 1).astype(np.uint8) | (stream[at] & 0x81)
+    off = np.full(n_nals, CR.M64, dtype=np.uint64)
+    vcl = np.flatnonzero((types < 32) & (sizes >= 2))
+    off[vcl] = (starts[vcl] + rng.integers(2, sizes[vcl] + 1)).astype(np.uint64)
+    index = np.zeros(n_nals, dtype=F.NAL_ENTRY)
+    index["start"], index["end"] = starts, ends
+    return stream, index, nal_au, (kept if keep else None), (off if po else None)
+
+
+# NALs of the hbs_cenc_subsamples cases: one plan workgroup; two and a ragged third with AUs and clear runs across both edges and
+# the long clear runs; between them with 1-byte lengths, no d_keep, no d_payload_off, HBS_CENC_ALIGN16 and a clear lead of 2
+CSUB = dict(small=dict(n=400, aus=200, L=4, keep=True, po=True, flags=0, lead=96, edges=(), big=False),
+            large=dict(n=2 * CENC_NAL_BLOCK + 900, aus=1700, L=4, keep=True, po=True, flags=0, lead=96, edges=(CENC_NAL_BLOCK, 2 * CENC_NAL_BLOCK), big=True),
+            odd=dict(n=CENC_NAL_BLOCK + 500, aus=900, L=1, keep=False, po=False, flags=CR.ALIGN16, lead=2, edges=(), big=False))
+
+
+def make_csub(which, seed):
+    p = CSUB[which]
+    stream, index, nal_au, keep, po = cenc_stream(np.random.default_rng(seed + 1200), p["n"], p["aus"], p["L"], p["keep"], p["po"], p["edges"], p["big"])
+    return finish(Case("csub", which, dict(stream=stream, index=index, nal_au=nal_au, n_aus=p["aus"], keep=keep, po=po, L=p["L"], flags=p["flags"],
+                                           clear_lead=p["lead"])))
+
+
+def crypt_tables(which, seed):
+    """the data and the four tables of one size, shared by the three crypt calls (built once).  Samples at odd addresses with gaps
+    of 1 to 9 bytes.  small: 120 samples of one to four entries.  large: 3 x 256 + 40 samples cut at random entries of 16 x 1 024 +
+    300, half of them with 64 to 70 whole blocks and 0 to 15 bytes protected, the rest with 0 to 48 bytes.  odd: 356 samples of which
+    four in ten have no entry and size 0, the first and the last among them.  hollow: 300 samples, none with an entry"""
+    key = ("crypt tables", which, seed)
+    if key in _cases:
+        return _cases[key]
+    rng = np.random.default_rng(seed + 1300)
+    if which == "large":
+        ns, E = 3 * CRYPT_SAMPLE_BLOCK + 40, 16 * CRYPT_RANGES + 300
+        first = np.concatenate([[0], np.sort(rng.choice(np.arange(1, E), size=ns - 1, replace=False)), [E]])
+        long_ = rng.random(E) < 0.5
+        protect = np.where(long_, 16 * rng.integers(CBCS_LANE_BLOCKS, CBCS_LANE_BLOCKS + 7, E) + rng.integers(0, 16, E), rng.integers(0, 49, E))
+    else:
+        if which == "small":
+            per = rng.integers(1, 5, 120)
+        elif which == "odd":
+            per = np.where(rng.random(CRYPT_SAMPLE_BLOCK + 100) < 0.4, 0, rng.integers(3, 12, CRYPT_SAMPLE_BLOCK + 100))
+            per[[0, 7, 8, -1]] = 0
+        else:
+            per = np.zeros(300, dtype=np.int64)
+        ns, E = len(per), int(per.sum())
+        first = np.concatenate([[0], np.cumsum(per)])
+        protect = rng.integers(0, 200, E)
+    clear = rng.integers(0, 21, E)
+    sub = np.zeros(E, dtype=CR.SUBSAMPLE)
+    sub["clear"], sub["protect"] = clear, protect
+    total = np.concatenate([[0], np.cumsum(clear + protect)])
+    size = total[first[1:]] - total[first[:-1]]
+    gaps = rng.integers(1, 10, ns)
+    off = 3 + np.concatenate([[0], np.cumsum(size + gaps)[:-1]])
+    data = rng.integers(0, 256, int(off[-1] + size[-1]) + CRYPT_TAIL, dtype=np.uint8)
+    _cases[key] = dict(data=data, off=off.astype(np.uint64), size=size.astype(np.uint64), first=first.astype(np.uint64), sub=sub)
+    return _cases[key]
+
+
+def long_entries_a_range(a):
+    """the entries of kCbcsLaneBlocks whole blocks and more in each of the 1 024 ranges (hbs_cenc.h: cenc_range_begin)"""
+    E, G = crypt_entries(a), CRYPT_RANGES
+    begin = [E // G * g + E % G * g // G for g in range(G + 1)]
+    long_ = np.concatenate([[0], np.cumsum(a["sub"]["protect"] // 16 >= CBCS_LANE_BLOCKS)])
+    return np.diff(long_[begin]), np.diff(begin)
+
+
+def make_crypt(call):
+    """small and large: the IVs of the samples in d_iv; hbs_cbcs_crypt 1:9 and 1:0 (every long entry of the large tables is
+    kCbcsLaneBlocks crypt blocks or more).  odd and hollow: hbs_cenc_crypt with iv_mode 1 from ff..fe (the third sample's counter
+    block wraps to 0) and a d_iv that receives the blocks; hbs_cbcs_crypt 3:7 with HBS_CBCS_WHOLE_RUNS, the constant IV, no d_iv"""
+    def make(which, seed):
+        t = crypt_tables(which, seed)
+        rng = np.random.default_rng(seed + 1400 + CALLS3.index(call))
+        plain = which in ("small", "large")
+        a = dict(t, key=bytes(rng.integers(0, 256, 16, dtype=np.uint8)), iv=rng.integers(0, 256, 16 * len(t["off"]), dtype=np.uint8) if plain else None)
+        if call == "cenc":
+            a.update(iv0=None if plain else bytes.fromhex("fffffffffffffffe"), ivo=not plain)
+        else:
+            c, k = dict(small=(1, 9), large=(1, 0)).get(which, (3, 7))
+            a.update(iv0=None if plain else bytes(rng.integers(0, 256, 16, dtype=np.uint8)), ivo=False, c=c, k=k, whole=not plain)
+        return finish(Case(call, which, a))
+    return make
+
+
+MAKERS.update(aut=make_aut, csub=make_csub, cenc=make_crypt("cenc"), cbcs=make_crypt("cbcs"), cbcsd=make_crypt("cbcsd"))
+
+
+def hollow(call, seed=1):
+    """the table of a crypt call in which every sample has no entries and size 0"""
+    return case(call, "hollow", seed)
+
+
+def empty3(call):
+    if call == "aut":
+        return dict(au=T.table([]), kw=dict(delay=9), outs=tuple(name for name, _ in AUT_TABLES))
+    if call == "csub":
+        return dict(stream=np.zeros(0, dtype=np.uint8), index=np.zeros(0, dtype=F.NAL_ENTRY), nal_au=np.zeros(0, dtype=np.uint32), n_aus=0, keep=None,
+                    po=None, L=4, flags=0, clear_lead=96)
+    z64 = np.zeros(0, dtype=np.uint64)
+    a = dict(data=np.random.default_rng(5).integers(0, 256, 100, dtype=np.uint8), off=z64, size=z64, first=np.zeros(1, dtype=np.uint64),
+             sub=np.zeros(0, dtype=CR.SUBSAMPLE), key=bytes(range(16)), iv=None, iv0=bytes(range(16, 24 if call == "cenc" else 32)), ivo=False)
+    if call != "cenc":
+        a.update(c=1, k=9, whole=False)
+    return a
+
+
+# the check group a malformed variant of a crypt call fails (early, late): the sums (d_sample_size[j] += 1), the first group
+# (d_sub_first falls behind sample j), the second (a clear count of 65 536 in sample j's first entry)
+CRYPT_FAULTS = dict(cenc=("sums", "falling"), cbcs=("clear", "sums"), cbcsd=("falling", "clear"))
+
+
+def malformed3(good, late):
+    """hbs_au_times: a table with a span of HBS_AUT_MAX_SPAN + 1, tests/test_gpu_au_times.py::span_tables, with the good case's
+    parameters and tables.  Both ends of such a span offend -- fwd of the AU in front, back of the AU behind -- so the lowest
+    offending AU is always the one in front: `early` has it in the first workgroup, and `late` has the AU behind in the last
+    workgroup, 1 025 AUs behind the one the summary names (no table can name an AU of its last workgroup).  hbs_cenc_subsamples:
+    tests/test_gpu_cenc.py::test_a_slice_the_parse_did_not_read_is_an_error, "start+1".  The crypt calls: CRYPT_FAULTS, as
+    test_each_error_alone of their modules"""
+    a = dict(good.a)
+    named_error = E_ARG
+    if good.call == "aut":
+        span, lead, tail = T.MAX_SPAN + 1, (45, 5) if late else (10, 40), None
+        a["au"] = T.table([0] * lead[0] + [9] + [1] * span + [50] * lead[1], junk=np.random.default_rng(len(good.a["au"]) + late))
+        at, among, named_error = lead[0], (len(a["au"]), AUT_BLOCK), E_DEPTH
+    elif good.call == "csub":
+        assert a["po"] is not None, "the fault is a d_payload_off"
+        n, per = items(good)[0]
+        at = 5 if not late else max((blocks(n, per) - 1) * per, n - 40)
+        usable = (a["po"] != CR.M64) & (a["keep"] != 0 if a["keep"] is not None else True)
+        at = at + int(np.flatnonzero(usable[at:])[0])          # the next kept VCL NAL of two bytes and more
+        a["po"] = a["po"].copy()
+        a["po"][at] = a["index"]["start"][at] + np.uint64(1)
+        among = (n, per)
+    else:
+        n, per = items(good)[0]
+        fault = CRYPT_FAULTS[good.call][1 if late else 0]
+        at = max(n - 3, (blocks(n, per) - 1) * per) if late else min(5, n - 1)
+        first = a["first"].astype(np.int64)
+        if fault == "sums":                        # (a gap of a byte and more lies behind every sample, and CRYPT_TAIL behind the last)
+            a["size"] = a["size"].copy()
+            a["size"][at] += np.uint64(1)
+        elif fault == "falling":
+            at += int(np.flatnonzero(first[at:-1] > 0)[0])
+            a["first"] = a["first"].copy()
+            a["first"][at + 1] = a["first"][at] - np.uint64(1)
+        else:
+            at += int(np.flatnonzero(first[at + 1:] > first[at:-1])[0])          # the next sample with an entry
+            e, more = int(first[at]), 65536 - int(a["sub"]["clear"][int(first[at])])
+            a["sub"], a["size"], a["off"] = a["sub"].copy(), a["size"].copy(), a["off"].copy()
+            a["sub"]["clear"][e] = 65536
+            a["size"][at] += np.uint64(more)
+            a["off"][at + 1:] += np.uint64(more)
+            a["data"] = np.concatenate([a["data"], np.zeros(more, dtype=np.uint8)])
+        among = (n, per)
+    v = Case(good.call, good.name + (" bad-late" if late else " bad-early"), a, bad=at)
+    v.caps, v.room = needs3(v) if good.call != "csub" else (dict(good.caps), dict(good.room))
+    v.named, v.among, v.error = (0, at + 1), among, named_error
+    return v
+
+
+def sequence3(call, seed=1):
+    """the steps of a CALLS3 sequence on one context: the ten steps; the crypt calls have the table without any entry behind the
+    odd one and, having no plan, no plan-only step; hbs_cenc_subsamples alone has a capacity, so it alone has the step that is an
+    entry short and the roomy one -> [(case, plan only?)]"""
+    small, large, odd = (case(call, w, seed) for w in SIZES)
+    steps = [(large, False), (small, False), (variant(large, "bad_late"), False), (small, False), (variant(small, "bad_early"), False), (odd, False)]
+    if call in CRYPT_CALLS:
+        steps.append((hollow(call, seed), False))
+    steps.append((empty(call), False))
+    if call == "csub":
+        steps += [(variant(large, "short"), False), (variant(small, "roomy"), False)]
+    if call not in CRYPT_CALLS:
+        steps.append((large, True))
+    return steps + [(large, False)]
+
+
+# what the three crypt calls do one after the other in the one buffer they share: (call, case)
+SHARED_CRYPT = (("cenc", "large"), ("cbcsd", "small"), ("cbcs", "large"), ("cenc", "small"), ("cbcsd", "large"), ("cenc", "hollow"), ("cbcsd", "small"),
+                ("cbcs", "large bad-late"), ("cenc", "small"), ("cbcsd", "odd"), ("cbcsd", "hollow"), ("cenc", "large"))
+
+
+def shared_crypt_steps(seed=1):
+    out = []
+    for call, name in SHARED_CRYPT:
+        which, _, bad = name.partition(" ")
+        c = case(call, which, seed)
+        out.append((variant(c, bad.replace("-", "_")) if bad else c, False))
+    return out

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import _carve as K
 from tests import _cbcs_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +44,10 @@ def fresh_summary():
 def summary_dict(s):
     return dict(error=int(s["error"]), nal_count=int(s["nal_count"]), nal_found=int(s["nal_found"]), rbsp_bytes=int(s["rbsp_bytes"]),
                 stream_bytes=int(s["stream_bytes"]), stop_reason=int(s["stop_reason"]), reserved=[int(x) for x in s["reserved"]])
+
+
+def summary_matches(s, want):
+    assert summary_dict(s) == want
 
 
 def layout(entries_per_sample, gaps, lead=0):
@@ -498,3 +503,79 @@ def test_end_to_end_on_a_live_context(ctx):
     src = np.frombuffer(stream, dtype=np.uint8)
     back, _, _ = ctx.lenpref_to_annexb(out, so, sz, length_size=4, startcode_bytes=4)
     assert bytes(back.cpu().numpy()) == b"".join(b"\x00\x00\x00\x01" + bytes(src[int(e["start"]):int(e["end"])]) for e in h_idx)
+
+
+# ---- many long entries in a step, decrypting ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("c,k", ((1, 0), (1, 9)))
+def test_many_long_entries_in_a_step(ctx, c, k):
+    """the large tables of tests/_seq_cases.py: 2 to 15 entries of kCbcsLaneBlocks crypt blocks and more in every range, more than
+    four in nine ranges of ten (tests/test_seq_cases.py), so the decrypting kernel lists more entries in a step than it has
+    wavefronts.  Random bytes are the ciphertext.  With 1:9 the long entries are scaled to the same 64 to 70 crypt blocks.  Then
+    the device's encryption of the device's plaintext, against the reference on the same tables (all samples: the reference's step
+    loop has the 70 steps of the longest chain whatever the pattern, under two seconds), gives the ciphertext back"""
+    from tests import _seq_cases as S
+    t = S.crypt_tables("large", 1)
+    rng = np.random.default_rng(1700 + k)
+    sub, first = t["sub"].copy(), t["first"]
+    if k:                                                   # m crypt blocks of 1:9 are (m - 1) x 10 + 1 blocks
+        long_ = sub["protect"] // 16 >= LANE_BLOCKS
+        sub["protect"][long_] = 16 * ((sub["protect"][long_] // 16 - 1) * (c + k) + 1) + sub["protect"][long_] % 16
+    blocks = np.array([R.crypt_blocks(c, k, False, int(p) // 16) for p in sub["protect"]])
+    begin = [S.crypt_entries(t) // RANGES * g + S.crypt_entries(t) % RANGES * g // RANGES for g in range(RANGES + 1)]
+    listed = np.diff(np.concatenate([[0], np.cumsum(blocks >= LANE_BLOCKS)])[begin])
+    assert (listed > 4).sum() >= 900 and listed.min() >= 1 and max(np.diff(begin)) <= 256 and blocks.max() <= 70
+    total = np.concatenate([[0], np.cumsum(sub["clear"].astype(np.int64) + sub["protect"])])
+    size = (total[first[1:].astype(np.int64)] - total[first[:-1].astype(np.int64)]).astype(np.uint64)
+    off = (3 + np.concatenate([[0], np.cumsum(size.astype(np.int64) + 5)[:-1]])).astype(np.uint64)
+    n = int(off[-1] + size[-1]) + 11
+    cipher = rng.integers(0, 256, n, dtype=np.uint8)
+    x = Crypt(cipher, off, size, first, sub, bytes(rng.integers(0, 256, 16, dtype=np.uint8)), iv=rng.integers(0, 256, 16 * len(off), dtype=np.uint8), c=c, k=k,
+              decrypt=True)
+    assert x.launch(ctx) == 0
+    plain = x.check(ctx)
+    assert int(ctx.read_summary(x.summary)["rbsp_bytes"]) == 16 * int(blocks.sum())
+    x.direction(False)
+    assert x.launch(ctx) == 0
+    back = x.check(ctx, before=plain)
+    assert np.array_equal(back, cipher)
+
+
+# ---- carved buffers ----------------------------------------------------------------------------------------------------------------
+
+def test_carved_buffers_at_each_accepted_alignment(ctx):
+    """every pointer of the call inside a larger allocation, at each offset from a page boundary its alignment accepts -- each goes
+    through its whole set while the others rotate; 4 KiB of known bytes lie on both sides of every buffer and are looked at
+    afterwards.  data_bytes is no multiple of 16 and the last sample ends on the last byte"""
+    import hevcbitstream_amd as hbs
+    rng = np.random.default_rng(66)
+    for j in range(len(K.OFFS8)):
+        o16 = lambda i: K.OFFS16[(j + i) % len(K.OFFS16)]          # noqa: E731
+        o8 = lambda i: K.OFFS8[(j + i) % len(K.OFFS8)]             # noqa: E731
+        entries = [[(int(rng.integers(0, 21)), int(rng.integers(0, 400))) for _ in range(int(rng.integers(0, 5)))] for _ in range(39)]
+        entries.append([(4, 16 * 70 + 9)])                  # a wavefront's entry, when decrypting, up to the buffer's last bytes
+        lead = int(rng.integers(0, 16))
+        n, off, size, first, sub = layout(entries, rng.integers(0, 9, 39).tolist() + [0], lead=lead)
+        if n % 16 == 0:
+            n, off, size, first, sub = layout(entries, rng.integers(0, 9, 39).tolist() + [0], lead=lead + 1)
+        assert n % 16 and int(off[-1] + size[-1]) == n
+        c, k = PATTERNS[j % len(PATTERNS)]
+        decrypt, whole, const = bool(j % 2), bool(j % 3 == 0), j % 4 == 3
+        data, key, ns = rng.integers(0, 256, n, dtype=np.uint8), bytes(rng.integers(0, 256, 16, dtype=np.uint8)), len(off)
+        iv, iv0 = rng.integers(0, 256, 16 * ns, dtype=np.uint8), bytes(rng.integers(0, 256, 16, dtype=np.uint8))
+        want, done = R.crypt_many(data, off, size, first, sub, key, iv=None if const else iv, iv0=iv0 if const else None, c=c, k=k, whole=whole, decrypt=decrypt)
+        cd = K.Carved(n, o16(0), CAN, K.PAD, True).put(data)
+        co = K.Carved(ns * 8, o8(1), 0xFF, K.PAD, True).put(off)
+        cz = K.Carved(ns * 8, o8(4), 0xFF, K.PAD, True).put(size)
+        cf = K.Carved((ns + 1) * 8, o8(7), 0xFF, K.PAD, True).put(first)
+        cs = K.Carved(len(sub) * 8, o8(9), 0xFF, K.PAD, True).put(sub)
+        ci = K.Carved(ns * 16, o16(3), CAN, K.PAD, True).put(iv)
+        cm = K.Carved(64, o16(5), 0xEE, K.PAD, True)
+        prm = hbs.cbcs_params(key, iv0=iv0 if const else None, flags=(hbs.CBCS_DECRYPT if decrypt else 0) | (hbs.CBCS_WHOLE_RUNS if whole else 0),
+                              crypt_byte_block=c, skip_byte_block=k)
+        assert ctx.cbcs_crypt_async(cd.view, n, co.view, cz.view, ns, cf.view, cs.view, ci.view, prm, cm.view) == 0, j
+        summary_matches(ctx.read_summary(cm.view), dict(error=0, nal_count=len(sub), nal_found=ns, rbsp_bytes=done, stream_bytes=n, stop_reason=0,
+                                                        reserved=[0, 0, 0]))
+        assert np.array_equal(cd.get(), want) and np.array_equal(ci.get(), iv), j
+        for name, cv in (("data", cd), ("sample_off", co), ("sample_size", cz), ("sub_first", cf), ("sub", cs), ("iv", ci), ("summary", cm)):
+            assert cv.intact(), (j, name, cv.damage())

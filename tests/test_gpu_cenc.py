@@ -5,10 +5,12 @@ tolerances.  The crypt kernel takes 64 KiB of protected bytes a workgroup and wa
 import numpy as np
 import pytest
 
+from tests import _carve as K
 from tests import _cenc_ref as R
 
 pytestmark = pytest.mark.gpu
 CAN = 0xC3
+RANGES, STEP, TILE = 1024, 256, 64 * 1024
 H = bytes.fromhex
 KEY_38A = H("2b7e151628aed2a6abf7158809cf4f3c")
 STRADDLE = [(5, 7), (3, 30), (0, 1), (65535, 0), (2, 11), (0, 0), (1, 16)]
@@ -38,6 +40,17 @@ def fresh_summary():
 def summary_dict(s):
     return dict(error=int(s["error"]), nal_count=int(s["nal_count"]), nal_found=int(s["nal_found"]), rbsp_bytes=int(s["rbsp_bytes"]),
                 stream_bytes=int(s["stream_bytes"]), stop_reason=int(s["stop_reason"]), reserved=[int(x) for x in s["reserved"]])
+
+
+def summary_matches(s, want):
+    """every field the reference gives: under HBS_E_ARG hbs_cenc_subsamples' "counts mean nothing", and the reference leaves them out
+    (a None in its reserved[])"""
+    got = summary_dict(s)
+    for k, v in want.items():
+        if k == "reserved":
+            assert all(x is None or g == x for g, x in zip(got[k], v)), (got, want)
+        else:
+            assert got[k] == v, (k, got, want)
 
 
 def layout(entries_per_sample, gaps, lead=0):
@@ -499,3 +512,239 @@ def test_one_replay_of_subsamples_from_a_graph(ctx):
         assert np.array_equal(got[: 8 * len(w["sub"])].view(R.SUBSAMPLE), w["sub"]) and (got[8 * len(w["sub"]):] == CAN).all()
         assert np.array_equal(p.d_first.cpu().numpy()[: 8 * (n_aus + 1)].view(np.uint64), w["sub_first"])
     replay(lambda: p.launch(ctx, sub, cap=2048), load, check, ctx)
+
+
+# ---- more entries than one step a range ------------------------------------------------------------------------------------------
+
+def cut_table(rng, clear, protect, n_samples, lead, gaps):
+    """samples cut at random entries of (clear, protect), `gaps` bytes between them -> (data_bytes, off, size, first, sub)"""
+    E = len(clear)
+    first = np.concatenate([[0], np.sort(rng.choice(np.arange(1, E), size=n_samples - 1, replace=False)), [E]])
+    total = np.concatenate([[0], np.cumsum(clear + protect)])
+    size = total[first[1:]] - total[first[:-1]]
+    off = lead + np.concatenate([[0], np.cumsum(size + gaps)[:-1]])
+    sub = np.zeros(E, dtype=R.SUBSAMPLE)
+    sub["clear"], sub["protect"] = clear, protect
+    return int(off[-1] + size[-1] + gaps[-1]), off.astype(np.uint64), size.astype(np.uint64), first.astype(np.uint64), sub
+
+
+def steps_skipped(sub):
+    """(the tiles of 64 KiB of protected bytes whose first byte lies behind the first 256 entries of its range, the tiles): for those
+    the crypt kernel's first step ends in front of the tile and is skipped"""
+    E = len(sub)
+    K = np.concatenate([[0], np.cumsum(sub["protect"].astype(np.int64))])
+    begin = np.array([E // RANGES * g + E % RANGES * g // RANGES for g in range(RANGES)])
+    t0 = TILE * np.arange((int(K[-1]) + TILE - 1) // TILE)
+    first = begin[np.searchsorted(K[begin], t0, side="right") - 1]
+    return int((K[np.minimum(first + STEP, E)] <= t0).sum()), len(t0)
+
+
+@pytest.mark.parametrize("per_range,clear_hi,protect_hi", ((STEP, 8, 40), (700, 2, 3)), ids=("257-a-range", "701-a-range"))
+def test_more_entries_than_one_step_a_range(ctx, per_range, clear_hi, protect_hi):
+    """more than 256 entries in a range, in 64 samples cut at random entries: the crypt kernel's walk goes on step after step to the
+    tile's end (13 steps a tile, and 170), skips a first step that ends in front of the tile -- 2 of the 81 tiles with 256 or 257
+    entries a range, 11 of 17 with 700 or 701 -- and a keystream block's byte walk goes on into the entries of the next step"""
+    rng = np.random.default_rng(5151 + per_range - STEP)
+    E = RANGES * per_range + 1000
+    n, off, size, first, sub = cut_table(rng, rng.integers(0, clear_hi + 1, E), rng.integers(0, protect_hi + 1, E), 64, 5, rng.integers(0, 9, 64))
+    protected = int(sub["protect"].astype(np.int64).sum())
+    skipped, tiles = steps_skipped(sub)
+    assert (skipped, tiles, n) == ((2, 81, 6328795) if per_range == STEP else (11, 17, 1796337)) and (sub["protect"] == 0).sum() > 1000
+    data = rng.integers(0, 256, n, dtype=np.uint8)
+    c = Crypt(data, off, size, first, sub, bytes(rng.integers(0, 256, 16, dtype=np.uint8)), iv=rng.integers(0, 256, 16 * len(off), dtype=np.uint8))
+    assert c.launch(ctx) == 0
+    got, _ = c.check(ctx)
+    assert int(ctx.read_summary(c.summary)["rbsp_bytes"]) == protected and not np.array_equal(got, data)
+    c.summary.fill_(0x5A)
+    assert c.launch(ctx) == 0
+    c.check(ctx, before=got)
+    assert np.array_equal(c.data(), data)
+
+
+# ---- tile edges --------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("lead", (32, 45))
+@pytest.mark.parametrize("k", (0, 1, 15, 16, 17))
+def test_a_sample_begins_k_bytes_in_front_of_a_tile(ctx, k, lead):
+    """sample 0 protects 65 536 - k bytes in one entry, so the protected bytes of sample 1 -- the short ranges and the fillers of
+    STRADDLE -- begin k bytes in front of the second tile; sample 2 protects nothing, sample 3 40 bytes"""
+    rng = np.random.default_rng(600 + 32 * k + lead)
+    samples = [[(3, TILE - k)], STRADDLE, [(9, 0), (4, 0)], [(2, 40)]]
+    n, off, size, first, sub = layout(samples, [5, 0, 7, 3], lead=lead)
+    data = rng.integers(0, 256, n, dtype=np.uint8)
+    c = Crypt(data, off, size, first, sub, bytes(rng.integers(0, 256, 16, dtype=np.uint8)), iv=rng.integers(0, 256, 16 * 4, dtype=np.uint8))
+    assert c.launch(ctx) == 0
+    got, _ = c.check(ctx)
+    inside = np.zeros(n, dtype=bool)                        # by hand: the protected ranges, entry by entry
+    for s, entries in enumerate(samples):
+        p = int(off[s])
+        for clear, protect in entries:
+            inside[p + clear: p + clear + protect] = True
+            p += clear + protect
+    assert inside.sum() == TILE - k + 65 + 40 == int(ctx.read_summary(c.summary)["rbsp_bytes"])
+    assert np.array_equal(got[~inside], data[~inside])
+    for s, total in ((0, TILE - k), (1, 65), (3, 40)):       # one keystream a sample, no byte of it skipped
+        mine = inside & (np.arange(n) >= int(off[s])) & (np.arange(n) < int(off[s] + size[s]))
+        assert np.array_equal(got[mine], data[mine] ^ R.keystream(c.key, bytes(c.iv[16 * s: 16 * s + 16]), total)), s
+
+
+# ---- offsets above 2^32 ------------------------------------------------------------------------------------------------------------
+
+def test_samples_around_offset_4gib(ctx):
+    """as tests/test_gpu_cbcs.py::test_samples_around_offset_4gib: the same allocation, the same first and last window; the middle
+    window begins 68 KiB earlier, so that the sample with a (65535, 0) filler lies inside what is compared.  Both iv_modes; the
+    second call of each restores the windows"""
+    import torch
+    import hevcbitstream_amd as hbs
+    rng = np.random.default_rng(4097)
+    G, total = 1 << 32, (1 << 32) + (64 << 20)
+    big = torch.empty(total, dtype=torch.uint8, device="cuda")
+    mid = G - 8192 - 69632
+    windows = [(0, 4096), (mid, 69632 + 16384), (total - 4096, 4096)]
+    placed = [(0, 100, [(9, 16 * 21 + 5)]), (1, 11, [(65535, 0), (7, 100), (0, 0), (3, 29)]), (1, 69632 + 1000, [(3, 160), (0, 75)]),
+              (1, 69632 + 8192 - 1500, [(11, 16 * 180 + 2)]),                                              # lies across 2^32
+              (1, 69632 + 8192 + 1500, [(0, 16 * 70)]), (1, 69632 + 8192 + 3000, [(5, 33)]), (2, 4096 - 16 * 30 - 7, [(7, 16 * 30)])]
+    off = np.array([windows[w][0] + o for w, o, _ in placed], dtype=np.uint64)
+    _, _, size, first, sub = layout([e for _, _, e in placed], [0] * len(placed))
+    assert int(off[3]) < G < int(off[3] + size[3]) and int(off[-1] + size[-1]) == total and int(off[1] + size[1]) <= int(off[2])
+    plain = [rng.integers(0, 256, z, dtype=np.uint8) for _, z in windows]
+    for (lo, z), h in zip(windows, plain):
+        big[lo: lo + z] = torch.from_numpy(h).cuda()
+    key, iv = bytes(rng.integers(0, 256, 16, dtype=np.uint8)), rng.integers(0, 256, 16 * len(off), dtype=np.uint8)
+    iv0 = H("fffffffffffffffd")
+    d_off, d_size, d_first, d_sub, d_iv = dev(off), dev(size), dev(first), dev(sub), dev(iv)
+    for mode in (0, 1):
+        host = plain
+        d_ivo = torch.full((16 * len(off),), CAN, dtype=torch.uint8, device="cuda")
+        for again in (False, True):
+            want, used = [], {}
+            for w in range(len(windows)):                   # the reference, window by window, on offsets rebased to the window
+                mine = [i for i, (pw, _, _) in enumerate(placed) if pw == w]
+                _, _, wsize, wfirst, wsub = layout([placed[i][2] for i in mine], [0] * len(mine))
+                woff = np.array([placed[i][1] for i in mine], dtype=np.uint64)
+                ivs = np.concatenate([np.frombuffer(R.sample_ctr(i, iv, None if mode == 0 else iv0), dtype=np.uint8) for i in mine])
+                out, done, _ = R.crypt(host[w], woff, wsize, wfirst, wsub, key, iv=ivs)
+                want.append((out, done))
+                used.update({i: ivs[16 * j: 16 * j + 16] for j, i in enumerate(mine)})
+            summary = fresh_summary()
+            prm = hbs.cenc_params(key, iv0=None if mode == 0 else iv0)
+            assert ctx.cenc_crypt_async(big, total, d_off, d_size, len(off), d_first, d_sub, d_iv if mode == 0 else d_ivo, prm, summary) == 0
+            assert summary_dict(ctx.read_summary(summary)) == dict(error=0, nal_count=len(sub), nal_found=len(off), rbsp_bytes=sum(d for _, d in want),
+                                                                   stream_bytes=total, stop_reason=0, reserved=[0, 0, 0])
+            for (lo, z), (out, _) in zip(windows, want):
+                got = big[lo: lo + z].cpu().numpy()
+                assert np.array_equal(got, out), (mode, again, lo, np.flatnonzero(got != out)[:8])
+            if mode == 1:
+                assert np.array_equal(d_ivo.cpu().numpy(), np.concatenate([used[i] for i in range(len(off))]))
+            if not again:
+                assert not np.array_equal(want[1][0], host[1])
+                host = [out for out, _ in want]
+        assert all(np.array_equal(out, p) for (out, _), p in zip(want, plain)), mode
+
+
+# ---- carved buffers ----------------------------------------------------------------------------------------------------------------
+
+def small_table(rng, n_samples, lead):
+    """a few dozen samples of 0 to 4 entries; data_bytes is no multiple of 16 and the last sample ends on the last byte"""
+    entries = [[(int(rng.integers(0, 21)), int(rng.integers(0, 121))) for _ in range(int(rng.integers(0, 5)))] for _ in range(n_samples - 1)] + [[(4, 57)]]
+    n, off, size, first, sub = layout(entries, rng.integers(0, 9, n_samples - 1).tolist() + [0], lead=lead)
+    if n % 16 == 0:
+        return small_table(rng, n_samples, lead + 1)
+    assert int(off[-1] + size[-1]) == n
+    return n, off, size, first, sub
+
+
+def test_carved_buffers_at_each_accepted_alignment(ctx):
+    """every pointer of hbs_cenc_crypt and hbs_cenc_subsamples inside a larger allocation, at each offset from a page boundary its
+    alignment accepts -- each pointer goes through its whole set while the others rotate; 4 KiB of known bytes lie on both sides
+    of every buffer and are looked at afterwards"""
+    import hevcbitstream_amd as hbs
+    rng = np.random.default_rng(66)
+    for k in range(len(K.OFFS8)):
+        o16 = lambda j: K.OFFS16[(k + j) % len(K.OFFS16)]          # noqa: E731
+        o8 = lambda j: K.OFFS8[(k + j) % len(K.OFFS8)]             # noqa: E731
+        n, off, size, first, sub = small_table(rng, 40, int(rng.integers(0, 16)))
+        data, key, ns = rng.integers(0, 256, n, dtype=np.uint8), bytes(rng.integers(0, 256, 16, dtype=np.uint8)), len(off)
+        mode = k % 2
+        iv, iv0 = rng.integers(0, 256, 16 * ns, dtype=np.uint8), bytes(rng.integers(0, 256, 8, dtype=np.uint8))
+        want, done, used = R.crypt(data, off, size, first, sub, key, iv=None if mode else iv, iv0=iv0 if mode else None)
+        cd = K.Carved(n, o16(0), CAN, K.PAD, True).put(data)
+        co = K.Carved(ns * 8, o8(1), 0xFF, K.PAD, True).put(off)
+        cz = K.Carved(ns * 8, o8(4), 0xFF, K.PAD, True).put(size)
+        cf = K.Carved((ns + 1) * 8, o8(7), 0xFF, K.PAD, True).put(first)
+        cs = K.Carved(len(sub) * 8, o8(9), 0xFF, K.PAD, True).put(sub)
+        ci = K.Carved(ns * 16, o16(3), CAN, K.PAD, True)
+        if not mode:
+            ci.put(iv)
+        cm = K.Carved(64, o16(5), 0xEE, K.PAD, True)
+        prm = hbs.cenc_params(key, iv0=iv0 if mode else None)
+        assert ctx.cenc_crypt_async(cd.view, n, co.view, cz.view, ns, cf.view, cs.view, ci.view, prm, cm.view) == 0, k
+        summary_matches(ctx.read_summary(cm.view), dict(error=0, nal_count=len(sub), nal_found=ns, rbsp_bytes=done, stream_bytes=n, stop_reason=0,
+                                                        reserved=[0, 0, 0]))
+        assert np.array_equal(cd.get(), want) and np.array_equal(ci.get(), used.reshape(-1)), k
+        for name, c in (("data", cd), ("sample_off", co), ("sample_size", cz), ("sub_first", cf), ("sub", cs), ("iv", ci), ("summary", cm)):
+            assert c.intact(), (k, name, c.damage())
+    for k in range(16):                                     # hbs_cenc_subsamples: d_keep at 0 to 15, d_nal_au through OFFS4
+        o16 = lambda j: K.OFFS16[(k + j) % len(K.OFFS16)]          # noqa: E731
+        o8 = lambda j: K.OFFS8[(k + j) % len(K.OFFS8)]             # noqa: E731
+        L = (1, 2, 4)[k % 3]
+        st = build_stream(700 + k, L, n_nals=300)
+        p = Plan(st, L, k % 2, 96, True)
+        w = p.want()
+        nn, total = len(st["starts"]), len(w["sub"])
+        idx = np.zeros(nn, dtype=NAL_ENTRY)
+        idx["start"], idx["end"] = st["starts"], st["ends"]
+        cs = K.Carved(len(st["stream"]), o16(0), 0x3C, K.PAD, True).put(st["stream"])
+        cx = K.Carved(nn * 32, o8(2), 0xFF, K.PAD, True).put(idx)
+        ck = K.Carved(nn, k, 0xFF, K.PAD, True).put(st["keep"])
+        ca = K.Carved(nn * 4, K.OFFS4[k % len(K.OFFS4)], 0xFF, K.PAD, True).put(st["nal_au"])
+        cp = K.Carved(nn * 8, o8(5), 0xFF, K.PAD, True).put(st["payload_off"])
+        cf = K.Carved((st["n_aus"] + 1) * 8, o8(8), CAN, K.PAD, True)
+        cu = K.Carved(total * 8, o8(0), CAN, K.PAD, True)
+        cm = K.Carved(64, o16(4), 0xEE, K.PAD, True)
+        assert ctx.cenc_subsamples_async(cs.view, len(st["stream"]), cx.view, nn, ca.view, st["n_aus"], p.prm, cf.view, cu.view, cm.view, keep=ck.view,
+                                         payload_off=cp.view, sub_cap=total) == 0, k
+        assert summary_dict(ctx.read_summary(cm.view)) == p.summary_of(w), k
+        assert np.array_equal(cu.get().view(R.SUBSAMPLE), w["sub"]) and np.array_equal(cf.get().view(np.uint64), w["sub_first"]), k
+        for name, c in (("stream", cs), ("index", cx), ("keep", ck), ("nal_au", ca), ("payload_off", cp), ("sub_first", cf), ("sub", cu), ("summary", cm)):
+            assert c.intact(), (k, name, c.damage())
+
+
+def test_the_nearest_misalignment_of_each_pointer_is_refused(ctx):
+    """+8 on a 16-byte pointer, +4 on an 8-byte one, +2 and +1 on d_nal_au: HBS_E_ARG at once, and every output and the summary hold
+    what they were filled with"""
+    import torch
+    import hevcbitstream_amd as hbs
+    rng = np.random.default_rng(67)
+    n, off, size, first, sub = small_table(rng, 40, 3)
+    x = Crypt(rng.integers(0, 256, n, dtype=np.uint8), off, size, first, sub, bytes(range(16)), iv0=bytes(8))
+    x.d_data = torch.cat([x.d_data, torch.full((64,), CAN, dtype=torch.uint8, device="cuda")])
+    prm = x.prm.ctypes.data
+    base = dict(data=x.d_data.data_ptr(), off=x.d_off.data_ptr(), size=x.d_size.data_ptr(), first=x.d_first.data_ptr(), sub=x.d_sub.data_ptr(),
+                iv=x.d_iv.data_ptr(), summary=x.summary.data_ptr())
+    order = ("data", "off", "size", "first", "sub", "iv", "summary")
+
+    def crypt(**shift):
+        a = {name: base[name] + shift.get(name, 0) for name in order}
+        return ctx.lib.hbs_cenc_crypt(ctx.h, a["data"], n - 16, a["off"], a["size"], 0 if shift else x.n, a["first"], a["sub"], a["iv"], prm, a["summary"])
+    # (the shifted calls pass no samples and 16 bytes less, so that a call that were accepted would stay inside the buffers)
+    for name, by in (("data", 8), ("iv", 8), ("summary", 8), ("off", 4), ("size", 4), ("first", 4), ("sub", 4)):
+        assert crypt(**{name: by}) == R.E_ARG, name
+    torch.cuda.synchronize()
+    assert (x.summary.cpu().numpy() == 0x5A).all() and np.array_equal(x.data(), x.host[0]) and (x.d_iv.cpu().numpy() == CAN).all()
+    st = build_stream(800, 4, n_nals=300)
+    p = Plan(st, 4, 0, 96, True)
+    total, nn = len(p.want()["sub"]), len(st["starts"])
+    d_sub = torch.full((total * 8 + 64,), CAN, dtype=torch.uint8, device="cuda")
+    base = dict(stream=p.d_stream.data_ptr(), index=p.d_idx.data_ptr(), keep=p.d_keep.data_ptr(), nal_au=p.d_au.data_ptr(), po=p.d_po.data_ptr(),
+                first=p.d_first.data_ptr(), sub=d_sub.data_ptr(), summary=p.summary.data_ptr())
+
+    def plan(**shift):
+        a = {name: v + shift.get(name, 0) for name, v in base.items()}
+        return ctx.lib.hbs_cenc_subsamples(ctx.h, a["stream"], len(st["stream"]) - 16, a["index"], nn - 1, a["keep"], a["nal_au"], st["n_aus"], a["po"],
+                                           p.prm.ctypes.data, a["first"], a["sub"], total, a["summary"])
+    for name, by in (("stream", 8), ("summary", 8), ("index", 4), ("po", 4), ("first", 4), ("sub", 4), ("nal_au", 2), ("nal_au", 1)):
+        assert plan(**{name: by}) == R.E_ARG, (name, by)
+    torch.cuda.synchronize()
+    assert (p.summary.cpu().numpy() == 0x5A).all() and (d_sub.cpu().numpy() == CAN).all() and (p.d_first.cpu().numpy() == CAN).all()
+    assert plan(keep=1) == 0                                # d_keep takes any address

@@ -4,17 +4,22 @@ written it is the previous call's, in that call's layout.  Here calls of differe
 on one context, and every one of them is held, byte for byte and field for field, against the plain loops of tests/_*_ref.py:
 never against a fresh context, which could be wrong in the same way.  The cases are tests/_seq_cases.py's; tests/test_seq_cases.py
 holds on the CPU that they are what the sequences need.  alloc, launch, verify and step also serve the RTP and MP4 calls, whose
-sequences are in tests/test_gpu_sequences_rtp_mp4.py."""
+sequences are in tests/test_gpu_sequences_rtp_mp4.py, and hbs_au_times, hbs_cenc_subsamples, hbs_cenc_crypt and hbs_cbcs_crypt, whose
+sequences are in tests/test_gpu_sequences_times_crypt.py."""
 import numpy as np
 import pytest
 
+from tests import _au_times_ref as T
 from tests import _mp4_ref as MF
 from tests import _rtp_order_ref as RO
 from tests import _rtp_ref as R
 from tests import _rtp_unpack_ref as RU
 from tests import _seq_cases as S
 from tests import _tsmux_ref as TSM
+from tests import test_gpu_au_times as TA
 from tests import test_gpu_auins as AI
+from tests import test_gpu_cbcs as TY
+from tests import test_gpu_cenc as TC
 from tests import test_gpu_lenpref as LP
 from tests import test_gpu_mp4 as TF
 from tests import test_gpu_mp4_read as TQ
@@ -36,10 +41,15 @@ OUTPUTS = dict(a2l=(("out", 0), ("io", 1), ("so", 2)), l2a=(("out", 0), ("so", 1
                rtp=(("out", 0), ("no", 1), ("npk", 2)), rtpa=(("out", 0), ("no", 1), ("npk", 2)), rtpu=(("out", 0), ("io", 1), ("nau", 2), ("ats", 3)),
                rtpo=(("ooff", 0), ("osize", 1), ("src", 2), ("ext", 3)), mp4f=(("out", 0), ("so", 1), ("ss", 2), ("fr", 3)),
                mp4s=(("so", 0), ("ss", 1), ("dts", 2), ("pts", 3), ("sfl", 4), ("fr", 5)), stbl=(("so", 0), ("ss", 1), ("dts", 2), ("pts", 3), ("sfl", 4)),
-               stblw=(("out", 0), ("tab", 1)))
+               stblw=(("out", 0), ("tab", 1)),
+               aut=(("dts", 0), ("pts", 1), ("order", 2), ("display", 3)), csub=(("sf", 0), ("sub", 1)), cenc=(("data", 0), ("ivo", 1)),
+               cbcs=(("data", 0),), cbcsd=(("data", 0),))
 PER_NAL_TABLES = ("io", "src", "nau")                # of hbs_au_insert: d_index_out, d_nal_src, d_nal_au_out
-PLAN_WRITES = {"stblw": ("tab",)}                    # "d_out == NULL: plan only -- ... the summary and d_tables are written"
-SUMMARY_MATCHES = dict(a2l=LP, l2a=LP, tsd=TS, tsm=TM, ins=AI, rtp=TR, rtpa=TR, rtpu=TU, rtpo=TO, mp4f=TF, mp4s=TQ, stbl=TB, stblw=TW)
+# "d_out == NULL: plan only -- ... the summary and d_tables are written"; "d_sub == NULL: plan only -- the summary and d_sub_first are written"
+PLAN_WRITES = {"stblw": ("tab",), "csub": ("sf",)}
+IN_PLACE = ("data",)                                 # the buffer hbs_cenc_crypt and hbs_cbcs_crypt work in: uploaded, and compared after an error too
+SUMMARY_MATCHES = dict(a2l=LP, l2a=LP, tsd=TS, tsm=TM, ins=AI, rtp=TR, rtpa=TR, rtpu=TU, rtpo=TO, mp4f=TF, mp4s=TQ, stbl=TB, stblw=TW,
+                       aut=TA, csub=TC, cenc=TC, cbcs=TY, cbcsd=TY)
 
 
 def new_ctx():
@@ -74,7 +84,15 @@ def alloc(c, tables=True, ts=None, given=None):
     a = c.a
     b = dict(summary=filled(SUMMARY.itemsize, 0xEE))
     held = lambda name, make: given[name] if given and name in given else make()          # noqa: E731
-    if c.call in ("rtp", "rtpa"):
+    if c.call == "aut":
+        b.update(au=held("au", lambda: dev(a["au"])), prm=T.params_record(**a["kw"]))
+    elif c.call == "csub":
+        b.update(stream=held("stream", lambda: dev(a["stream"])), index=held("index", lambda: dev(a["index"])),
+                 nal_au=held("nal_au", lambda: dev(a["nal_au"])), keep=opt(a["keep"]), po=held("po", lambda: opt(a["po"])))
+    elif c.call in S.CRYPT_CALLS:
+        b.update(off=held("off", lambda: dev(a["off"])), size=held("size", lambda: dev(a["size"])), first=held("first", lambda: dev(a["first"])),
+                 sub=held("sub", lambda: dev(a["sub"])), iv=opt(a["iv"]))
+    elif c.call in ("rtp", "rtpa"):
         b.update(stream=dev(a["stream"]), index=dev(a["index"]), nal_au=opt(a["nal_au"]), pts=opt(a["pts"]), prm=R.params_record(a["prm"]))
     elif c.call in ("rtpu", "rtpo"):
         b.update(data=held("data", lambda: dev(a["data"])), off=held("off", lambda: dev(a["off"])), size=held("size", lambda: dev(a["size"])),
@@ -99,7 +117,12 @@ def alloc(c, tables=True, ts=None, given=None):
     else:
         b.update(stream=dev(a["stream"]), index=dev(a["index"]), parsed=dev(a["parsed"]), au=dev(a["au"]), nal_au=dev(a["nal_au"]))
     for name, _ in OUTPUTS[c.call]:
+        if c.call in S.CALLS3 and name not in c.room:          # a table hbs_au_times is not asked for; no d_iv that receives the counter blocks
+            b[name] = None
+            continue
         b[name] = canary(c.room[name]) if tables or name not in PER_NAL_TABLES else None
+    if c.call in S.CRYPT_CALLS:                               # the data, fresh, in front of its canary (or the device's own: `given`)
+        b["data"][: len(a["data"])].copy_(held("data", lambda: dev(a["data"]))[: len(a["data"])])
     return b
 
 
@@ -108,6 +131,21 @@ def launch(ctx, c, b, plan=False):
     a, caps = c.a, c.caps
     o = {name: None if plan else b[name] for name, _ in OUTPUTS[c.call]}
     cap = lambda name: 0 if plan else caps[name]          # noqa: E731
+    if c.call == "aut":
+        return ctx.au_times_async(b["au"], len(a["au"]), b["prm"], b["summary"], dts=o["dts"], pts=o["pts"], order=o["order"], display=o["display"])
+    if c.call == "csub":                                  # (a plan writes d_sub_first)
+        import hevcbitstream_amd as hbs
+        return ctx.cenc_subsamples_async(b["stream"], len(a["stream"]), b["index"], len(a["index"]), b["nal_au"], a["n_aus"],
+                                         hbs.cenc_plan_params(length_size=a["L"], flags=a["flags"], clear_lead=a["clear_lead"]), b["sf"], o["sub"],
+                                         b["summary"], keep=b["keep"], payload_off=b["po"], sub_cap=cap("sub_cap"))
+    if c.call in S.CRYPT_CALLS:
+        import hevcbitstream_amd as hbs
+        tables = (b["data"], len(a["data"]), b["off"], b["size"], len(a["off"]), b["first"], b["sub"])
+        if c.call == "cenc":
+            return ctx.cenc_crypt_async(*tables, b["ivo"] if a["ivo"] else b["iv"], hbs.cenc_params(a["key"], iv0=a["iv0"]), b["summary"])
+        flags = (hbs.CBCS_DECRYPT if c.call == "cbcsd" else 0) | (hbs.CBCS_WHOLE_RUNS if a["whole"] else 0)
+        prm = hbs.cbcs_params(a["key"], iv0=a["iv0"], flags=flags, crypt_byte_block=a["c"], skip_byte_block=a["k"])
+        return ctx.cbcs_crypt_async(*tables, b["iv"], prm, b["summary"])
     if c.call in ("rtp", "rtpa"):
         return ctx.rtp_pack_async(b["stream"], len(a["stream"]), b["index"], len(a["index"]), b["nal_au"], a["n_aus"], b["pts"], b["prm"], o["out"],
                                   o["no"], o["npk"], b["summary"], out_cap=cap("out_cap"))
@@ -162,7 +200,8 @@ def verify(ctx, c, b, plan=False):
     if c.named is not None:                                 # the word the header gives this fault, where this kind of call looks for it
         word, value = c.named
         if c.in_plan or not plan:
-            assert int(s["error"]) == S.E_ARG and int(s["reserved"][word]) == value, (c, s)
+            error = c.error if c.call in S.CALLS3 else S.E_ARG          # (hbs_au_times names the AU under HBS_E_DEPTH)
+            assert int(s["error"]) == error and int(s["reserved"][word]) == value, (c, s)
         else:
             assert int(s["error"]) == 0, (c, s)
     elif c.bad is not None:                                 # this call's own entry plus one, where the call names it
@@ -172,7 +211,7 @@ def verify(ctx, c, b, plan=False):
         if b[name] is None:
             continue
         g = b[name].cpu().numpy()
-        if (ws["error"] and refused_writes_nothing) or (plan and name not in PLAN_WRITES.get(c.call, ())):
+        if (ws["error"] and refused_writes_nothing and name not in IN_PLACE) or (plan and name not in PLAN_WRITES.get(c.call, ())):
             assert (g == CAN).all(), "%s written by %s" % (name, "a plan" if plan else "a call that reports error %d" % ws["error"])
             continue
         x = np.ascontiguousarray(w[place])
