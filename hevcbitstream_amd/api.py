@@ -84,6 +84,11 @@ MP4_INIT_PARAMS = np.dtype([("track_id", "<u4"), ("timescale", "<u4"), ("width",
                             ("chroma_format_idc", "<i4"), ("bit_depth_luma", "<i4"), ("bit_depth_chroma", "<i4")])
 MP4_CUT_AT_IRAP = 1
 MP4_HEV1 = 1
+MP4_PROTECT_PARAMS = np.dtype([("iv_size", "<u4"), ("flags", "<u4"), ("reserved", "<u4", (6,))])
+MP4_TENC = np.dtype([("scheme", "<u4"), ("crypt_byte_block", "u1"), ("skip_byte_block", "u1"), ("iv_size", "u1"), ("constant_iv_size", "u1"),
+                     ("kid", "u1", (16,)), ("constant_iv", "u1", (16,)), ("reserved", "<u4", (6,))])
+MP4_SCHEME_CENC = 0x63656E63      # 'cenc'
+MP4_SCHEME_CBCS = 0x63626373      # 'cbcs'
 # layout of hbs_mp4_read_params / hbs_mp4_track (hbs_mp4_samples, hbs_mp4_init_read_host)
 MP4_READ_PARAMS = np.dtype([("flags", "<u4"), ("track_id", "<u4"), ("trex_duration", "<u4"), ("trex_size", "<u4"), ("trex_flags", "<u4"),
                             ("reserved", "<u4", (3,))])
@@ -135,7 +140,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_mp4_fragment", "hbs_mp4_fragment_bytes_host", "hbs_mp4_init_host",
            "hbs_mp4_samples", "hbs_mp4_init_read_host", "hbs_mp4_stbl_samples", "hbs_mp4_stbl_find_host",
            "hbs_mp4_track_read_host",
-           "hbs_mp4_stbl_write", "hbs_mp4_stbl_write_bytes_host", "hbs_mp4_moov_host"]
+           "hbs_mp4_stbl_write", "hbs_mp4_stbl_write_bytes_host", "hbs_mp4_moov_host",
+           "hbs_mp4_protect", "hbs_mp4_protect_bytes_host", "hbs_mp4_init_protect_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -331,6 +337,14 @@ def load_library():
     lib.hbs_mp4_stbl_write_bytes_host.restype = C.c_uint64
     lib.hbs_mp4_moov_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
     lib.hbs_mp4_moov_host.restype = C.c_int64
+    lib.hbs_mp4_protect.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hbs_mp4_protect.restype = C.c_int
+    lib.hbs_mp4_protect_bytes_host.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+    lib.hbs_mp4_protect_bytes_host.restype = C.c_uint64
+    lib.hbs_mp4_init_protect_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                              C.c_uint64]
+    lib.hbs_mp4_init_protect_host.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -541,6 +555,50 @@ def mp4_moov(nals, duration, tables_bytes, **kw):
     that hbs_mp4_stbl_write writes complete the moov.  duration: reserved[1] of that call's summary.  The other arguments are
     mp4_init's.  Raises HbsError for what the call refuses."""
     return mp4_init(nals, _moov=(duration, tables_bytes), **kw)
+
+
+def mp4_protect_params(iv_size=8, flags=0):
+    """an hbs_mp4_protect_params record (ndarray[MP4_PROTECT_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=MP4_PROTECT_PARAMS)
+    p["iv_size"], p["flags"] = iv_size, flags
+    return p
+
+
+def mp4_protect_bytes(samples, entries, iv_size):
+    """hbs_mp4_protect_bytes_host: the bytes a fragment of `samples` samples with `entries` subsample entries grows by"""
+    return int(load_library().hbs_mp4_protect_bytes_host(int(samples), int(entries), int(iv_size)))
+
+
+def mp4_init_protect(init_bytes, kid, scheme=MP4_SCHEME_CENC, iv_size=8, constant_iv=None, crypt_byte_block=0, skip_byte_block=0,
+                     pssh=(), track_id=0, tenc=None):
+    """hbs_mp4_init_protect_host: the init segment (bytes-like) with the track's sample entry turned into 'encv' with sinf /
+    frma / schm / schi / tenc, and the given whole 'pssh' boxes (bytes-like each) appended to the moov, as bytes.  kid: 16
+    bytes; constant_iv: None, or 8 or 16 bytes with iv_size 0; tenc: an ndarray[MP4_TENC] of one in place of those keywords.
+    Raises HbsError for what the call refuses."""
+    lib = load_library()
+    if tenc is None:
+        tenc = np.zeros(1, dtype=MP4_TENC)
+        tenc["scheme"], tenc["crypt_byte_block"], tenc["skip_byte_block"], tenc["iv_size"] = scheme, crypt_byte_block, skip_byte_block, iv_size
+        tenc["kid"][0] = np.frombuffer(bytes(kid), dtype=np.uint8)
+        if constant_iv is not None:
+            b = bytes(constant_iv)
+            tenc["constant_iv_size"] = len(b)
+            tenc["constant_iv"][0][: len(b)] = np.frombuffer(b, dtype=np.uint8)
+    tenc, tenc_p = _rec(tenc, MP4_TENC)
+    seg = np.frombuffer(bytes(init_bytes), dtype=np.uint8)
+    bufs = [np.frombuffer(bytes(x), dtype=np.uint8) if len(x) else np.zeros(0, dtype=np.uint8) for x in pssh]
+    ptrs = (C.c_void_p * max(len(bufs), 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    sizes = np.array([b.size for b in bufs], dtype=np.uint64)
+    args = (seg.ctypes.data_as(C.c_void_p) if seg.size else None, seg.size, int(track_id), tenc_p, C.cast(ptrs, C.c_void_p),
+            sizes.ctypes.data_as(C.c_void_p), len(bufs))
+    need = int(lib.hbs_mp4_init_protect_host(*args, None, 0))
+    if need < 0:
+        raise HbsError("hbs_mp4_init_protect_host: error %d" % need)
+    out = np.zeros(need, dtype=np.uint8)
+    got = int(lib.hbs_mp4_init_protect_host(*args, out.ctypes.data_as(C.c_void_p), need))
+    if got != need:
+        raise HbsError("hbs_mp4_init_protect_host: %d, then %d" % (need, got))
+    return out.tobytes()
 
 
 def mp4_stbl_write_params(flags=0, max_chunk_samples=0, sample_duration=0, base_time=0, data_offset=0):
@@ -1480,6 +1538,45 @@ class Context:
         s = self._run(name, self.mp4_samples_async(data, nbytes, prm, summary, moof_cap=m, sample_cap=n, sample_off=so, sample_size=ss, dts=dt,
                                                    pts=pt, sample_flags=fl, frag=fr, **kw), summary)
         return (*(_host(x, n, np.uint64) for x in (so, ss, dt, pt)), _host(fl, n, np.uint32), _host(fr, m, MP4_FRAG), s)
+
+    def mp4_protect_async(self, data, in_bytes, frag, n_frags, sub_first, sub, iv, n_samples, params, out, summary, sample_off=None,
+                          sample_size=None, frag_out=None, out_cap=None):
+        """Enqueue hbs_mp4_protect on the current torch stream.  data / frag / sub_first / sub / iv / out / summary / sample_off /
+        sample_size / frag_out are device tensors (out None: plan only; iv may be None with iv_size 0; sample_off with
+        sample_size and frag_out may be None); params is an ndarray[MP4_PROTECT_PARAMS] of one in host memory.  out_cap (bytes)
+        defaults to what out holds.  Returns the call's return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        if out_cap is None:
+            out_cap = _holds(out)
+        params, params_p = _rec(params, MP4_PROTECT_PARAMS)
+        on = bool(n_samples)
+        return self.lib.hbs_mp4_protect(self.h, _p(data) if in_bytes else None, int(in_bytes), _p(frag) if n_frags else None, int(n_frags),
+                                        _p(sub_first) if on else None, _p(sub) if on else None, _p(iv), int(n_samples), params_p, _p(out),
+                                        int(out_cap), _p(sample_off), _p(sample_size), _p(frag_out), _p(summary))
+
+    def mp4_protect(self, data, frags, sub_first, sub, iv=None, iv_size=8, in_bytes=None):
+        """Convenience: the fragments of `data` (device uint8 tensor) that `frags` names, with saiz, saio and senc in every traf.
+        frags: ndarray[MP4_FRAG]; sub_first: one uint64 per sample and one; sub: ndarray[CENC_SUBSAMPLE]; iv: None (iv_size 0) or
+        16 bytes per sample -- host arrays or device uint8 tensors of their bytes.  Plans first, allocates the exact output,
+        runs.  Returns (out device tensor, sample_off ndarray[uint64], sample_size ndarray[uint64], frags ndarray[MP4_FRAG],
+        summary record)."""
+        name = "hbs_mp4_protect"
+        d_frag, n_frags = self._dv(frags, MP4_FRAG)
+        d_first, n1 = self._dv(sub_first, np.uint64)
+        d_sub, _ = self._dv(sub, CENC_SUBSAMPLE)
+        d_iv, _ = self._dv(iv, np.uint8)
+        n = max(n1 - 1, 0)
+        prm = mp4_protect_params(iv_size=iv_size)
+        nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
+        summary = self._zeros()
+        args = (data, nbytes, d_frag, n_frags, d_first, d_sub, d_iv, n, prm)
+        s = self._run(name, self.mp4_protect_async(*args, None, summary), summary, " (sample {0}, fragment {1})")
+        need = int(s["stream_bytes"])
+        out = self._empty(max(need, 16))
+        so, ss = (self._empty(max(n, 1) * 8) for _ in range(2))
+        fr = self._empty(max(n_frags, 1) * MP4_FRAG.itemsize)
+        s = self._run(name, self.mp4_protect_async(*args, out, summary, sample_off=so, sample_size=ss, frag_out=fr, out_cap=need), summary)
+        return out[:need], _host(so, n, np.uint64), _host(ss, n, np.uint64), _host(fr, n_frags, MP4_FRAG), s
 
     def mp4_stbl_samples_async(self, data, in_bytes, tables, summary, sample_cap=0, sample_off=None, sample_size=None, dts=None, pts=None,
                                sample_flags=None):

@@ -31,6 +31,7 @@
 #include "hbs_rtpord.h"
 #include "hbs_mp4.h"
 #include "hbs_mp4rd.h"
+#include "hbs_mp4prot.h"
 #include "hbs_mp4stbl.h"
 #include "hbs_mp4stblw.h"
 
@@ -60,8 +61,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kXws    hbs_au_times' scratch
  * kCws    hbs_cenc_subsamples' scratch
  * kYws    hbs_cenc_crypt's scratch (tables about the samples and the entries; the key is never in it); hbs_cbcs_crypt's too: the
- *         same tables, and the calls of a context are ordered by its one stream */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kCws, kYws, kBufs };
+ *         same tables, and the calls of a context are ordered by its one stream
+ * kEws    hbs_mp4_protect's scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kCws, kYws, kEws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -848,6 +850,33 @@ int hbs_mp4_fragment(hbs_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
     const uint64_t most = hbs::mp4_output_bound(n_nals, n_aus, stream_bytes, a.L);
     a.tiles = d_out && n_nals ? hbs::mp4_tiles(out_cap < most ? out_cap : most) : 0;
     return carve_and_launch(c, c->buf[kPws], "hipMalloc(MP4 scratch)", a, hbs::lay_mp4, hbs::launch_mp4_fragment, "launch_mp4_fragment");
+}
+
+int hbs_mp4_protect(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const hbs_mp4_frag* d_frag, uint64_t n_frags,
+                    const uint64_t* d_sub_first, const hbs_cenc_subsample* d_sub, const uint8_t* d_iv, uint64_t n_samples,
+                    const hbs_mp4_protect_params* params, uint8_t* d_out, uint64_t out_cap,
+                    uint64_t* d_sample_off, uint64_t* d_sample_size, hbs_mp4_frag* d_frag_out, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_mp4_protect_params) == 32 && sizeof(hbs_mp4_tenc) == 64, "hbs_mp4_protect layouts");
+    if (!c || !d_summary || !hbs::mp4_protect_params_ok(params) || n_frags > 0xFFFFFFFFull || n_samples > 0xFFFFFFFFull) return HBS_E_ARG;
+    if (n_frags ? (!d_frag || (in_bytes && !d_in)) : n_samples != 0) return HBS_E_ARG;
+    if (n_samples && (!d_sub_first || !d_sub || (params->iv_size && !d_iv))) return HBS_E_ARG;
+    if ((d_sample_off == nullptr) != (d_sample_size == nullptr)) return HBS_E_ARG;
+    if (misaligned_refused(c, "input/output/fragment tables/IV/summary pointers must be 16-byte aligned, the 64-bit tables and the entries 8-byte",
+                           {d_in, d_out, d_frag, d_frag_out, d_iv, d_summary}, {d_sub_first, d_sub, d_sample_off, d_sample_size})) return HBS_E_ARG;
+    if (out_cap_refused(c, d_out, out_cap)) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::Mp4ProtArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_in; a.n = in_bytes; a.frag = d_frag; a.n_frags = n_frags;
+    a.sub_first = reinterpret_cast<const unsigned long long*>(d_sub_first); a.sub = d_sub; a.iv = d_iv; a.n_samples = n_samples;
+    a.V = params->iv_size; a.out = d_out; a.out_cap = out_cap; a.summary = d_summary;
+    if (d_out) {
+        a.sample_off = reinterpret_cast<unsigned long long*>(d_sample_off); a.sample_size = reinterpret_cast<unsigned long long*>(d_sample_size);
+        a.frag_out = d_frag_out;
+        a.tiles = n_frags ? hbs::mp4prot_tiles(out_cap) : 0;                 /* the copy's grid: the tiles out_cap has room for */
+    }
+    return carve_and_launch(c, c->buf[kEws], "hipMalloc(MP4 protect scratch)", a, hbs::lay_mp4prot, hbs::launch_mp4_protect, "launch_mp4_protect");
 }
 
 int hbs_mp4_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const void* d_seg, uint64_t seg_stride, uint64_t n_segs,

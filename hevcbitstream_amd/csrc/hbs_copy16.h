@@ -1,6 +1,6 @@
 /*
  * hbs_copy16.h -- device-only, for .hip files: what the copies that take one lane per aligned 16-byte output chunk share
- * (hbs_pieces.hip, hbs_rtp.hip, hbs_tsmux.hip, hbs_ts.hip, hbs_mp4.hip).  The fast path of a chunk that lies inside one run of source bytes:
+ * (hbs_pieces.hip, hbs_rtp.hip, hbs_tsmux.hip, hbs_ts.hip, hbs_mp4.hip, hbs_mp4prot.hip).  The fast path of a chunk that lies inside one run of source bytes:
  * load16_pair, realign, arena_store16 (hbs_wave.h).  The slow path of a chunk that holds other bytes or spans runs: pack_byte
  * for each byte, then store_chunk.  last_le finds the unit a chunk lies in, tile_first_of the unit an output tile begins in.
  */

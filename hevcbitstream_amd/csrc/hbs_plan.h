@@ -1,5 +1,5 @@
 /* hbs_plan.h -- device-only: the scans of a "count, scan, place" plan (hbs_filter.hip, hbs_lenpref.hip, hbs_ts.hip,
- * hbs_tsmux.hip, hbs_rtp.hip, hbs_rtpun.hip, hbs_rtpord.hip, hbs_auins.hip, hbs_mp4.hip, hbs_mp4rd.hip): over the lanes of a workgroup the exclusive sums (block_scan), the
+ * hbs_tsmux.hip, hbs_rtp.hip, hbs_rtpun.hip, hbs_rtpord.hip, hbs_auins.hip, hbs_mp4.hip, hbs_mp4rd.hip, hbs_mp4prot.hip): over the lanes of a workgroup the exclusive sums (block_scan), the
  * exclusive maxima (block_excl_max) and the sums that restart at marked lanes (block_seg_excl, seg_scan_parts).  A count kernel leaves 8 words a workgroup -- N sums, then a word that says what was
  * wrong -- and one workgroup of kPlanLanes lanes turns the sums into offsets (scan_parts). */
 #ifndef HBS_PLAN_H

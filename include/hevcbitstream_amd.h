@@ -115,13 +115,13 @@ typedef struct hbs_ctx hbs_ctx;
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
  *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples,
  *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write, hbs_au_times, hbs_cenc_subsamples, hbs_cenc_crypt,
- *   hbs_cbcs_crypt.
+ *   hbs_cbcs_crypt, hbs_mp4_protect.
  * hbs_cenc_crypt takes its key and iv0 from host memory when it is called: a captured graph replays with the key and iv0 it was
  * captured with.  So does hbs_cbcs_crypt, and with the direction and the pattern of the capture.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
  * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py,
  * tests/test_gpu_mp4_stbl.py, tests/test_gpu_mp4_stbl_write.py, tests/test_gpu_au_times.py, tests/test_gpu_cenc.py and
- * tests/test_gpu_cbcs.py replay, no more: hbs_parse_headers_compact,
+ * tests/test_gpu_cbcs.py and tests/test_gpu_mp4_protect.py replay, no more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
  * A replay is the captured call on what the buffers hold then: every argument the host passed (counts, byte sizes, capacities,
@@ -474,7 +474,8 @@ int hbs_lenpref_to_annexb(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes, 
  * d_nal_au 4 bytes; d_keep any byte.
  * STATED LIMITS: one track; 32-bit mdat and moof sizes; no styp, sidx, prft, emsg, senc or encryption; no edit list (a stream
  * with reordering begins with a positive composition offset).  hbs_mp4_samples, below, reads fragments back.  (The samples can
- * be encrypted in place behind this call -- hbs_cenc_subsamples and hbs_cenc_crypt, below -- but no box says so yet.)
+ * be encrypted in place behind this call -- hbs_cenc_subsamples and hbs_cenc_crypt, below -- but no box says so yet.  The boxes
+ * that say so are a call of their own behind this one: hbs_mp4_protect, below.)
  *
  * hbs_mp4_init_host (plain C, no GPU): the init segment for those fragments -- ftyp (iso6, 0, iso6, mp41), then moov with
  * mvhd (rate 0x00010000, volume 0x0100, unity matrix, next_track_ID = track_id + 1), one trak (tkhd flags 3 with
@@ -1608,7 +1609,7 @@ int hbs_au_times(hbs_ctx* ctx, const hbs_access_unit* d_au, uint64_t n_aus,
  * Two device calls.  hbs_cenc_subsamples writes the subsample table of every sample from tables alone; hbs_cenc_crypt applies
  * AES-128 in counter mode, in place, to the protected ranges of samples that lie anywhere in a buffer.  Encryption and
  * decryption are the same call.  NOT written or read: senc, saiz, saio, sinf / tenc, pssh (the records below are in the senc
- * entry form -- 16-bit clear, 32-bit protected -- so a writer can follow); the schemes cbcs, cens, cbc1 (params->scheme is there
+ * entry form -- 16-bit clear, 32-bit protected -- so a writer can follow: hbs_mp4_protect and hbs_mp4_init_protect_host, below); the schemes cbcs, cens, cbc1 (params->scheme is there
  * for them; anything but cenc is refused -- cbcs is a call of its own, hbs_cbcs_crypt, below); key rotation (one key a call).
  *
  * hbs_cenc_subsamples.  The samples are exactly those of hbs_mp4_fragment / hbs_annexb_to_lenpref: sample a is the kept NALs
@@ -1703,7 +1704,7 @@ int hbs_cenc_crypt(hbs_ctx* ctx, uint8_t* d_data, uint64_t data_bytes,
  * 16-byte blocks are enciphered in CBC mode, skip_byte_block blocks stay clear, and so on (video: 1 and 9).  It takes the tables
  * of hbs_cenc_crypt, above -- the subsample table of hbs_cenc_subsamples is the same for every scheme -- and a params record of
  * its own.  CBC is not its own inverse: HBS_CBCS_DECRYPT selects the way back.  NOT done: cens and cbc1; senc, saiz, saio,
- * sinf / tenc, pssh; key rotation (one key a call).
+ * sinf / tenc, pssh (hbs_mp4_protect and hbs_mp4_init_protect_host, below, write them); key rotation (one key a call).
  *
  * Sample s is d_data[off_s, off_s + size_s) with off_s = d_sample_off[s], size_s = d_sample_size[s]; its subsamples are
  * d_sub[d_sub_first[s], d_sub_first[s+1]), laid end to end from off_s: `clear` bytes untouched, then `protect` bytes.
@@ -1766,6 +1767,113 @@ int hbs_cbcs_crypt(hbs_ctx* ctx, uint8_t* d_data, uint64_t data_bytes,
                    const uint64_t* d_sub_first /* n_samples + 1 */, const hbs_cenc_subsample* d_sub,
                    const uint8_t* d_iv /* n_samples x 16 bytes, iv_mode 0 */,
                    const hbs_cbcs_params* params, hbs_summary* d_summary);
+
+/*
+ * ---- protected fragments: saiz, saio and senc into every traf on the device; encv / sinf / tenc and pssh on the host -------
+ * hbs_mp4_protect is the writer the records above were laid out for.  It puts the sample auxiliary information -- which IV
+ * each sample has, where its clear and protected ranges lie -- into the fragments hbs_mp4_fragment wrote, and fixes the sizes
+ * and the trun's data offset; hbs_mp4_init_protect_host makes the init segment say that the track is protected.  With them
+ * fragment -> hbs_cenc_subsamples -> protect -> crypt yields segments a cenc / cbcs player can decrypt.  Every integer in a box
+ * is big-endian.  tests/_mp4_protect_ref.py restates the rule as one loop.
+ *
+ * INPUT.  Fragment r is d_in[out_off_r, out_off_r + out_bytes_r) of d_frag[r]: the table hbs_mp4_fragment wrote (hbs_mp4_samples
+ * writes the same form).  Fragments may lie anywhere in d_in, in any order, with anything between them.  Sample numbering is
+ * the pointer-offset rule of the other calls: first_au_r - first_au_0 equals the sum of `samples` of the fragments below r,
+ * and the total is n_samples.  Sample s of the call has the entries d_sub[d_sub_first[s], d_sub_first[s+1]) and the IV
+ * d_iv[16 s, 16 s + iv_size): the table hbs_cenc_crypt reads, or writes with iv_mode 1.  d_out must not overlap d_in.
+ * FRAGMENT RULE, checked on the device before anything is written.  A fragment is accepted only in the form hbs_mp4_fragment
+ * states, with S = samples_r: out_off + out_bytes <= in_bytes without a wrap; out_bytes >= 96 + 16 S; word 0 is 88 + 16 S, then
+ * 'moof'; 'traf' at +28 with size 64 + 16 S; 'tfhd' at +36, 'tfdt' at +52; 'trun' at +72 with size 20 + 16 S, version and flags
+ * 01 00 0F 01, count S, data_offset 96 + 16 S; at 88 + 16 S an 'mdat' whose size is out_bytes - 88 - 16 S (so that has 32 bits,
+ * and S is (2^32 - 89) / 16 at most).  The mfhd, the sequence, the track id and the decode time are not constrained.
+ * Anything else, or a broken numbering rule -- fragment r breaks it when first_au_r - first_au_0 is not the sum below r, when
+ * that sum + S passes n_samples, or, the last fragment, when it is not n_samples -- is a FRAGMENT ERROR: HBS_E_ARG,
+ * reserved[1] = 1 + the lowest such fragment.
+ * SAMPLE RULE, with V = iv_size and n_s the entries of sample s; only looked at when no fragment offends.  In two groups, and
+ * the sample named is the lowest of the first group that fails (the entries are not read through a d_sub_first that is
+ * wrong: hbs_cenc_crypt's way).  First: d_sub_first starts at 0, never decreases and stays below 2^48; n_s <=
+ * floor((253 - V) / 6), so that the saiz byte V + 2 + 6 n_s fits; with V == 8 the bytes d_iv[16 s + 8, 16 s + 16) are zero
+ * (else the 8-byte IV in the box is not the counter block the sample was enciphered with).  Second: every clear <= 65535; the
+ * entries add up to exactly the size word of the sample's trun entry.  A SAMPLE ERROR is HBS_E_ARG, reserved[0] = 1 + that
+ * sample.  Behind both: a new moof size above 2^31 - 9 (the trun's data_offset is a signed 32-bit field) is a fragment error.
+ * OUTPUT.  The fragments back to back in order; gaps of the input are dropped.  Fragment r, with E entries over its samples:
+ *   moof  size M' = 141 + (19 + V) S + 6 E
+ *     mfhd  copied
+ *     traf  size M' - 24
+ *       tfhd, tfdt  copied
+ *       trun  copied, but data_offset = M' + 8
+ *       saiz  size 17 + S   'saiz' 00 00 00 00  default_sample_info_size 00  sample_count(4) = S, then a byte a sample: V + 2 + 6 n_s
+ *       saio  00 00 00 14   'saio' 00 00 00 00  entry_count(4) = 1  offset(4) = 141 + 17 S      (from the moof's first byte)
+ *       senc  size 16 + (V + 2) S + 6 E   'senc' 00 00 00 02  sample_count(4) = S,
+ *             then a sample: IV (V bytes)  subsample_count(2) = n_s, then n_s x ( clear(2) protect(4) )
+ *   mdat  copied whole (header and payload)
+ * The fragment grows by 53 + (V + 3) S + 6 E bytes (hbs_mp4_protect_bytes_host); the output is the sum of out_bytes_r plus
+ * 53 n_frags + (V + 3) n_samples + 6 E_total.  d_sample_off / d_sample_size (optional, both or neither, n_samples each) give
+ * every sample's place in d_out -- its mdat payload offset is the sizes of the trun entries in front of it -- in the form
+ * hbs_cenc_crypt, hbs_cbcs_crypt and hbs_lenpref_to_annexb read: enciphering may run before this call on d_in or after it on
+ * d_out, with the same bytes either way.  d_frag_out[r] (optional, n_frags) is d_frag[r] with the new out_off and out_bytes.
+ *
+ * d_summary: nal_count = fragments, nal_found = n_samples, rbsp_bytes = entries in all, stream_bytes = output bytes,
+ * stop_reason = 0 (with HBS_E_ARG the two byte counts are 0).  HBS_E_CAPACITY when out_cap is below the output; the counts are
+ * right then.  Also HBS_E_CAPACITY, with or without a d_out and with both byte counts 0, when the sum of floor(out_bytes_r /
+ * 2^20) plus n_frags reaches 2^41: the output could pass 2^61 bytes.  On any error nothing but the summary is written.
+ * d_out == NULL: plan only, the summary alone is written.  n_frags == 0 with n_samples == 0 is valid.
+ * Refused with HBS_E_ARG at once, before anything is written: params NULL, an iv_size other than 0, 8, 16, flags or reserved
+ * words not 0, iv_size > 0 without a d_iv when n_samples > 0, n_frags or n_samples above 2^32 - 1, n_frags == 0 with n_samples
+ * != 0, one of the two sample tables without the other, out_cap above 2^46 with a d_out, a missing d_frag or (in_bytes > 0)
+ * d_in with n_frags > 0, a missing d_sub_first or d_sub with n_samples > 0, a missing d_summary, a misaligned pointer.
+ * Alignment: d_in, d_out, d_frag, d_frag_out, d_iv, d_summary 16 bytes; d_sub_first, d_sub, d_sample_off, d_sample_size 8.
+ * Nothing outside [d_out, d_out + output bytes), d_sample_off / d_sample_size[0, n_samples), d_frag_out[0, n_frags) and the
+ * summary is stored; no load touches a 16-byte granule that holds no byte of d_in[0, in_bytes); no host synchronisation (HIP
+ * graphs, above).  Scratch comes from the context's workspace and is sized by n_frags, n_samples and out_cap alone: 32 bytes a
+ * fragment and 80 per 256 fragments, 80 bytes per 256 samples, 8 bytes per 64 KiB of out_cap with a d_out (so pass what the
+ * plan gave as out_cap), every table rounded up to 256 bytes, and 64 bytes.
+ *
+ * hbs_mp4_init_protect_host (plain C, no GPU).  It walks init[0, n) by the box rule of hbs_mp4_init_read_host to the first
+ * 'hvc1' / 'hev1' entry that has an hvcC of the track (track_id 0: as there).  The output is the segment with that entry renamed
+ * 'encv', with a sinf appended to the entry -- frma (12 bytes, the original fourcc); schm (20 bytes: version and flags 0, the
+ * scheme, version 00 01 00 00); schi holding a tenc: version 0, or 1 when crypt_byte_block or skip_byte_block is not 0; flags 0;
+ * 00; crypt_byte_block << 4 | skip_byte_block (00 at version 0); 01; iv_size; the KID; and, with iv_size 0, constant_iv_size
+ * and that many bytes of constant_iv -- with the sinf's size added to the 32-bit sizes of the entry, stsd, stbl, minf, mdia,
+ * trak and moov, and with the pssh boxes appended at the end of the moov (their bytes added to its size).  Each pssh[i] must be
+ * one box of type 'pssh' whose size field equals pssh_bytes[i].  Returns the bytes the segment takes; it is written to out only
+ * when cap suffices.  HBS_E_ARG: anything hbs_mp4_init_read_host's walk calls malformed, no such track or entry; one of the seven
+ * boxes with a 64-bit size or a size field of 0; a size that would pass 2^32 - 1; a scheme other than 'cenc' and 'cbcs'; a
+ * block count above 15; a pattern with 'cenc'; an iv_size other than 0, 8, 16; constant_iv_size other than 8 or 16 with iv_size
+ * 0, or other than 0 without; a reserved word not 0; a NULL pointer.  Every length is bounded before it is used; no byte at or
+ * behind init + n, or outside the pssh boxes, is read.
+ * OUT OF SCOPE: reading senc / encv back (hbs_mp4_samples and hbs_mp4_init_read_host stay as they are: an 'encv' entry is not
+ * a video entry to them); key rotation (sbgp / sgpd 'seig'); cens and cbc1; several tracks; building pssh payloads.
+ */
+typedef struct hbs_mp4_protect_params {   /* HOST memory, 32 bytes */
+    uint32_t iv_size;        /* 0, 8 or 16: IV bytes a sample in the senc; 0: none (tenc's constant IV, the usual cbcs form) */
+    uint32_t flags;          /* none defined: 0 */
+    uint32_t reserved[6];    /* 0 */
+} hbs_mp4_protect_params;
+
+int hbs_mp4_protect(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
+                    const hbs_mp4_frag* d_frag, uint64_t n_frags,
+                    const uint64_t* d_sub_first /* n_samples + 1 */, const hbs_cenc_subsample* d_sub,
+                    const uint8_t* d_iv /* n_samples x 16; read when iv_size > 0 */, uint64_t n_samples,
+                    const hbs_mp4_protect_params* params,
+                    uint8_t* d_out, uint64_t out_cap,                 /* d_out NULL: plan only */
+                    uint64_t* d_sample_off, uint64_t* d_sample_size,  /* optional, both or neither, n_samples: in d_out */
+                    hbs_mp4_frag* d_frag_out /* optional, n_frags */,
+                    hbs_summary* d_summary);
+uint64_t hbs_mp4_protect_bytes_host(uint64_t samples, uint64_t entries, uint32_t iv_size);   /* 53 + (iv_size + 3) S + 6 E */
+
+typedef struct hbs_mp4_tenc {            /* 64 bytes */
+    uint32_t scheme;                     /* 'cenc' (0x63656E63) or 'cbcs' (0x63626373) */
+    uint8_t  crypt_byte_block, skip_byte_block;   /* 0..15; both 0: tenc version 0 */
+    uint8_t  iv_size;                    /* 0, 8, 16: default_Per_Sample_IV_Size */
+    uint8_t  constant_iv_size;           /* 8 or 16 with iv_size 0, else 0 */
+    uint8_t  kid[16], constant_iv[16];
+    uint32_t reserved[6];                /* 0 */
+} hbs_mp4_tenc;
+int64_t hbs_mp4_init_protect_host(const uint8_t* init, uint64_t n, uint32_t track_id /* 0: as hbs_mp4_init_read_host */,
+                                  const hbs_mp4_tenc* t,
+                                  const uint8_t* const* pssh, const uint64_t* pssh_bytes, uint64_t n_pssh /* whole 'pssh' boxes */,
+                                  uint8_t* out, uint64_t cap);   /* bytes needed; written only when cap suffices; HBS_E_ARG */
 
 /*
  * ---- access-unit delimiters and parameter sets in front of access units ---------------------------------------------
