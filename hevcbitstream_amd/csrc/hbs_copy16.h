@@ -3,6 +3,18 @@
  * (hbs_pieces.hip, hbs_rtp.hip, hbs_tsmux.hip, hbs_ts.hip, hbs_mp4.hip, hbs_mp4prot.hip).  The fast path of a chunk that lies inside one run of source bytes:
  * load16_pair, realign, arena_store16 (hbs_wave.h).  The slow path of a chunk that holds other bytes or spans runs: pack_byte
  * for each byte, then store_chunk.  last_le finds the unit a chunk lies in, tile_first_of the unit an output tile begins in.
+ *
+ * The skeleton around them, the same in k_piece_copy, k_rtp_copy, k_tsm_copy, k_mp4_copy and k_prot_copy, has two phases:
+ *
+ *   copy_batches    each lane walks its 16-byte output chunks, kLanes chunks apart, kBatch at a time.  In the first half of a
+ *                   batch the kernel's locate() says for each chunk whether it lies wholly inside one run of source bytes, and
+ *                   such a chunk issues load16_pair: kBatch chunks' loads are in flight a lane.  The second half realigns and
+ *                   stores them, and hands every other chunk of the range to the kernel's defer().  k_rtp_copy, k_mp4_copy and
+ *                   k_prot_copy call it; k_piece_copy and k_tsm_copy keep the loop written out, each with a row that ran
+ *                   longer with the call (profiles/r26/copy_time.txt)
+ *   the slow chunks behind the batches, byte by byte from the kernel's own rule.  Either they were noted in registers (a bit
+ *                   mask: k_piece_copy, k_tsm_copy) and the lane that met a chunk assembles it, or defer() put them on a list
+ *                   in LDS (slow_push) and copy_slow_list spreads the tile's list over the workgroup, a lane a byte
  */
 #ifndef HBS_COPY16_H
 #define HBS_COPY16_H
@@ -93,6 +105,97 @@ __device__ __forceinline__ void tile_first_of(const unsigned long long* starts, 
     if (t > used || count == 0) return;
     if (t == used) { tile_first[t] = count - 1; return; }
     tile_first[t] = last_le((uint64_t)0, count - 1, t * kTile, [&](uint64_t i) { return (uint64_t)starts[i]; });
+}
+
+constexpr int kBatch = 4;                         /* chunks whose loads a copy lane issues together */
+constexpr int kSlowBatch = 4;                     /* listed slow chunks a group of sixteen lanes takes together */
+
+/* The batches of a workgroup of kLanes lanes over the `tlen` output bytes at `out` (16-byte aligned), kChunks chunks a lane:
+ * lane t takes the chunks at r = 16 (t + kLanes k), k in [0, kChunks).  locate(r, tag, s) -> bool is asked for every chunk
+ * that begins inside the range, in rising k: whether out[r, r + 16) is src[s, s + 16) and all of it lies inside the range; it
+ * leaves in `tag` what the kernel wants to know of a chunk that is not.  defer(r, tag) gets each of those, behind the
+ * stores of its batch.  The loads stay in the first half of a batch and the stores in the second: that is what keeps kB
+ * chunks' loads in flight. */
+template <int kLanes, int kChunks, int kB = kBatch, class Locate, class Defer>
+__device__ __forceinline__ void copy_batches(const uint8_t* src, uint8_t* out, uint32_t tlen, Locate locate, Defer defer)
+{
+    static_assert(kChunks % kB == 0, "whole batches");
+#pragma unroll 1
+    for (int b = 0; b < kChunks; b += kB) {
+        u32x4 va[kB], vb[kB];
+        uint32_t sh[kB], tag[kB];
+        bool simple[kB], in[kB];
+#pragma unroll
+        for (int u = 0; u < kB; ++u) {
+            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kLanes * (uint32_t)(b + u));
+            simple[u] = false; sh[u] = 0; tag[u] = 0;
+            va[u] = zero4(); vb[u] = zero4();
+            in[u] = r < tlen;
+            if (in[u]) {
+                uint64_t s = 0;
+                if (locate(r, tag[u], s)) {
+                    simple[u] = true;
+                    load16_pair(src, s, va[u], vb[u], sh[u]);
+                }
+            }
+        }
+        /* s_waitcnt vmcnt(0), once for the batch's loads.  Left to the compiler, the wait is placed in front of each chunk's
+         * realign where no register copy happens to force it earlier, and there it also waits for the store of the chunk
+         * before: the batch's stores would go out one at a time. */
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+#pragma unroll
+        for (int u = 0; u < kB; ++u) {
+            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kLanes * (uint32_t)(b + u));
+            if (simple[u]) arena_store16(out + r, realign(va[u], vb[u], sh[u]));
+            else if (in[u]) defer(r, tag[u]);
+        }
+    }
+}
+
+/* The list of a tile's slow chunks in LDS, an entry a chunk: the chunk's number in the tile | tag << 12, the tag being the
+ * number in the tile of the unit the chunk begins in (a unit has a byte or more).  kTile: the tile's bytes. */
+template <uint32_t kTile>
+__device__ __forceinline__ void slow_push(uint32_t* s_slow, uint32_t& s_nslow, uint32_t r, uint32_t tag)
+{
+    static_assert(kTile / 16 <= (1u << 12) && kTile <= (1u << 20), "a slow chunk and its tag share a word");
+    s_slow[atomicAdd(&s_nslow, 1u)] = (r >> 4) | (tag << 12);
+}
+
+/* ... and the workgroup's pass over the `nslow` entries (behind a barrier that follows the last slow_push): kSlow kLanes / 16
+ * chunks at a time -- sixty-four with 256 lanes -- a lane a byte of kSlow of them, byte(tag, cur) being output byte cur of a
+ * chunk with that tag; the sixteen lanes of a chunk put their bytes together and the first stores them.  The tile is
+ * out[t0, t0 + tlen), and its last chunk is stored byte-exactly. */
+template <int kLanes, int kSlow = kSlowBatch, class Byte>
+__device__ __forceinline__ void copy_slow_list(const uint32_t* s_slow, uint32_t nslow, uint8_t* out, uint64_t t0, uint32_t tlen,
+                                               Byte byte)
+{
+#pragma unroll 1
+    for (uint32_t base = 0; base < nslow; base += kSlow * (kLanes / 16)) {
+        const uint32_t b = threadIdx.x & 15u;
+        uint32_t v[kSlow], r[kSlow], len[kSlow];
+#pragma unroll
+        for (int u = 0; u < kSlow; ++u) {
+            const uint32_t c = base + (uint32_t)u * (kLanes / 16) + (threadIdx.x >> 4);
+            v[u] = 0; r[u] = 0; len[u] = 0;
+            if (c < nslow) {
+                const uint32_t e = s_slow[c];
+                r[u] = (e & 0xFFFu) << 4;
+                len[u] = tlen - r[u] < 16 ? tlen - r[u] : 16u;
+                if (b < len[u]) v[u] = byte(e >> 12, t0 + r[u] + b);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kSlow; ++u) {
+            if (!len[u]) continue;                                    /* (the sixteen lanes of a chunk agree) */
+            uint32_t w = v[u] << (8u * (b & 3u));
+            w |= __shfl_xor(w, 1, 16);
+            w |= __shfl_xor(w, 2, 16);
+            u32x4 x;
+            x.x = __shfl(w, 0, 16); x.y = __shfl(w, 4, 16); x.z = __shfl(w, 8, 16); x.w = __shfl(w, 12, 16);
+            if (len[u] == 16) { if (b == 0) arena_store16(out + t0 + r[u], x); }
+            else if (b < len[u]) out[t0 + r[u] + b] = (uint8_t)v[u];  /* the output's end: these bytes and no others */
+        }
+    }
 }
 
 } // namespace hbs

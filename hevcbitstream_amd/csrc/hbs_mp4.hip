@@ -22,12 +22,10 @@
  *   k_mp4_tiles      a lane per 64 KiB output tile: binary search of the fragment and of the record its first byte lies in
  *   k_mp4_copy       one workgroup per output tile: the tile's fragments (at most 587: a fragment has 112 bytes or more) and
  *                    records (up to 1024; more are read from memory) are staged in LDS; each lane takes 16-byte output chunks
- *                    4 KiB apart; a chunk wholly inside one NAL's payload is two aligned 16-byte non-temporal loads, alignbyte
- *                    and one aligned 16-byte non-temporal store, four chunks' loads in flight a lane; the chunks that hold
- *                    container bytes or a length field, or span two payloads, are listed and done behind the others, sixty-four
- *                    at a time, a lane a byte: the byte's fragment and, in the trun array, the one word of its sample it lies
- *                    in come from the rule; the sixteen lanes of a chunk put their bytes together and the first stores them.
- *                    The output's last chunk is stored byte-exactly.
+ *                    4 KiB apart, in the skeleton of hbs_copy16.h: copy_batches for the chunks wholly inside one NAL's payload;
+ *                    the chunks that hold container bytes or a length field, or span two payloads, go to the list in LDS, and
+ *                    copy_slow_list makes their bytes from the rule (chunk_byte): the byte's fragment and, in the trun array,
+ *                    the one word of its sample it lies in.
  *
  * Traffic: the kept payloads read once and the output written once; the index read twice (32 B a NAL), the times, the AU flags
  * and B(a) by each AU pass and by the lanes of the trun bytes; 16 B a kept NAL, 24 B an AU and 16 B a tile of scratch.
@@ -43,8 +41,6 @@ namespace {
 constexpr int kMT = kMp4Lanes;
 constexpr uint32_t kTile = (uint32_t)kMp4TileBytes;
 constexpr int kChunks = (int)(kMp4TileBytes / 16 / kMT);              /* 16-byte output chunks a copy lane takes  */
-constexpr int kBatch = 4;                                             /* ... loads of that many issued together   */
-constexpr int kSlowBatch = 4;                                         /* slow chunks a group of sixteen lanes takes at a time */
 constexpr uint32_t kLdsRecs = 1024;                                   /* records a tile stages in LDS; more: read from memory */
 constexpr uint32_t kLdsFrags = 640;                                   /* fragments a tile can hold, and two              */
 static_assert(kMp4TileBytes / (kMp4FragFixed + 16) + 3 <= kLdsFrags, "every fragment of a tile is staged");
@@ -441,70 +437,22 @@ __global__ __launch_bounds__(kMT) void k_mp4_copy(Mp4Args a)
     __syncthreads();
     const uint32_t L = a.L;
     uint32_t flo = 0, jlo = 0;
-#pragma unroll 1
-    for (int b = 0; b < kChunks; b += kBatch) {
-        u32x4 va[kBatch], vb[kBatch];
-        uint32_t sh[kBatch], fi[kBatch];
-        bool simple[kBatch];
-#pragma unroll
-        for (int u = 0; u < kBatch; ++u) {
-            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kMT * (uint32_t)(b + u));
-            simple[u] = false; sh[u] = 0; fi[u] = flo;
-            va[u] = zero4(); vb[u] = zero4();
-            if (r < tlen) {
-                const uint64_t o = t0 + r;
-                flo = tm.find_frag(flo, o);
-                fi[u] = flo;
-                /* wholly in the fragment's mdat payload ... */
-                if (o - tm.foff(flo) >= tm.head(flo) && o + 16 <= tm.foff(flo + 1)) {
-                    const uint64_t p = o - tm.fpay(flo);
-                    jlo = tm.find_rec(jlo, p);
-                    /* ... and in one record's payload */
-                    if (p - tm.rB(jlo) >= L && p + 16 <= tm.rB(jlo + 1)) {
-                        simple[u] = true;
-                        load16_pair(a.src, p + tm.rdelta(jlo), va[u], vb[u], sh[u]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kBatch; ++u) {
-            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kMT * (uint32_t)(b + u));
-            if (simple[u]) arena_store16(a.out + t0 + r, realign(va[u], vb[u], sh[u]));
-            else if (r < tlen) s_slow[atomicAdd(&s_nslow, 1u)] = (r >> 4) | (fi[u] << 12);
-        }
-    }
-    /* behind the batches: the tile's slow chunks, sixty-four at a time, a lane a byte of four of them; the sixteen lanes of a
-     * chunk put their bytes together and the first stores them */
+    copy_batches<kMT, kChunks>(a.src, a.out + t0, tlen,
+        [&](uint32_t r, uint32_t& fi, uint64_t& s) {
+            const uint64_t o = t0 + r;
+            fi = flo = tm.find_frag(flo, o);
+            /* wholly in the fragment's mdat payload ... */
+            if (o - tm.foff(flo) < tm.head(flo) || o + 16 > tm.foff(flo + 1)) return false;
+            const uint64_t p = o - tm.fpay(flo);
+            jlo = tm.find_rec(jlo, p);
+            /* ... and in one record's payload */
+            if (p - tm.rB(jlo) < L || p + 16 > tm.rB(jlo + 1)) return false;
+            s = p + tm.rdelta(jlo);
+            return true;
+        },
+        [&](uint32_t r, uint32_t fi) { slow_push<kTile>(s_slow, s_nslow, r, fi); });
     __syncthreads();
-    const uint32_t nslow = s_nslow;
-#pragma unroll 1
-    for (uint32_t base = 0; base < nslow; base += kSlowBatch * (kMT / 16)) {
-        const uint32_t b = threadIdx.x & 15u;
-        uint32_t v[kSlowBatch], r[kSlowBatch], len[kSlowBatch];
-#pragma unroll
-        for (int u = 0; u < kSlowBatch; ++u) {
-            const uint32_t c = base + (uint32_t)u * (kMT / 16) + (threadIdx.x >> 4);
-            v[u] = 0; r[u] = 0; len[u] = 0;
-            if (c < nslow) {
-                const uint32_t e = s_slow[c];
-                r[u] = (e & 0xFFFu) << 4;
-                len[u] = tlen - r[u] < 16 ? tlen - r[u] : 16u;
-                if (b < len[u]) v[u] = chunk_byte(a, tm, e >> 12, t0 + r[u] + b);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kSlowBatch; ++u) {
-            if (!len[u]) continue;                                    /* (the sixteen lanes of a chunk agree) */
-            uint32_t w = v[u] << (8u * (b & 3u));
-            w |= __shfl_xor(w, 1, 16);
-            w |= __shfl_xor(w, 2, 16);
-            u32x4 x;
-            x.x = __shfl(w, 0, 16); x.y = __shfl(w, 4, 16); x.z = __shfl(w, 8, 16); x.w = __shfl(w, 12, 16);
-            if (len[u] == 16) { if (b == 0) arena_store16(a.out + t0 + r[u], x); }
-            else if (b < len[u]) a.out[t0 + r[u] + b] = (uint8_t)v[u];  /* the output's end: these bytes and no others */
-        }
-    }
+    copy_slow_list<kMT>(s_slow, s_nslow, a.out, t0, tlen, [&](uint32_t fi, uint64_t cur) { return chunk_byte(a, tm, fi, cur); });
 }
 
 } // namespace

@@ -21,12 +21,10 @@
  *   k_prot_frag<2>  d_frag_out;  k_prot_samp<2>  d_sample_off / d_sample_size (each only when asked for)
  *   k_prot_tiles    a lane per 64 KiB output tile: binary search of the fragment its first byte lies in
  *   k_prot_copy     one workgroup per output tile: the tile's fragments (at most 442: a fragment has 149 bytes or more) are
- *                   staged in LDS; each lane takes 16-byte output chunks 4 KiB apart; a chunk wholly inside one fragment's mdat
- *                   (header and payload, which come from the source at any byte offset) is two aligned 16-byte non-temporal
- *                   loads, alignbyte and one aligned 16-byte non-temporal store, four chunks' loads in flight a lane; the
- *                   chunks that hold moof bytes or span two fragments are listed and done behind the others, sixty-four at a
- *                   time, a lane a byte through mp4prot_moof_byte; the sixteen lanes of a chunk put their bytes together and
- *                   the first stores them.  The output's last chunk is stored byte-exactly.
+ *                   staged in LDS; each lane takes 16-byte output chunks 4 KiB apart, in the skeleton of hbs_copy16.h:
+ *                   copy_batches for the chunks wholly inside one fragment's mdat (header and payload, which come from the
+ *                   source at any byte offset); the chunks that hold moof bytes or span two fragments go to the list in LDS,
+ *                   and copy_slow_list makes their bytes through mp4prot_moof_byte (chunk_byte).
  *
  * Traffic: the mdats read once and the output written once; thirteen header words a fragment, the fragment table three times,
  * d_sub_first by each sample pass, the entries twice (the sums, the senc), the trun size words twice; 32 B a fragment and 8 B a
@@ -43,8 +41,6 @@ namespace {
 constexpr int kPT = kProtLanes;
 constexpr uint32_t kTile = (uint32_t)kProtTileBytes;
 constexpr int kChunks = (int)(kProtTileBytes / 16 / kPT);             /* 16-byte output chunks a copy lane takes  */
-constexpr int kBatch = 4;                                             /* ... loads of that many issued together   */
-constexpr int kSlowBatch = 4;                                         /* slow chunks a group of sixteen lanes takes at a time */
 constexpr uint32_t kMinFrag = kMp4FragFixed + kProtFixed;             /* a protected fragment of no samples and an empty mdat */
 constexpr uint32_t kLdsFrags = 448;                                   /* fragments a tile can hold, and two       */
 static_assert(kProtTileBytes / kMinFrag + 3 <= kLdsFrags, "every fragment of a tile is staged");
@@ -273,65 +269,18 @@ __global__ __launch_bounds__(kPT) void k_prot_copy(Mp4ProtArgs a)
     if (threadIdx.x == 0) s_nslow = 0;
     __syncthreads();
     uint32_t flo = 0;
-#pragma unroll 1
-    for (int b = 0; b < kChunks; b += kBatch) {
-        u32x4 va[kBatch], vb[kBatch];
-        uint32_t sh[kBatch], fi[kBatch];
-        bool simple[kBatch];
-#pragma unroll
-        for (int u = 0; u < kBatch; ++u) {
-            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kPT * (uint32_t)(b + u));
-            simple[u] = false; sh[u] = 0; fi[u] = flo;
-            va[u] = zero4(); vb[u] = zero4();
-            if (r < tlen) {
-                const uint64_t o = t0 + r;
-                flo = tf.find(flo, o);
-                fi[u] = flo;
-                /* wholly in the fragment's mdat, header or payload: source bytes */
-                if (o >= s_body[flo] && o + 16 <= tf.at(flo + 1)) {
-                    simple[u] = true;
-                    load16_pair(a.src, o + s_delta[flo], va[u], vb[u], sh[u]);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kBatch; ++u) {
-            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kPT * (uint32_t)(b + u));
-            if (simple[u]) arena_store16(a.out + t0 + r, realign(va[u], vb[u], sh[u]));
-            else if (r < tlen) s_slow[atomicAdd(&s_nslow, 1u)] = (r >> 4) | (fi[u] << 12);
-        }
-    }
-    /* behind the batches: the tile's slow chunks, sixty-four at a time, a lane a byte of four of them; the sixteen lanes of a
-     * chunk put their bytes together and the first stores them */
+    copy_batches<kPT, kChunks>(a.src, a.out + t0, tlen,
+        [&](uint32_t r, uint32_t& fi, uint64_t& s) {
+            const uint64_t o = t0 + r;
+            fi = flo = tf.find(flo, o);
+            /* wholly in the fragment's mdat, header or payload: source bytes */
+            if (o < s_body[flo] || o + 16 > tf.at(flo + 1)) return false;
+            s = o + s_delta[flo];
+            return true;
+        },
+        [&](uint32_t r, uint32_t fi) { slow_push<kTile>(s_slow, s_nslow, r, fi); });
     __syncthreads();
-    const uint32_t nslow = s_nslow;
-#pragma unroll 1
-    for (uint32_t base = 0; base < nslow; base += kSlowBatch * (kPT / 16)) {
-        const uint32_t b = threadIdx.x & 15u;
-        uint32_t v[kSlowBatch], r[kSlowBatch], len[kSlowBatch];
-#pragma unroll
-        for (int u = 0; u < kSlowBatch; ++u) {
-            const uint32_t c = base + (uint32_t)u * (kPT / 16) + (threadIdx.x >> 4);
-            v[u] = 0; r[u] = 0; len[u] = 0;
-            if (c < nslow) {
-                const uint32_t e = s_slow[c];
-                r[u] = (e & 0xFFFu) << 4;
-                len[u] = tlen - r[u] < 16 ? tlen - r[u] : 16u;
-                if (b < len[u]) v[u] = chunk_byte(a, tf, e >> 12, t0 + r[u] + b);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kSlowBatch; ++u) {
-            if (!len[u]) continue;                                    /* (the sixteen lanes of a chunk agree) */
-            uint32_t w = v[u] << (8u * (b & 3u));
-            w |= __shfl_xor(w, 1, 16);
-            w |= __shfl_xor(w, 2, 16);
-            u32x4 x;
-            x.x = __shfl(w, 0, 16); x.y = __shfl(w, 4, 16); x.z = __shfl(w, 8, 16); x.w = __shfl(w, 12, 16);
-            if (len[u] == 16) { if (b == 0) arena_store16(a.out + t0 + r[u], x); }
-            else if (b < len[u]) a.out[t0 + r[u] + b] = (uint8_t)v[u];  /* the output's end: these bytes and no others */
-        }
-    }
+    copy_slow_list<kPT>(s_slow, s_nslow, a.out, t0, tlen, [&](uint32_t fi, uint64_t cur) { return chunk_byte(a, tf, fi, cur); });
 }
 
 } // namespace

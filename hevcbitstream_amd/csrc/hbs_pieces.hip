@@ -7,10 +7,11 @@
  *
  *   k_piece_tiles    one lane per 64 KiB output tile: binary search of the piece its first byte lies in
  *   k_piece_copy     one workgroup per output tile: each lane takes 16-byte output chunks 4 KiB apart and finds the piece of
- *                    each (the tile's pieces are staged in LDS; more than 2 048 are read from memory).  A chunk inside one
- *                    payload is loaded as aligned 16-byte non-temporal loads, realigned with alignbyte and stored as one
- *                    aligned 16-byte non-temporal store; a chunk that holds a prefix byte or spans pieces, and the output's
- *                    last chunk, is assembled byte by byte and stored byte-exact.  A payload of any size spreads over the
+ *                    each (the tile's pieces are staged in LDS; more than 2 048 are read from memory), in the skeleton that
+ *                    hbs_copy16.h describes, its batch loop written out here: the fast path for the chunks inside one
+ *                    payload; a chunk that holds a prefix byte or spans pieces, and the output's last chunk, is marked in a
+ *                    bit mask and assembled byte by byte behind them by the lane that met it (copy_chunk_bytes), stored
+ *                    byte-exact.  A payload of any size spreads over the
  *                    tiles it covers.  <kMode>: kPieceBare for a table without prefixes, where all that is about them folds
  *                    away; kPiecePrefix for one prefix form a table; kPieceLiteral for a literal a piece (piece_lit), whose
  *                    length is staged next to the piece and whose bytes are read where a chunk holds some.
@@ -29,7 +30,6 @@ namespace {
 constexpr int kCT = 256;                                              /* lanes of the copy workgroup             */
 constexpr uint32_t kTile = (uint32_t)kPieceTileBytes;
 constexpr int kChunks = (int)(kPieceTileBytes / 16 / kCT);            /* 16-byte output chunks a copy lane takes */
-constexpr int kBatch = 4;                                             /* ... loads of that many issued together  */
 constexpr uint32_t kLdsPieces = 2048;                                 /* pieces a tile stages in LDS; more: read from memory */
 constexpr int32_t kFar = -8;                                          /* a piece that begins this far in front of the tile or
                                                                          further: its prefix (<= 7 bytes) is not in the tile */
@@ -149,6 +149,8 @@ __global__ __launch_bounds__(kCT) void k_piece_copy(PieceTable a)
     uint32_t lo = 0;
     uint32_t slow = 0;                        /* chunks done byte by byte, behind the batches: bit b + u */
     uint32_t slow_ip[kChunks];
+    /* copy_batches (hbs_copy16.h) written out: with it the filter's row of one ~128-byte NAL in ten ran 1.0 to 1.4 % longer in
+     * two samples of two, the other rows of the piece calls shorter by up to 8 % (profiles/r26/copy_time.txt) */
 #pragma unroll 1
     for (int b = 0; b < kChunks; b += kBatch) {
         u32x4 va[kBatch], vb[kBatch];

@@ -13,12 +13,10 @@
  *   k_rtp_tiles   one lane per 64 KiB output tile: binary search of the NAL its first byte lies in
  *   k_rtp_copy    one workgroup per output tile: each lane takes 16-byte output chunks 4 KiB apart and finds the NAL of each
  *                 (the tile's NALs are staged in LDS; more than 512 are read from memory); the packet of the chunk is a
- *                 division by the full packet's size.  A chunk that lies wholly inside one packet's NAL bytes is one or two
- *                 aligned 16-byte non-temporal loads, alignbyte and one aligned 16-byte non-temporal store, four chunks' loads
- *                 in flight a lane; a chunk that holds length, RTP header or FU header bytes or spans packets or NALs -- two in
- *                 75 at 1 200-byte packets -- goes to a list in LDS, and behind the batches the workgroup takes the list
- *                 sixty-four chunks at a time, a lane a byte of four chunks from the rule, sixteen lanes' bytes put together into one aligned
- *                 16-byte store; the output's last chunk is stored byte-exactly.
+ *                 division by the full packet's size.  The copy is the skeleton of hbs_copy16.h: copy_batches for the chunks
+ *                 that lie wholly inside one packet's NAL bytes; a chunk that holds length, RTP header or FU header bytes or
+ *                 spans packets or NALs -- two in 75 at 1 200-byte packets -- goes to the list in LDS, and copy_slow_list
+ *                 makes its bytes from the rule (chunk_byte).
  *
  * HBS_RTP_AGGREGATE (aggregation packets for groups of small NALs) is a second instance of k_rtp_count, k_rtp_place and
  * k_rtp_copy; the instance without the flag compiles from the statements it had before the flag existed.  In the plan each
@@ -45,13 +43,10 @@ namespace {
 constexpr int kRT = 256;                                              /* lanes of the copy workgroup             */
 constexpr uint32_t kTile = (uint32_t)kRtpTileBytes;
 constexpr int kChunks = (int)(kRtpTileBytes / 16 / kRT);              /* 16-byte output chunks a copy lane takes */
-constexpr int kBatch = 4;                                             /* ... loads of that many issued together  */
-constexpr int kSlowBatch = 4;                                         /* slow chunks a group of sixteen lanes takes together */
 constexpr uint32_t kLdsNals = 512;                                    /* NALs a tile stages in LDS; more: read from memory */
 constexpr unsigned long long kMarker = 1ull << 32;                    /* rec_tm: the NAL ends its access unit    */
 constexpr unsigned long long kKindShift = 62, kLenMask = (1ull << kKindShift) - 1;   /* rec_len with HBS_RTP_AGGREGATE */
 constexpr uint32_t kOwn = 0, kApFirst = 1, kApLater = 2;              /* ... its kinds                           */
-static_assert(kTile / 16 <= 0x1000 && kTile / 4 < (1u << 20), "a slow chunk and its NAL share a word");
 
 struct NalEval {
     uint64_t start, L;
@@ -367,85 +362,33 @@ __global__ __launch_bounds__(kRT) void k_rtp_copy(RtpArgs a)
     const uint32_t head_single = rtp_head_bytes(a.q, false), head_fu = rtp_head_bytes(a.q, true);
     [[maybe_unused]] const uint32_t head_ap = rtp_ap_first_head(a.q);
     uint32_t lo = 0;
-#pragma unroll 1
-    for (int b = 0; b < kChunks; b += kBatch) {
-        u32x4 va[kBatch], vb[kBatch];
-        uint32_t sh[kBatch], ip[kBatch];
-        bool simple[kBatch];
-#pragma unroll
-        for (int u = 0; u < kBatch; ++u) {
-            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kRT * (uint32_t)(b + u));
-            simple[u] = false; sh[u] = 0; ip[u] = lo;
-            va[u] = zero4(); vb[u] = zero4();
-            if (r < tlen) {
-                const uint64_t o = t0 + r;
-                lo = tn.find(lo, cnt - 1, o);
-                ip[u] = lo;
-                if (o + 16 <= tn.out(lo + 1)) {                       /* the chunk ends inside the NAL's packets */
-                    const uint64_t q = o - tn.out(lo), S = tn.src(lo);
-                    uint64_t s;
-                    bool ok;
-                    uint64_t len = tn.len(lo);
-                    [[maybe_unused]] uint32_t kind = kOwn;
-                    if constexpr (kAp) { kind = (uint32_t)(len >> kKindShift); len &= kLenMask; }
-                    if (kAp && kind != kOwn) {
-                        const uint32_t head = kind == kApFirst ? head_ap : kRtpApSize;
-                        ok = q >= head;
-                        s = S + (q - head);
-                    } else if (len <= mp) {
-                        ok = q >= head_single;
-                        s = S + (q - head_single);
-                    } else {
-                        const uint64_t p = packet_of(q, P);
-                        const uint32_t i = (uint32_t)(q - p * P);
-                        ok = i >= head_fu && i + 16u <= P;
-                        s = S + 2u + p * F + (i - head_fu);
-                    }
-                    if (ok) {
-                        simple[u] = true;
-                        load16_pair(a.src, s, va[u], vb[u], sh[u]);
-                    }
-                }
+    copy_batches<kRT, kChunks>(a.src, a.out + t0, tlen,
+        [&](uint32_t r, uint32_t& ip, uint64_t& s) {
+            const uint64_t o = t0 + r;
+            ip = lo = tn.find(lo, cnt - 1, o);
+            if (o + 16 > tn.out(lo + 1)) return false;                /* the chunk must end inside the NAL's packets */
+            const uint64_t q = o - tn.out(lo), S = tn.src(lo);
+            uint64_t len = tn.len(lo);
+            [[maybe_unused]] uint32_t kind = kOwn;
+            if constexpr (kAp) { kind = (uint32_t)(len >> kKindShift); len &= kLenMask; }
+            if (kAp && kind != kOwn) {
+                const uint32_t head = kind == kApFirst ? head_ap : kRtpApSize;
+                s = S + (q - head);
+                return q >= head;
             }
-        }
-#pragma unroll
-        for (int u = 0; u < kBatch; ++u) {
-            const uint32_t r = 16u * (threadIdx.x + (uint32_t)kRT * (uint32_t)(b + u));
-            if (simple[u]) arena_store16(a.out + t0 + r, realign(va[u], vb[u], sh[u]));
-            else if (r < tlen) s_slow[atomicAdd(&s_nslow, 1u)] = (r >> 4) | (ip[u] << 12);
-        }
-    }
-    /* behind the batches: the tile's slow chunks, sixty-four at a time, a lane a byte of four of them; the sixteen lanes of a chunk put their
-     * bytes together and the first stores them */
+            if (len <= mp) {
+                s = S + (q - head_single);
+                return q >= head_single;
+            }
+            const uint64_t p = packet_of(q, P);
+            const uint32_t i = (uint32_t)(q - p * P);
+            s = S + 2u + p * F + (i - head_fu);
+            return i >= head_fu && i + 16u <= P;
+        },
+        [&](uint32_t r, uint32_t ip) { slow_push<kTile>(s_slow, s_nslow, r, ip); });
     __syncthreads();
-    const uint32_t nslow = s_nslow;
-#pragma unroll 1
-    for (uint32_t base = 0; base < nslow; base += kSlowBatch * (kRT / 16)) {
-        const uint32_t b = threadIdx.x & 15u;
-        uint32_t v[kSlowBatch], r[kSlowBatch], len[kSlowBatch];
-#pragma unroll
-        for (int u = 0; u < kSlowBatch; ++u) {
-            const uint32_t c = base + (uint32_t)u * (kRT / 16) + (threadIdx.x >> 4);
-            v[u] = 0; r[u] = 0; len[u] = 0;
-            if (c < nslow) {
-                const uint32_t e = s_slow[c];
-                r[u] = (e & 0xFFFu) << 4;
-                len[u] = tlen - r[u] < 16 ? tlen - r[u] : 16u;
-                if (b < len[u]) v[u] = chunk_byte<kAp>(a, tn, e >> 12, cnt, t0 + r[u] + b);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kSlowBatch; ++u) {
-            if (!len[u]) continue;                                    /* (the sixteen lanes of a chunk agree) */
-            uint32_t w = v[u] << (8u * (b & 3u));
-            w |= __shfl_xor(w, 1, 16);
-            w |= __shfl_xor(w, 2, 16);
-            u32x4 x;
-            x.x = __shfl(w, 0, 16); x.y = __shfl(w, 4, 16); x.z = __shfl(w, 8, 16); x.w = __shfl(w, 12, 16);
-            if (len[u] == 16) { if (b == 0) arena_store16(a.out + t0 + r[u], x); }
-            else if (b < len[u]) a.out[t0 + r[u] + b] = (uint8_t)v[u];  /* the output's end: these bytes and no others */
-        }
-    }
+    copy_slow_list<kRT>(s_slow, s_nslow, a.out, t0, tlen,
+                        [&](uint32_t ip, uint64_t cur) { return chunk_byte<kAp>(a, tn, ip, cnt, cur); });
 }
 
 } // namespace

@@ -179,6 +179,21 @@ def test_tiles_inside_a_payload_and_inside_a_trun_array(ctx):
     assert int(s["nal_count"]) == 1
 
 
+def test_tiles_of_slow_chunks_only_and_a_partial_last_chunk(ctx):
+    """18 801 AUs of one 3-byte NAL, L = 4, one fragment: a 7-byte record never holds 16 payload bytes, so every chunk of every
+    tile is on the copy's slow list -- the tiles of the trun array, the tile the payload begins in, a whole tile of payload
+    alone -- and the last tile ends in a chunk of 7 bytes"""
+    rng = np.random.default_rng(55)
+    n = 18801
+    starts = 3 * np.arange(n)
+    stream = rng.integers(0, 256, size=3 * n, dtype=np.uint8)
+    case = (stream, R.entries(starts, starts + 3), None, np.arange(n, dtype=np.uint32), R.au_records(np.zeros(n, np.uint32)), None, None)
+    out, want, s, _ = run(ctx, case, R.params(length_size=4, sample_duration=3003))
+    payload = int(want[1][0])                                   # where the first sample begins
+    assert int(s["nal_count"]) == 1 and len(out) == payload + 7 * n and len(out) % 16 == 7
+    assert (payload + TILE - 1) // TILE < len(out) // TILE, "a whole tile of payload alone"
+
+
 def test_more_plan_blocks_than_one_scan_pass(ctx):
     """PASS plan workgroups and five entries more on both sides: PASS * W + 5 = 524 293 NALs, one an AU, so as many AUs; NALs of
     0..3 bytes, L = 1, an IRAP every 64th AU with HBS_MP4_CUT_AT_IRAP: 8 193 fragments, 11 MB of output"""

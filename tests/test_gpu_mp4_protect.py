@@ -251,6 +251,20 @@ def uniform_output(b, V, iv):
     return out.reshape(-1), so, np.full(n, fin - 112, dtype=np.uint64), fr, P.summary(0, n, n, n, n * fout)
 
 
+def test_a_tile_of_slow_chunks_only_and_a_partial_last_chunk(ctx):
+    """350 fragments of one 7-byte sample, iv_size 8: an mdat has 15 bytes, so no chunk lies wholly inside one.  All 4 096 chunks of
+    the first tile are on the copy's slow list; the second tile has 614 bytes, 6 in its last chunk"""
+    rng = np.random.default_rng(55)
+    n = 350
+    b = build(ctx, rng, case=uniform_case(n, rng), flags=0, max_samples=1)
+    assert len(b["frags"]) == n and (b["frags"]["out_bytes"] == 112 + 7).all()
+    iv = ivs(rng, n, 8)
+    out, want, _, _ = run(ctx, b, 8, iv)
+    assert len(out) == 189 * n == TILE + 614 and 614 % 16 == 6
+    quick = uniform_output(b, 8, iv)
+    assert all(np.array_equal(x, y) for x, y in zip(quick[:4], want[:4])) and quick[4] == want[4]
+
+
 def test_more_fragment_blocks_than_one_scan_pass(ctx):
     """70 000 fragments of one sample against the plain loop, and against the same output as array arithmetic; then 525 000 of
     them, which is more plan workgroups (of fragments and of samples) than scan_parts takes in one pass, against the arithmetic"""

@@ -224,6 +224,21 @@ def test_many_nals_of_one_small_packet(ctx):
         assert int(s["nal_count"]) == 5000 and int(s["reserved"][2]) == 0
 
 
+def test_a_tile_of_slow_chunks_only_and_a_partial_last_chunk(ctx):
+    """4 500 NALs of 3 bytes, framing 0: 15 output bytes a NAL, so no chunk lies behind a 12-byte header and ends inside its
+    NAL.  All 4 096 chunks of the first tile are on the copy's slow list; the second tile has 1 964 bytes, 12 in its last chunk"""
+    rng = np.random.default_rng(57)
+    n = 4500
+    starts = 3 * np.arange(n)
+    stream = rng.integers(0, 256, size=3 * n, dtype=np.uint8)
+    stream[starts] &= 0x5F
+    nal_au = (np.arange(n) // 3).astype(np.uint32)
+    pts = 3003 * np.arange(n // 3, dtype=np.uint64)
+    out, _, s, _ = run(ctx, stream, R.entries(starts, starts + 3), nal_au, n // 3, pts, R.params(max_payload=1188, framing=0, seq=65000))
+    assert len(out) == int(s["stream_bytes"]) == 15 * n == TILE + 1964 and 1964 % 16 == 12
+    assert int(s["nal_count"]) == n and int(s["reserved"][2]) == 0
+
+
 def test_sequence_numbers_across_two_calls(ctx):
     """seq starts at 65 530 and wraps; the first call ends inside an access unit (HBS_RTP_OPEN_END), the second is seeded from
     reserved[1] and takes its tables by pointer offset: together they are the one call"""
