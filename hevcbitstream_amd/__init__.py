@@ -26,7 +26,8 @@ from .api import (Context, HbsError, NAL_ENTRY, PARSED, SUMMARY, ST_ERROR, ST_TR
                   MP4_READ_PARAMS, MP4_TRACK, mp4_read_params, mp4_init_read,
                   MP4_STBL, MP4_STBL_CO64, mp4_stbl_find, mp4_track_read,
                   MP4_STBL_WRITE_PARAMS, mp4_stbl_write_params, mp4_stbl_write_bytes, mp4_moov,
-                  MP4_PROTECT_PARAMS, MP4_TENC, MP4_SCHEME_CENC, MP4_SCHEME_CBCS, mp4_protect_params, mp4_protect_bytes, mp4_init_protect)
+                  MP4_PROTECT_PARAMS, MP4_TENC, MP4_SCHEME_CENC, MP4_SCHEME_CBCS, mp4_protect_params, mp4_protect_bytes, mp4_init_protect,
+                  MP4_SENC_PARAMS, MP4_SENC_CLEAR_IF_ABSENT, mp4_senc_params, mp4_init_unprotect)
 
 __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", "ST_TRAILING03",
            "ST_UNTERMINATED", "library_path", "load_library", "source_digest",
@@ -49,4 +50,5 @@ __all__ = ["Context", "HbsError", "NAL_ENTRY", "PARSED", "SUMMARY", "ST_ERROR", 
            "MP4_READ_PARAMS", "MP4_TRACK", "mp4_read_params", "mp4_init_read",
            "MP4_STBL", "MP4_STBL_CO64", "mp4_stbl_find", "mp4_track_read",
            "MP4_STBL_WRITE_PARAMS", "mp4_stbl_write_params", "mp4_stbl_write_bytes", "mp4_moov",
-           "MP4_PROTECT_PARAMS", "MP4_TENC", "MP4_SCHEME_CENC", "MP4_SCHEME_CBCS", "mp4_protect_params", "mp4_protect_bytes", "mp4_init_protect"]
+           "MP4_PROTECT_PARAMS", "MP4_TENC", "MP4_SCHEME_CENC", "MP4_SCHEME_CBCS", "mp4_protect_params", "mp4_protect_bytes", "mp4_init_protect",
+           "MP4_SENC_PARAMS", "MP4_SENC_CLEAR_IF_ABSENT", "mp4_senc_params", "mp4_init_unprotect"]

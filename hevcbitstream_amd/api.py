@@ -87,6 +87,8 @@ MP4_HEV1 = 1
 MP4_PROTECT_PARAMS = np.dtype([("iv_size", "<u4"), ("flags", "<u4"), ("reserved", "<u4", (6,))])
 MP4_TENC = np.dtype([("scheme", "<u4"), ("crypt_byte_block", "u1"), ("skip_byte_block", "u1"), ("iv_size", "u1"), ("constant_iv_size", "u1"),
                      ("kid", "u1", (16,)), ("constant_iv", "u1", (16,)), ("reserved", "<u4", (6,))])
+MP4_SENC_PARAMS = np.dtype([("iv_size", "<u4"), ("track_id", "<u4"), ("flags", "<u4"), ("reserved", "<u4", (5,))])
+MP4_SENC_CLEAR_IF_ABSENT = 1
 MP4_SCHEME_CENC = 0x63656E63      # 'cenc'
 MP4_SCHEME_CBCS = 0x63626373      # 'cbcs'
 # layout of hbs_mp4_read_params / hbs_mp4_track (hbs_mp4_samples, hbs_mp4_init_read_host)
@@ -141,7 +143,8 @@ EXPORTS = ["hbs_version", "hbs_ctx_create", "hbs_ctx_destroy", "hbs_ctx_set_stre
            "hbs_mp4_samples", "hbs_mp4_init_read_host", "hbs_mp4_stbl_samples", "hbs_mp4_stbl_find_host",
            "hbs_mp4_track_read_host",
            "hbs_mp4_stbl_write", "hbs_mp4_stbl_write_bytes_host", "hbs_mp4_moov_host",
-           "hbs_mp4_protect", "hbs_mp4_protect_bytes_host", "hbs_mp4_init_protect_host"]
+           "hbs_mp4_protect", "hbs_mp4_protect_bytes_host", "hbs_mp4_init_protect_host",
+           "hbs_mp4_senc_samples", "hbs_mp4_init_unprotect_host"]
 
 
 PAIR_REPORT = np.dtype([("chunks", "<u4"), ("probed", "<u4"), ("rejected", "<u4"), ("accepted_fast", "<u4"),
@@ -345,6 +348,12 @@ def load_library():
     lib.hbs_mp4_init_protect_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                               C.c_uint64]
     lib.hbs_mp4_init_protect_host.restype = C.c_int64
+    lib.hbs_mp4_senc_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.hbs_mp4_senc_samples.restype = C.c_int
+    lib.hbs_mp4_init_unprotect_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.hbs_mp4_init_unprotect_host.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -599,6 +608,36 @@ def mp4_init_protect(init_bytes, kid, scheme=MP4_SCHEME_CENC, iv_size=8, constan
     if got != need:
         raise HbsError("hbs_mp4_init_protect_host: %d, then %d" % (need, got))
     return out.tobytes()
+
+
+def mp4_senc_params(iv_size=8, track_id=0, flags=0):
+    """an hbs_mp4_senc_params record (ndarray[MP4_SENC_PARAMS] of one, host memory)"""
+    p = np.zeros(1, dtype=MP4_SENC_PARAMS)
+    p["iv_size"], p["track_id"], p["flags"] = iv_size, track_id, flags
+    return p
+
+
+def mp4_init_unprotect(init_bytes, track_id=0):
+    """hbs_mp4_init_unprotect_host: the clear init segment of a protected one (bytes-like), with what its sinf and pssh boxes
+    said.  Returns (bytes, tenc ndarray[MP4_TENC] of one, the frma fourcc as an int, [the whole 'pssh' boxes as bytes]).
+    Raises HbsError for what the call refuses."""
+    lib = load_library()
+    seg = np.frombuffer(bytes(init_bytes), dtype=np.uint8)
+    tenc = np.zeros(1, dtype=MP4_TENC)
+    fmt, n_pssh = C.c_uint32(0), C.c_uint64(0)
+    head = (seg.ctypes.data_as(C.c_void_p) if seg.size else None, seg.size, int(track_id), tenc.ctypes.data_as(C.c_void_p), C.byref(fmt))
+    need = int(lib.hbs_mp4_init_unprotect_host(*head, None, None, 0, C.byref(n_pssh), None, 0))
+    if need < 0:
+        raise HbsError("hbs_mp4_init_unprotect_host: error %d" % need)
+    k = int(n_pssh.value)
+    off, size = np.zeros(max(k, 1), dtype=np.uint64), np.zeros(max(k, 1), dtype=np.uint64)
+    out = np.zeros(max(need, 1), dtype=np.uint8)
+    got = int(lib.hbs_mp4_init_unprotect_host(*head, off.ctypes.data_as(C.c_void_p), size.ctypes.data_as(C.c_void_p), k, C.byref(n_pssh),
+                                              out.ctypes.data_as(C.c_void_p), need))
+    if got != need or int(n_pssh.value) != k:
+        raise HbsError("hbs_mp4_init_unprotect_host: %d, then %d" % (need, got))
+    raw = seg.tobytes()
+    return out[:need].tobytes(), tenc, int(fmt.value), [raw[int(o):int(o) + int(z)] for o, z in zip(off[:k], size[:k])]
 
 
 def mp4_stbl_write_params(flags=0, max_chunk_samples=0, sample_duration=0, base_time=0, data_offset=0):
@@ -1577,6 +1616,41 @@ class Context:
         fr = self._empty(max(n_frags, 1) * MP4_FRAG.itemsize)
         s = self._run(name, self.mp4_protect_async(*args, out, summary, sample_off=so, sample_size=ss, frag_out=fr, out_cap=need), summary)
         return out[:need], _host(so, n, np.uint64), _host(ss, n, np.uint64), _host(fr, n_frags, MP4_FRAG), s
+
+    def mp4_senc_samples_async(self, data, in_bytes, frag, n_frags, sample_size, n_samples, params, sub_first, sub, iv, summary, sub_cap=None):
+        """Enqueue hbs_mp4_senc_samples on the current torch stream.  data / frag / sample_size / sub_first / sub / iv / summary are
+        device tensors (sample_size may be None; sub None: plan only; iv may be None with iv_size 0); params is an
+        ndarray[MP4_SENC_PARAMS] of one in host memory.  sub_cap (entries) defaults to what sub holds.  Returns the call's
+        return code (0, or HBS_E_ARG for arguments it refuses)."""
+        self._bind_stream()
+        if sub_cap is None:
+            sub_cap = _holds(sub, CENC_SUBSAMPLE.itemsize)
+        params, params_p = _rec(params, MP4_SENC_PARAMS)
+        return self.lib.hbs_mp4_senc_samples(self.h, _p(data) if in_bytes else None, int(in_bytes), _p(frag) if n_frags else None, int(n_frags),
+                                             _p(sample_size), int(n_samples), params_p, _p(sub_first), _p(sub), int(sub_cap), _p(iv),
+                                             _p(summary))
+
+    def mp4_senc_samples(self, data, frags, sample_size=None, iv_size=8, track_id=0, flags=0, in_bytes=None, n_samples=None):
+        """Convenience: the subsample table and the IVs of the protected fragments of `data` (device uint8 tensor) that `frags`
+        (ndarray[MP4_FRAG], as mp4_samples returns it) names.  sample_size: None or one uint64 per sample, a host array or a
+        device uint8 tensor of its bytes; n_samples: default the sum of the fragments' samples.  Plans first, allocates the exact
+        tables, runs.  Returns (sub_first device tensor, sub device tensor, iv device tensor or None, summary record): device
+        uint8 tensors of the tables' bytes, in the form cenc_crypt and cbcs_crypt take."""
+        name = "hbs_mp4_senc_samples"
+        d_frag, n_frags = self._dv(frags, MP4_FRAG)
+        d_size, _ = self._dv(sample_size, np.uint64)
+        n = int(np.asarray(frags)["samples"].sum()) if n_samples is None else int(n_samples)
+        prm = mp4_senc_params(iv_size=iv_size, track_id=track_id, flags=flags)
+        nbytes = int(data.numel()) if in_bytes is None else int(in_bytes)
+        summary = self._zeros()
+        first = self._empty((n + 1) * 8)
+        iv = self._empty(max(n, 1) * 16) if iv_size else None
+        args = (data, nbytes, d_frag, n_frags, d_size, n, prm, first)
+        s = self._run(name, self.mp4_senc_samples_async(*args, None, iv, summary), summary, " (sample {0}, fragment {1})")
+        total = int(s["nal_count"])
+        sub = self._empty(max(total, 1) * CENC_SUBSAMPLE.itemsize)
+        s = self._run(name, self.mp4_senc_samples_async(*args, sub, iv, summary, sub_cap=total), summary)
+        return first, sub[: total * CENC_SUBSAMPLE.itemsize], (iv[: n * 16] if iv is not None else None), s
 
     def mp4_stbl_samples_async(self, data, in_bytes, tables, summary, sample_cap=0, sample_off=None, sample_size=None, dts=None, pts=None,
                                sample_flags=None):

@@ -32,6 +32,7 @@
 #include "hbs_mp4.h"
 #include "hbs_mp4rd.h"
 #include "hbs_mp4prot.h"
+#include "hbs_mp4senc.h"
 #include "hbs_mp4stbl.h"
 #include "hbs_mp4stblw.h"
 
@@ -62,8 +63,9 @@ struct Buf { void* ptr; uint64_t bytes; };     /* grow-only device memory (grow)
  * kCws    hbs_cenc_subsamples' scratch
  * kYws    hbs_cenc_crypt's scratch (tables about the samples and the entries; the key is never in it); hbs_cbcs_crypt's too: the
  *         same tables, and the calls of a context are ordered by its one stream
- * kEws    hbs_mp4_protect's scratch */
-enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kCws, kYws, kEws, kBufs };
+ * kEws    hbs_mp4_protect's scratch
+ * kNws    hbs_mp4_senc_samples' scratch */
+enum { kDesc, kWs, kAhead, kWs2, kZeros, kFws, kAws, kLws, kTws, kMws, kIws, kRws, kUws, kOws, kPws, kQws, kSws, kVws, kXws, kCws, kYws, kEws, kNws, kBufs };
 /* a persistent scan kernel's workgroups: launched, what the GPU holds (`blocks` may be cut: cut_grids), per compute unit */
 struct Grid { int blocks, full, per_cu; };
 
@@ -877,6 +879,27 @@ int hbs_mp4_protect(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const hb
         a.tiles = n_frags ? hbs::mp4prot_tiles(out_cap) : 0;                 /* the copy's grid: the tiles out_cap has room for */
     }
     return carve_and_launch(c, c->buf[kEws], "hipMalloc(MP4 protect scratch)", a, hbs::lay_mp4prot, hbs::launch_mp4_protect, "launch_mp4_protect");
+}
+
+int hbs_mp4_senc_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const hbs_mp4_frag* d_frag, uint64_t n_frags,
+                         const uint64_t* d_sample_size, uint64_t n_samples, const hbs_mp4_senc_params* params,
+                         uint64_t* d_sub_first, hbs_cenc_subsample* d_sub, uint64_t sub_cap, uint8_t* d_iv, hbs_summary* d_summary)
+{
+    static_assert(sizeof(hbs_mp4_senc_params) == 32 && sizeof(hbs::SencFind) == 40, "hbs_mp4_senc_samples layouts");
+    if (!c || !d_summary || !d_sub_first || !hbs::mp4_senc_params_ok(params)) return HBS_E_ARG;
+    if (n_frags > 0xFFFFFFFFull || n_samples > 0xFFFFFFFFull || in_bytes > hbs::kRdMaxIn) return HBS_E_ARG;
+    if (n_frags ? (!d_frag || (in_bytes && !d_in)) : n_samples != 0) return HBS_E_ARG;
+    if (n_samples && params->iv_size && !d_iv) return HBS_E_ARG;
+    if (misaligned_refused(c, "input/fragment table/IV/summary pointers must be 16-byte aligned, the sample sizes and the two subsample tables 8-byte",
+                           {d_in, d_frag, d_iv, d_summary}, {d_sample_size, d_sub_first, d_sub})) return HBS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return HBS_E_NO_DEVICE;
+    hbs::Mp4SencArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_in; a.n = in_bytes; a.frag = d_frag; a.n_frags = n_frags;
+    a.sample_size = reinterpret_cast<const unsigned long long*>(d_sample_size); a.n_samples = n_samples;
+    a.V = params->iv_size; a.track_id = params->track_id; a.flags = params->flags;
+    a.sub_first = reinterpret_cast<unsigned long long*>(d_sub_first); a.sub = d_sub; a.sub_cap = sub_cap; a.iv = d_iv; a.summary = d_summary;
+    return carve_and_launch(c, c->buf[kNws], "hipMalloc(MP4 senc scratch)", a, hbs::lay_mp4senc, hbs::launch_mp4_senc_samples, "launch_mp4_senc_samples");
 }
 
 int hbs_mp4_samples(hbs_ctx* c, const uint8_t* d_in, uint64_t in_bytes, const void* d_seg, uint64_t seg_stride, uint64_t n_segs,

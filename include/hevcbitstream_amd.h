@@ -115,13 +115,13 @@ typedef struct hbs_ctx hbs_ctx;
  *   hbs_lenpref_to_annexb, hbs_ts_demux, hbs_ts_mux, hbs_au_insert, hbs_au_keep, hbs_rtp_pack (with and without
  *   HBS_RTP_AGGREGATE), hbs_rtp_unpack, hbs_rtp_order, hbs_mp4_fragment, hbs_mp4_samples,
  *   hbs_mp4_stbl_samples, hbs_mp4_stbl_write, hbs_au_times, hbs_cenc_subsamples, hbs_cenc_crypt,
- *   hbs_cbcs_crypt, hbs_mp4_protect.
+ *   hbs_cbcs_crypt, hbs_mp4_protect, hbs_mp4_senc_samples.
  * hbs_cenc_crypt takes its key and iv0 from host memory when it is called: a captured graph replays with the key and iv0 it was
  * captured with.  So does hbs_cbcs_crypt, and with the direction and the pattern of the capture.
  * The list is what tests/test_gpu_graphs.py, tests/test_gpu_scan.py, tests/test_gpu_rtp.py, tests/test_gpu_rtp_ap.py,
  * tests/test_gpu_rtp_unpack.py, tests/test_gpu_rtp_order.py, tests/test_gpu_mp4.py, tests/test_gpu_mp4_read.py,
  * tests/test_gpu_mp4_stbl.py, tests/test_gpu_mp4_stbl_write.py, tests/test_gpu_au_times.py, tests/test_gpu_cenc.py and
- * tests/test_gpu_cbcs.py and tests/test_gpu_mp4_protect.py replay, no more: hbs_parse_headers_compact,
+ * tests/test_gpu_cbcs.py and tests/test_gpu_mp4_protect.py and tests/test_gpu_mp4_senc.py replay, no more: hbs_parse_headers_compact,
  * hbs_parse_materialize, hbs_write_headers and hbs_access_units do not wait either, but no test has replayed them, and three
  * of the calls above were wrong at a replay until one did -- capture them at your own risk.
  * A replay is the captured call on what the buffers hold then: every argument the host passed (counts, byte sizes, capacities,
@@ -623,6 +623,8 @@ int64_t hbs_mp4_init_host(const hbs_mp4_init_params* p, int flags,
  * no encryption (senc, saiz, saio are stepped over; the samples stay as they are); no sidx-driven access (pass the segments);
  * a file without fragments is read by hbs_mp4_stbl_samples, below; one lane walks a segment's chain.  (hbs_cenc_crypt, below,
  * decrypts samples in place from the tables this call writes, given their subsample table and IVs from elsewhere.)
+ * (That elsewhere can be the fragments themselves: hbs_mp4_senc_samples, below, reads both from the senc boxes of the fragments
+ * d_frag names, and hbs_mp4_init_unprotect_host turns an 'encv' init segment into one hbs_mp4_init_read_host accepts.)
  *
  * hbs_mp4_init_read_host (plain C, no GPU): the counterpart of hbs_mp4_init_host.  It walks seg[0, n) by the box rule above:
  * moov; its trak boxes in order -- tkhd (version 0 or 1: track_id, width and height, the integer parts), mdia / mdhd (version
@@ -1665,6 +1667,8 @@ int hbs_au_times(hbs_ctx* ctx, const hbs_access_unit* d_au, uint64_t n_aus,
  * byte either -- beyond d_iv (iv_mode 1) and the summary; no load touches a granule that holds no byte of d_data[0, data_bytes);
  * no host synchronisation.  The key is expanded on the host (176 bytes of round keys) and goes to the kernels by value: it is
  * never stored in the context's scratch or any other device buffer.  Scratch: 16 bytes a sample, 64 per 256 samples, 65 KiB.
+ * To DECRYPT fragments that carry their tables in senc boxes, hbs_mp4_senc_samples (below) writes d_sub_first, d_sub and d_iv in
+ * the form this call reads with iv_mode 0.
  */
 #define HBS_CENC_ALIGN16      1u            /* hbs_cenc_plan_params.flags: protected ranges are whole 16-byte blocks */
 #define HBS_CENC_SCHEME_CENC  0x63656E63u   /* 'cenc' */
@@ -1747,6 +1751,8 @@ int hbs_cenc_crypt(hbs_ctx* ctx, uint8_t* d_data, uint64_t data_bytes,
  * crypt blocks a step, each lane's previous ciphertext block taken from the lane below.  When ENCRYPTING it stays on its one
  * lane, because C_j needs C_(j-1): that is CBC, not this library.  A sample of one 1 MiB NAL at 1:9 is about 6 500 dependent
  * blocks on one lane; throughput of encryption comes from many entries, not from long ones.
+ * To decrypt protected fragments: hbs_mp4_senc_samples (below) gives d_sub_first, d_sub and, with per-sample IVs, d_iv;
+ * hbs_mp4_init_unprotect_host gives the pattern and, with iv_size 0, the constant IV that goes into iv0.
  */
 #define HBS_CBCS_DECRYPT     1u   /* flags: the inverse direction (CBC is not its own inverse) */
 #define HBS_CBCS_WHOLE_RUNS  2u   /* flags: a last run of fewer than crypt_byte_block whole blocks stays clear */
@@ -1844,6 +1850,7 @@ int hbs_cbcs_crypt(hbs_ctx* ctx, uint8_t* d_data, uint64_t data_bytes,
  * behind init + n, or outside the pssh boxes, is read.
  * OUT OF SCOPE: reading senc / encv back (hbs_mp4_samples and hbs_mp4_init_read_host stay as they are: an 'encv' entry is not
  * a video entry to them); key rotation (sbgp / sgpd 'seig'); cens and cbc1; several tracks; building pssh payloads.
+ * (Reading back is the business of calls of its own: hbs_mp4_senc_samples and hbs_mp4_init_unprotect_host, below.)
  */
 typedef struct hbs_mp4_protect_params {   /* HOST memory, 32 bytes */
     uint32_t iv_size;        /* 0, 8 or 16: IV bytes a sample in the senc; 0: none (tenc's constant IV, the usual cbcs form) */
@@ -1874,6 +1881,104 @@ int64_t hbs_mp4_init_protect_host(const uint8_t* init, uint64_t n, uint32_t trac
                                   const hbs_mp4_tenc* t,
                                   const uint8_t* const* pssh, const uint64_t* pssh_bytes, uint64_t n_pssh /* whole 'pssh' boxes */,
                                   uint8_t* out, uint64_t cap);   /* bytes needed; written only when cap suffices; HBS_E_ARG */
+
+/*
+ * ---- protected fragments read back: senc to the subsample table and the IVs on the device; encv back to hvc1 on the host ----
+ * hbs_mp4_senc_samples is the inverse of hbs_mp4_protect, and reads other packagers' fragments too: from the senc box of every
+ * fragment it makes d_sub_first / d_sub / d_iv, the tables hbs_cenc_crypt (iv_mode 0) and hbs_cbcs_crypt read.  With it a
+ * protected segment goes hbs_mp4_samples -> hbs_mp4_senc_samples -> hbs_cenc_crypt / hbs_cbcs_crypt(HBS_CBCS_DECRYPT) ->
+ * hbs_lenpref_to_annexb and comes out as Annex-B with no byte visiting the host.  tests/_mp4_senc_ref.py restates both calls as
+ * one loop each.
+ *
+ * INPUT.  Fragment r has its moof at d_in + out_off_r and is d_in[out_off_r, out_off_r + out_bytes_r) of d_frag[r]: the table
+ * hbs_mp4_samples writes (out_bytes reaches to the next moof) or hbs_mp4_protect's d_frag_out.  Fragments may lie anywhere in
+ * d_in, in any order.  Sample numbering is hbs_mp4_protect's pointer-offset rule: first_au_r - first_au_0 equals the sum of
+ * `samples` of the fragments below r, and the last sum is n_samples.  A fragment with samples == 0 has only its bounds checked.
+ * d_sample_size (optional) is the table hbs_mp4_samples wrote for the same fragments.
+ * INSIDE THE MOOF the box rule of hbs_mp4_samples applies: a size of 1 is followed by a 64-bit size, a size of 0 runs to the
+ * container's end (the fragment's, for the moof), children of unknown type are stepped over.  Word 1 of the fragment must be
+ * 'moof'.  The traf is chosen exactly as hbs_mp4_samples chooses it: the first whose tfhd carries params->track_id (0: the
+ * first traf); every traf in front of it must have a well-formed tfhd; every child of the moof and of those trafs must hold
+ * the box rule.  tfdt, trun and mfhd are not looked at: `samples` is the caller's word, as hbs_mp4_samples counted it.  Of the
+ * chosen traf's children the first 'senc' is read.  Its payload is version/flags(4) sample_count(4), then a sample: IV (V =
+ * iv_size bytes) and, with flag 0x2, subsample_count(2) and that many clear(2) protect(4), all big-endian; without flag 0x2
+ * nothing more, and the sample is one entry (0, size_s) when size_s > 0 and none otherwise, which needs d_sample_size.  Bytes of
+ * the box behind the last sample are ignored.  No mdat byte is ever read.
+ * RESULT.  d_sub_first[s] = the entries of the samples below s (n_samples + 1 words, the total last); d_sub the entries in
+ * the host byte order of hbs_cenc_subsample; d_iv[16 s, 16 s + 16) the IV: V = 8 the IV and eight zero bytes (the form
+ * hbs_cenc_crypt iv_mode 0 reads), V = 16 as stored, V = 0 d_iv is untouched.  On the output of hbs_mp4_protect the three tables
+ * are the ones that went into it, value for value.
+ * HBS_SENC_CLEAR_IF_ABSENT: a chosen traf without a senc gives each of its samples of size z > 0 the entries of
+ * hbs_cenc_subsamples' EMIT(z, 0): ceil(z / 65535) - 1 entries (65535, 0), then the rest; its d_iv is zero; d_sample_size is
+ * needed.  Without the flag such a traf is a fragment error.
+ * ERRORS, in the two levels of hbs_mp4_protect.  A FRAGMENT ERROR is HBS_E_ARG with reserved[1] = 1 + the lowest fragment for
+ * which any of these holds: it leaves the buffer; word 1 is not 'moof', or the moof is larger than out_bytes; a child breaks
+ * the box rule; a tfhd is missing or too short; no traf is chosen although samples > 0; the senc's version is not 0 or its
+ * flags are other than 0 or 2; its sample_count is not samples_r; a sample of the senc leaves the box; there is no senc and the
+ * flag is not set; d_sample_size is missing where the rule needs it; the numbering rule is broken (as hbs_mp4_protect states
+ * it).  Only when no fragment offends a SAMPLE ERROR is raised: HBS_E_ARG with reserved[0] = 1 + the lowest sample whose size
+ * is above 2^32 - 1 where the size becomes an entry.  A total of entries at or above 2^48 is HBS_E_CAPACITY with zero counts.
+ * With a d_sub, sub_cap below the total is HBS_E_CAPACITY with the counts right.  On any error only the summary is written.
+ * d_sub == NULL: plan only, the summary and d_sub_first (and d_iv) are written, as hbs_cenc_subsamples does.
+ * d_summary: nal_count = entries, nal_found = n_samples, rbsp_bytes = the sum of protect over all entries, stream_bytes =
+ * in_bytes, stop_reason = 0, reserved[2] = fragments whose senc was read; with HBS_E_ARG, and at 2^48 entries, nal_count,
+ * rbsp_bytes and reserved[2] are 0.
+ * Refused with HBS_E_ARG at once, nothing touched: params NULL, an iv_size other than 0, 8, 16, unknown flags, a reserved word
+ * not 0, n_frags or n_samples above 2^32 - 1, in_bytes above 2^62, n_frags == 0 with n_samples != 0, a missing d_sub_first or
+ * d_summary, a missing d_frag or (in_bytes > 0) d_in with n_frags > 0, iv_size > 0 without a d_iv when n_samples > 0, a
+ * misaligned pointer.  Alignment: d_in, d_frag, d_iv, d_summary 16 bytes; d_sample_size, d_sub_first, d_sub 8.
+ * No load touches a 16-byte granule that holds no byte of d_in[0, in_bytes); nothing is stored outside d_sub_first[0,
+ * n_samples], d_sub[0, total), d_iv[0, 16 n_samples) and the summary; no host synchronisation (HIP graphs, above).  Scratch is
+ * a slot of its own in the context's workspace, sized by n_frags and n_samples alone: 64 bytes; 52 bytes a fragment and 80
+ * per 256 fragments; 16 bytes a sample, 128 per 256 samples and 64 for each of the min(2 048, 4 per 256 samples) workgroups
+ * that write entries; every table rounded up to 256 bytes.
+ * WORK.  One lane finds a fragment's boxes.  A lane per sample then takes the traf's saiz as a HINT: the sizes in front of a
+ * sample give the place its record would have, the lane reads subsample_count there and accepts the place when V + 2 + 6 n
+ * is the hinted size and the record stays in the box.  When every sample of a fragment passes, the places are the serial
+ * walk's by induction from sample 0.  A fragment without a usable saiz (none, another sample_count, too short), or with one
+ * failed check, is walked by one lane, a step a sample; only that walk can find that a sample leaves the box.  The saiz is
+ * never an authority: the result is defined by the senc alone.  The entries are written a lane an entry.
+ * STATED LIMITS: PIFF 'uuid' sample encryption boxes; auxiliary information outside a senc (a traf with saio but no senc);
+ * key rotation (sbgp / sgpd 'seig'); several tracks in one call; cens / cbc1.
+ *
+ * hbs_mp4_init_unprotect_host (plain C, no GPU): the inverse of hbs_mp4_init_protect_host.  It walks init[0, n) to the moov
+ * (the first; the top-level boxes in front of it hold the box rule of hbs_mp4_init_read_host) and through its children, which
+ * all hold it.  A trak with a 32-bit size field is looked at until one is found: its tkhd must be what hbs_mp4_init_read_host
+ * accepts; with track_id 0 or the tkhd's id, the first mdia, in it the first minf, stbl and stsd are taken, and of the stsd's
+ * entries the first 'encv' that satisfies all of: it holds an hvcC; it holds a sinf (the first) whose frma is 'hvc1' or 'hev1',
+ * whose schm is 'cenc' or 'cbcs' and whose schi / tenc has version 0 or 1, isProtected 1, an iv_size of 0, 8 or 16 and, with
+ * iv_size 0, a constant IV of 8 or 16 bytes; the record is one hbs_mp4_init_protect_host takes (no pattern with 'cenc').
+ * t_out is that record (at tenc version 0 the pattern is 0 whatever the byte holds); it feeds hbs_mp4_senc_params.iv_size and
+ * hbs_cbcs_params (crypt_byte_block, skip_byte_block, iv0).  format_out (optional) is the frma fourcc.  pssh_off / pssh_bytes
+ * list every 'pssh' that is a direct child of the moov, whole boxes as offsets into init; only the first pssh_cap are
+ * written, *n_pssh_out (optional) always is their number.  The output is the segment with that entry renamed to the frma
+ * fourcc, that sinf and the pssh boxes removed and the 32-bit sizes of entry, stsd, stbl, minf, mdia, trak and moov reduced;
+ * it must be one hbs_mp4_init_read_host accepts for that track with that entry, else HBS_E_ARG.  On the output of
+ * hbs_mp4_init_protect_host it returns the segment that went in, byte for byte, and the record that went in.  Returns the
+ * bytes the clear segment takes; out is written only when cap suffices; on an error nothing is written.  HBS_E_ARG: anything
+ * malformed on the way, no such track or entry, one of the seven boxes with a 64-bit or zero size field, n above 2^62, a NULL
+ * init or t_out, a NULL out with cap > 0, NULL lists with pssh_cap > 0.  Every length is bounded before it is used; no byte at
+ * or behind init + n is read.
+ */
+#define HBS_SENC_CLEAR_IF_ABSENT 1u   /* a traf without a senc: its samples are wholly clear (needs d_sample_size) */
+typedef struct hbs_mp4_senc_params {  /* HOST memory, 32 bytes */
+    uint32_t iv_size;      /* 0, 8, 16: tenc default_Per_Sample_IV_Size */
+    uint32_t track_id;     /* as hbs_mp4_read_params.track_id; 0: the first traf */
+    uint32_t flags;        /* HBS_SENC_CLEAR_IF_ABSENT */
+    uint32_t reserved[5];  /* 0 */
+} hbs_mp4_senc_params;
+
+int hbs_mp4_senc_samples(hbs_ctx* ctx, const uint8_t* d_in, uint64_t in_bytes,
+                         const hbs_mp4_frag* d_frag, uint64_t n_frags,          /* as hbs_mp4_samples / hbs_mp4_protect wrote it */
+                         const uint64_t* d_sample_size /* nullable, n_samples: as hbs_mp4_samples wrote it */, uint64_t n_samples,
+                         const hbs_mp4_senc_params* params,
+                         uint64_t* d_sub_first /* n_samples + 1 */, hbs_cenc_subsample* d_sub /* NULL: plan only */, uint64_t sub_cap,
+                         uint8_t* d_iv /* n_samples x 16; written when iv_size > 0; nullable when 0 */,
+                         hbs_summary* d_summary);
+int64_t hbs_mp4_init_unprotect_host(const uint8_t* init, uint64_t n, uint32_t track_id /* 0: the first track with such an entry */,
+                                    hbs_mp4_tenc* t_out, uint32_t* format_out /* frma: 'hvc1' / 'hev1' */,
+                                    uint64_t* pssh_off, uint64_t* pssh_bytes, uint64_t pssh_cap, uint64_t* n_pssh_out,
+                                    uint8_t* out, uint64_t cap);   /* bytes the clear init segment takes; written only when cap suffices */
 
 /*
  * ---- access-unit delimiters and parameter sets in front of access units ---------------------------------------------
