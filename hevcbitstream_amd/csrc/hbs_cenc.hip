@@ -244,13 +244,7 @@ __global__ __launch_bounds__(kT) void k_cenc_samples(CencArgs a)
 /* one workgroup of kPlanLanes: the lowest non-zero part_s word */
 __device__ __forceinline__ uint64_t lowest_bad_sample(const CencArgs& a)
 {
-    const uint64_t blocks = (a.n_samples + kT - 1) / kT;
-    uint64_t bad = 0;
-    for (uint64_t i = threadIdx.x; i < blocks; i += kPlanLanes) {
-        const uint64_t x = a.part_s[i * 8];
-        if (x && (!bad || x < bad)) bad = x;
-    }
-    return block_min_nonzero(bad);
+    return min_nonzero_of<8>(a.part_s, (a.n_samples + kT - 1) / kT);
 }
 
 __global__ __launch_bounds__(kPlanLanes) void k_cenc_begin(CencArgs a)

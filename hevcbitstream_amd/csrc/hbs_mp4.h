@@ -9,7 +9,7 @@
 #ifndef HBS_MP4_H
 #define HBS_MP4_H
 
-#include "hbs_common.h"
+#include "hbs_mp4box.h"
 
 namespace hbs {
 
@@ -23,8 +23,6 @@ constexpr uint32_t kMp4MoofHead = 88;                /* bytes of a fragment in f
 constexpr uint32_t kMp4FragFixed = 96;               /* ... and with the mdat header: what a fragment adds to 16 S + P */
 constexpr uint64_t kMp4MaxSamples = (0xFFFFFFFFull - kMp4MoofHead) / 16u;     /* 88 + 16 S is a 32-bit box size      */
 constexpr uint64_t kMp4MaxPayload = 0xFFFFFFFFull - 8u;                       /* 8 + P too: there is no 64-bit mdat  */
-
-#define HBS_MP4_FOURCC(a, b, c, d) (((uint32_t)(a) << 24) | ((uint32_t)(b) << 16) | ((uint32_t)(c) << 8) | (uint32_t)(d))
 
 HBS_HD uint64_t mp4_fragment_bytes(uint64_t samples, uint64_t sample_bytes) { return kMp4FragFixed + 16u * samples + sample_bytes; }
 
@@ -161,7 +159,7 @@ struct Mp4Writer {
     void end(uint64_t at, uint64_t behind = 0)                  /* behind: bytes of the box that the caller appends later */
     {
         const uint64_t size = n - at + behind;
-        if (p) { p[at] = (uint8_t)(size >> 24); p[at + 1] = (uint8_t)(size >> 16); p[at + 2] = (uint8_t)(size >> 8); p[at + 3] = (uint8_t)size; }
+        if (p) wr_be32(p + at, (uint32_t)size);
     }
     void matrix() { u32(0x00010000u); zeros(12); u32(0x00010000u); zeros(12); u32(0x40000000u); }
 };

@@ -181,12 +181,7 @@ __global__ __launch_bounds__(kPlanLanes) void k_mp4_scan(Mp4Args a, uint64_t nal
     uint64_t carry[2];
     const uint64_t bad_nal = scan_parts<2>(a.part_n, nal_blocks, carry);
     (void)max_scan_parts(a.last, au_blocks);
-    uint64_t bad_au = 0;
-    for (uint64_t i = threadIdx.x; i < au_blocks; i += kPlanLanes) {
-        const uint64_t x = a.bad_a[i];
-        if (x && (!bad_au || x < bad_au)) bad_au = x;
-    }
-    bad_au = block_min_nonzero(bad_au);
+    const uint64_t bad_au = min_nonzero_of(a.bad_a, au_blocks);
     if (threadIdx.x == 0) {
         a.ctl[kBadNal] = bad_nal; a.ctl[kBadAu] = bad_au;
         a.ctl[kRecBytes] = carry[0]; a.ctl[kKept] = carry[1];

@@ -4,7 +4,7 @@
  * host/device inline functions -- mp4prot_frag_ok is the fragment rule, mp4prot_sample_tables and mp4prot_sample_entries the two
  * groups of the sample rule, mp4prot_moof_byte the byte at a moof-relative offset of the output; the kernels of
  * hbs_mp4prot.hip, the host checks and the tests all run them -- the init segment's rewriter (mp4_init_protect: plain host code,
- * no GPU), and the host-visible launcher.  Everything above the launcher compiles with plain g++.
+ * no GPU; it grows the seven boxes of the reader's Mp4TrackPath), and the host-visible launcher.  Above that: plain g++.
  */
 #ifndef HBS_MP4PROT_H
 #define HBS_MP4PROT_H
@@ -185,18 +185,6 @@ inline void mp4prot_sinf(Mp4Writer& w, uint32_t fourcc, const hbs_mp4_tenc& t)
     w.end(tenc); w.end(schi); w.end(sinf);
 }
 
-/* the first child of type `type` (0: the one that holds byte `holds`) among the boxes that tile p[at, end), which are
- * well-formed: where it begins (its header is p[pos, pos + b.head)); false: none */
-inline bool mp4prot_child(const uint8_t* p, uint64_t at, uint64_t end, uint32_t type, uint64_t holds, uint64_t& pos, Mp4Box& b)
-{
-    while (at < end) {
-        if (!mp4rd_box(p, at, end, b)) return false;
-        if (type ? b.type == type : (holds >= at && holds < at + b.size)) { pos = at; return true; }
-        at += b.size;
-    }
-    return false;
-}
-
 /* hbs_mp4_init_protect_host */
 inline int64_t mp4_init_protect(const uint8_t* init, uint64_t n, uint32_t track_id, const hbs_mp4_tenc* t, const uint8_t* const* pssh,
                                 const uint64_t* pssh_bytes, uint64_t n_pssh, uint8_t* out, uint64_t cap)
@@ -209,31 +197,24 @@ inline int64_t mp4_init_protect(const uint8_t* init, uint64_t n, uint32_t track_
         pssh_total += k;
         if (pssh_total > 0xFFFFFFFFull) return HBS_E_ARG;
     }
-    /* the track, by the reader itself: every box on the way is well-formed behind it */
+    /* the track, by the reader itself, which leaves the boxes that hold the hvcC: moov, trak, mdia, minf, stbl, stsd, the entry */
     hbs_mp4_track trk;
-    if (mp4_init_read_host(init, n, track_id, &trk, nullptr, nullptr, 0) < 0) return HBS_E_ARG;
-    /* the boxes that hold the hvcC: moov, trak, mdia, minf, stbl, stsd, the entry */
-    const uint32_t path[7] = {HBS_MP4_FOURCC('m', 'o', 'o', 'v'), 0u, HBS_MP4_FOURCC('m', 'd', 'i', 'a'), HBS_MP4_FOURCC('m', 'i', 'n', 'f'),
-                              HBS_MP4_FOURCC('s', 't', 'b', 'l'), HBS_MP4_FOURCC('s', 't', 's', 'd'), 0u};
-    uint64_t pos[7], at = 0, end = n;
+    Mp4TrackPath path;
+    if (mp4_init_read_host(init, n, track_id, &trk, nullptr, nullptr, 0, &path) < 0) return HBS_E_ARG;
     Mp4Writer sw{nullptr, 0};
     mp4prot_sinf(sw, 0, *t);
     const uint64_t sinf_bytes = sw.n;
-    uint32_t size[7];
-    for (int i = 0; i < 7; ++i) {
-        Mp4Box b;
-        if (!mp4prot_child(init, at, end, path[i], trk.hvcc_off, pos[i], b)) return HBS_E_ARG;
-        if (i == 1 && b.type != HBS_MP4_FOURCC('t', 'r', 'a', 'k')) return HBS_E_ARG;
-        /* a size field of 0 ("to the end") or 1 (a 64-bit size) cannot grow in place */
-        if (b.head != 8u || rd_be32(init, pos[i]) != b.size) return HBS_E_ARG;
-        const uint64_t grown = b.size + sinf_bytes + (i == 0 ? pssh_total : 0);
+    uint32_t size[kPathBoxes];
+    for (int i = 0; i < kPathBoxes; ++i) {
+        const Mp4At& b = path.box[i];
+        if (!mp4_resizable(init, b)) return HBS_E_ARG;
+        const uint64_t grown = b.size + sinf_bytes + (i == kPathMoov ? pssh_total : 0);
         if (grown > 0xFFFFFFFFull) return HBS_E_ARG;
         size[i] = (uint32_t)grown;
-        at = pos[i] + 8u + (i == 5 ? 8u : 0u);            /* (the stsd's entries lie behind version, flags and the count) */
-        end = pos[i] + b.size;
     }
-    const uint64_t entry_end = end, moov_end = pos[0] + (size[0] - sinf_bytes - pssh_total);
-    const uint32_t fourcc = rd_be32(init, pos[6] + 4);
+    const Mp4At& entry = path.box[kPathEntry];
+    const uint64_t entry_end = entry.end(), moov_end = path.box[kPathMoov].end();
+    const uint32_t fourcc = rd_be32(init, entry.pos + 4);
     if (fourcc != trk.entry) return HBS_E_ARG;
     const uint64_t need = n + sinf_bytes + pssh_total;
     if (need > cap) return (int64_t)need;
@@ -243,11 +224,8 @@ inline int64_t mp4_init_protect(const uint8_t* init, uint64_t n, uint32_t track_
     w.bytes(init + entry_end, moov_end - entry_end);
     for (uint64_t i = 0; i < n_pssh; ++i) w.bytes(pssh[i], pssh_bytes[i]);
     w.bytes(init + moov_end, n - moov_end);
-    for (int i = 0; i < 7; ++i) {
-        uint8_t* q = out + pos[i];
-        q[0] = (uint8_t)(size[i] >> 24); q[1] = (uint8_t)(size[i] >> 16); q[2] = (uint8_t)(size[i] >> 8); q[3] = (uint8_t)size[i];
-    }
-    memcpy(out + pos[6] + 4, "encv", 4);
+    for (int i = 0; i < kPathBoxes; ++i) wr_be32(out + path.box[i].pos, size[i]);
+    memcpy(out + entry.pos + 4, "encv", 4);
     return (int64_t)need;
 }
 

@@ -48,17 +48,6 @@ static_assert(kProtLanes == kPlanLanes, "the plan's workgroups share block_scan'
 
 enum : int { kErr = 0, kTotal = 1, kBadFrag = 2, kBadTab = 3, kInBytes = 4, kTooLarge = 5, kBig = 6 };      /* ctl words */
 
-/* the lowest non-zero word of flags[0, blocks), by one workgroup */
-__device__ __forceinline__ uint64_t min_nonzero_of(const unsigned long long* flags, uint64_t blocks)
-{
-    uint64_t m = 0;
-    for (uint64_t i = threadIdx.x; i < blocks; i += kPlanLanes) {
-        const uint64_t x = flags[i];
-        if (x && (!m || x < m)) m = x;
-    }
-    return block_min_nonzero(m);
-}
-
 /* ---- fragments --------------------------------------------------------------------------------------------------------- */
 
 /* MODE 0 count, 1 place, 2 d_frag_out */

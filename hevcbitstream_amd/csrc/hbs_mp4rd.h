@@ -1,10 +1,11 @@
 /*
  * hbs_mp4rd.h -- hbs_mp4_samples and hbs_mp4_init_read_host (include/hevcbitstream_amd.h): the rules that read fragmented MP4
- * (ISO/IEC 14496-12) as host/device inline functions -- mp4rd_box decodes a box header within its container, mp4rd_tfhd and
- * mp4rd_trun lay the optional fields out from the flags, mp4rd_moof walks one moof and hands out its trun records,
- * mp4rd_sample resolves an entry through the three levels of defaults, mp4rd_place checks a sample's offset and times; the
- * kernels of hbs_mp4rd.hip, the host checks and the tests all run them -- the init segment's reader (plain host code, no GPU),
- * and the host-visible launcher.  Everything above the launcher compiles with plain g++.
+ * (ISO/IEC 14496-12) as host/device inline functions -- mp4rd_tfhd and mp4rd_trun lay the optional fields out from the
+ * flags, mp4rd_moof walks one moof and hands out its trun records, mp4rd_sample resolves an entry through the three levels of
+ * defaults, mp4rd_place checks a sample's offset and times (the byte reads and the box rule are hbs_mp4box.h's); the kernels
+ * of hbs_mp4rd.hip, the host checks and the tests all run them -- the init segment's reader (plain host code, no GPU: over the
+ * walk of hbs_mp4box.h, mp4rd_find_track returns the track and its Mp4TrackPath, from which hbs_mp4stbl.h and hbs_mp4prot.h
+ * take their boxes), and the host-visible launcher.  Everything above the launcher compiles with plain g++.
  */
 #ifndef HBS_MP4RD_H
 #define HBS_MP4RD_H
@@ -21,45 +22,6 @@ constexpr uint64_t kRdBaseCap = (1ull << 62) + (1ull << 32);   /* a base_data_of
 constexpr uint64_t kRdLarge = 1ull << 63;            /* Mp4RdArgs.moof_size: the moof has a largesize (a size is 2^62 at most)   */
 constexpr uint32_t kRdHead = 1u << 30;               /* Mp4TrunRec.tr: the sizes' sum restarts at the trun's first sample      */
 constexpr uint32_t kRdMoofFirst = 1u << 31;          /* ... the durations' sum does: the moof's first sample                   */
-
-/* ---- bytes ------------------------------------------------------------------------------------------------------------- */
-
-/* the big-endian 32-bit word at p + at.  On the device p is 16-byte aligned and the word is put together from the one or two
- * aligned words that hold a byte of it: no load touches a 16-byte granule that holds no byte of the word.  On the host: four
- * byte loads, so that a sanitizer sees exactly the bytes that are read. */
-HBS_HD uint32_t rd_be32(const uint8_t* p, uint64_t at)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(p + (at & ~3ull));
-    const uint32_t sh = (uint32_t)(at & 3u);
-    const uint32_t lo = w[0], hi = sh ? w[1] : 0u;
-    return __builtin_bswap32(alignbyte(hi, lo, sh));
-#else
-    return ((uint32_t)p[at] << 24) | ((uint32_t)p[at + 1] << 16) | ((uint32_t)p[at + 2] << 8) | (uint32_t)p[at + 3];
-#endif
-}
-HBS_HD uint64_t rd_be64(const uint8_t* p, uint64_t at) { return ((uint64_t)rd_be32(p, at) << 32) | rd_be32(p, at + 4); }
-
-/* ---- boxes ------------------------------------------------------------------------------------------------------------- */
-
-struct Mp4Box { uint64_t size; uint32_t type, head; };      /* head: 8, or 16 with a largesize */
-
-/* the box at `at` in a container that ends at `end` (at < end <= the buffer's size); false: it breaks a size rule */
-HBS_HD bool mp4rd_box(const uint8_t* p, uint64_t at, uint64_t end, Mp4Box& b)
-{
-    const uint64_t left = end - at;
-    if (left < 8) return false;
-    const uint32_t s = rd_be32(p, at);
-    b.type = rd_be32(p, at + 4);
-    b.head = 8; b.size = s;
-    if (s == 1u) {
-        if (left < 16) return false;
-        b.size = rd_be64(p, at + 8); b.head = 16;
-        if (b.size < 16) return false;
-    } else if (s == 0u) b.size = left;
-    else if (s < 8u) return false;
-    return b.size <= left;
-}
 
 struct Mp4Tfhd { uint32_t flags, track_id, dur, size, sflags; uint64_t base_data_offset; };
 
@@ -289,20 +251,6 @@ inline bool mp4_read_params_ok(const hbs_mp4_read_params* p)
     return p && p->flags == 0u && p->reserved[0] == 0u && p->reserved[1] == 0u && p->reserved[2] == 0u;
 }
 
-/* the first child of type `type` among the boxes that tile p[at, end); 0: well-formed, none; < 0: a box of the container, in
- * front of that child or behind it, breaks a size rule */
-inline int mp4rd_child(const uint8_t* p, uint64_t at, uint64_t end, uint32_t type, uint64_t& pay, uint64_t& pend)
-{
-    int found = 0;
-    while (at < end) {
-        Mp4Box b;
-        if (!mp4rd_box(p, at, end, b)) return -1;
-        if (b.type == type && !found) { pay = at + b.head; pend = at + b.size; found = 1; }
-        at += b.size;
-    }
-    return found;
-}
-
 /* the parameter-set NALs of the hvcC payload p[at, end): their number, or -1; offsets and sizes while they fit cap */
 inline int64_t mp4rd_hvcc(const uint8_t* p, uint64_t at, uint64_t end, int32_t& length_size, uint64_t* nal_off, uint64_t* nal_bytes, uint64_t cap)
 {
@@ -326,83 +274,58 @@ inline int64_t mp4rd_hvcc(const uint8_t* p, uint64_t at, uint64_t end, int32_t& 
     return (int64_t)n;
 }
 
-/* one trak p[at, end): 1 a video track with an hvcC (out's track fields and the NALs filled; p[stbl_at, stbl_end) its stbl's
- * children), 0 not one, -1 malformed */
-inline int mp4rd_trak(const uint8_t* p, uint64_t at, uint64_t end, hbs_mp4_track* out, int64_t& n_nals, uint64_t* nal_off, uint64_t* nal_bytes,
-                      uint64_t cap, uint64_t& stbl_at, uint64_t& stbl_end)
+/* the trak path.box[kPathTrak]: 1 a video track with an hvcC (out's track fields and the NALs filled, path filled down to the
+ * first 'hvc1' or 'hev1' entry that holds an hvcC), 0 not one, -1 malformed */
+inline int mp4rd_trak(const uint8_t* p, Mp4TrackPath& path, hbs_mp4_track* out, int64_t& n_nals, uint64_t* nal_off, uint64_t* nal_bytes, uint64_t cap)
 {
-    uint64_t a, e;
-    int rc = mp4rd_child(p, at, end, HBS_MP4_FOURCC('t', 'k', 'h', 'd'), a, e);
-    if (rc <= 0) return -1;
-    if (e - a < 4) return -1;
-    const uint32_t tv = p[a];
-    if (tv > 1u || e - a < (tv ? 96u : 84u)) return -1;
-    out->track_id = rd_be32(p, a + (tv ? 20u : 12u));
-    out->width = rd_be32(p, a + (tv ? 88u : 76u)) >> 16; out->height = rd_be32(p, a + (tv ? 92u : 80u)) >> 16;
-    uint64_t ma, me;
-    rc = mp4rd_child(p, at, end, HBS_MP4_FOURCC('m', 'd', 'i', 'a'), ma, me);
-    if (rc <= 0) return -1;
-    rc = mp4rd_child(p, ma, me, HBS_MP4_FOURCC('m', 'd', 'h', 'd'), a, e);
-    if (rc <= 0 || e - a < 4) return -1;
-    const uint32_t mv = p[a];
-    if (mv > 1u || e - a < (mv ? 32u : 20u)) return -1;
-    out->timescale = rd_be32(p, a + (mv ? 20u : 12u));
-    const uint32_t path[3] = {HBS_MP4_FOURCC('m', 'i', 'n', 'f'), HBS_MP4_FOURCC('s', 't', 'b', 'l'), HBS_MP4_FOURCC('s', 't', 's', 'd')};
-    a = ma; e = me;
-    for (int i = 0; i < 3; ++i) {
-        uint64_t ca, ce;
-        rc = mp4rd_child(p, a, e, path[i], ca, ce);
-        if (rc < 0) return -1;
-        if (rc == 0) return i == 0 ? 0 : -1;                   /* (a trak without a minf is not ours; below it the boxes are required) */
-        if (i == 2) { stbl_at = a; stbl_end = e; }
-        a = ca; e = ce;
-    }
-    if (e - a < 8) return -1;
-    const uint32_t entries = rd_be32(p, a + 4);
-    a += 8;
-    for (uint32_t i = 0; i < entries && a < e; ++i) {
-        Mp4Box b;
-        if (!mp4rd_box(p, a, e, b)) return -1;
-        if (b.type == HBS_MP4_FOURCC('h', 'v', 'c', '1') || b.type == HBS_MP4_FOURCC('h', 'e', 'v', '1')) {
-            const uint64_t va = a + b.head, ve = a + b.size;
-            if (ve - va < 78) return -1;                      /* a VisualSampleEntry's fixed part */
-            uint64_t ha, he;
-            rc = mp4rd_child(p, va + 78, ve, HBS_MP4_FOURCC('h', 'v', 'c', 'C'), ha, he);
-            if (rc < 0) return -1;
-            if (rc > 0) {
-                out->entry = b.type; out->hvcc_off = ha; out->hvcc_bytes = he - ha;
-                n_nals = mp4rd_hvcc(p, ha, he, out->length_size, nal_off, nal_bytes, cap);
-                return n_nals < 0 ? -1 : 1;
-            }
-        }
-        a += b.size;
-    }
-    return 0;
+    const Mp4At& trak = path.box[kPathTrak];
+    Mp4Tkhd k;
+    if (!mp4_tkhd(p, trak.pay(), trak.end(), k)) return -1;
+    out->track_id = k.track_id; out->width = k.width; out->height = k.height;
+    const int rc = mp4_track_descend(p, path, true, [&](uint32_t type, const Mp4At& e) -> int {
+        if (type != HBS_MP4_FOURCC('h', 'v', 'c', '1') && type != HBS_MP4_FOURCC('h', 'e', 'v', '1')) return 0;
+        if (e.size - e.head < 78) return -1;                   /* a VisualSampleEntry's fixed part */
+        Mp4At h;
+        const int c = mp4_child(p, e.pay() + 78, e.end(), HBS_MP4_FOURCC('h', 'v', 'c', 'C'), h);
+        if (c <= 0) return c;
+        out->entry = type; out->hvcc_off = h.pay(); out->hvcc_bytes = h.size - h.head;
+        n_nals = mp4rd_hvcc(p, h.pay(), h.end(), out->length_size, nal_off, nal_bytes, cap);
+        return n_nals < 0 ? -1 : 1;
+    });
+    if (rc < 0) return -1;
+    Mp4At m, mdia = path.box[kPathMdia];                       /* (the mdhd is required of every trak, one without a minf included) */
+    if (mp4_child(p, mdia.pay(), mdia.end(), HBS_MP4_FOURCC('m', 'd', 'h', 'd'), m) <= 0 || m.size - m.head < 4) return -1;
+    const uint32_t mv = p[m.pay()];
+    if (mv > 1u || m.size - m.head < (mv ? 32u : 20u)) return -1;
+    out->timescale = rd_be32(p, m.pay() + (mv ? 20u : 12u));
+    return rc;
 }
 
-/* The walk that hbs_mp4_init_read_host and hbs_mp4_stbl_find_host share: the moov of seg[0, n) (its children: seg[ma, me)) and
- * in it the trak asked for -- track_id, or with 0 the first that is a video track with an hvcC; the others are stepped over,
- * but must be well-formed.  t and the NALs as mp4rd_trak leaves them; seg[sa, se) the children of the track's stbl. */
-inline bool mp4rd_find_track(const uint8_t* seg, uint64_t n, uint32_t track_id, hbs_mp4_track& t, int64_t& n_nals, uint64_t* nal_off,
-                             uint64_t* nal_bytes, uint64_t cap, uint64_t& ma, uint64_t& me, uint64_t& sa, uint64_t& se)
+/* The walk that the five init-segment calls share: the moov of seg[0, n) and in it the trak asked for -- track_id, or with 0
+ * the first that is a video track with an hvcC; the others are stepped over, but must be well-formed.  t and the NALs as
+ * mp4rd_trak leaves them; path: the seven boxes from the moov to the track's sample entry. */
+inline bool mp4rd_find_track(const uint8_t* seg, uint64_t n, uint32_t track_id, hbs_mp4_track& t, Mp4TrackPath& path, int64_t& n_nals,
+                             uint64_t* nal_off, uint64_t* nal_bytes, uint64_t cap)
 {
-    if (mp4rd_child(seg, 0, n, HBS_MP4_FOURCC('m', 'o', 'o', 'v'), ma, me) <= 0) return false;
+    Mp4TrackPath k;                                            /* the trak that is looked at */
+    if (mp4_child(seg, 0, n, HBS_MP4_FOURCC('m', 'o', 'o', 'v'), k.box[kPathMoov]) <= 0) return false;
+    const Mp4At moov = k.box[kPathMoov];
     n_nals = -1;
     bool found = false;
-    for (uint64_t at = ma; at < me;) {
+    for (uint64_t at = moov.pay(); at < moov.end();) {
         Mp4Box b;
-        if (!mp4rd_box(seg, at, me, b)) return false;
+        if (!mp4rd_box(seg, at, moov.end(), b)) return false;
         if (b.type == HBS_MP4_FOURCC('t', 'r', 'a', 'k') && !found) {
-            hbs_mp4_track k;
-            memset(&k, 0, sizeof(k));
-            /* the track asked for must be a video track with an hvcC; with track_id 0 the others are stepped over */
-            int64_t kn = -1;
-            uint64_t ka = 0, ke = 0;
-            const int rc = mp4rd_trak(seg, at + b.head, at + b.size, &k, kn, nal_off, nal_bytes, cap, ka, ke);
+            hbs_mp4_track c;
+            memset(&c, 0, sizeof(c));
+            int64_t cn = -1;
+            k.box[kPathTrak] = Mp4At{at, b.size, b.head};
+            const int rc = mp4rd_trak(seg, k, &c, cn, nal_off, nal_bytes, cap);
             if (rc < 0) return false;
-            if (track_id == 0u ? rc == 1 : k.track_id == track_id) {
+            /* the track asked for must be a video track with an hvcC; with track_id 0 the others are stepped over */
+            if (track_id == 0u ? rc == 1 : c.track_id == track_id) {
                 if (rc != 1) return false;
-                found = true; n_nals = kn; t = k; sa = ka; se = ke;
+                found = true; n_nals = cn; t = c; path = k;
             }
         }
         at += b.size;
@@ -410,20 +333,22 @@ inline bool mp4rd_find_track(const uint8_t* seg, uint64_t n, uint32_t track_id, 
     return found;
 }
 
+/* hbs_mp4_init_read_host; path_out (nullable): the seven boxes down to the track's sample entry, for mp4_init_protect */
 inline int64_t mp4_init_read_host(const uint8_t* seg, uint64_t n, uint32_t track_id, hbs_mp4_track* out, uint64_t* nal_off, uint64_t* nal_bytes,
-                                  uint64_t cap)
+                                  uint64_t cap, Mp4TrackPath* path_out = nullptr)
 {
     if (!seg || !out || n > kRdMaxIn || (cap && (!nal_off || !nal_bytes))) return HBS_E_ARG;
-    uint64_t ma, me, sa, se;
     hbs_mp4_track t;
+    Mp4TrackPath path;
     int64_t n_nals = -1;
-    if (!mp4rd_find_track(seg, n, track_id, t, n_nals, nal_off, nal_bytes, cap, ma, me, sa, se)) return HBS_E_ARG;
-    uint64_t xa, xe;
-    if (mp4rd_child(seg, ma, me, HBS_MP4_FOURCC('m', 'v', 'e', 'x'), xa, xe) <= 0) return HBS_E_ARG;
+    if (!mp4rd_find_track(seg, n, track_id, t, path, n_nals, nal_off, nal_bytes, cap)) return HBS_E_ARG;
+    const Mp4At& moov = path.box[kPathMoov];
+    Mp4At x;
+    if (mp4_child(seg, moov.pay(), moov.end(), HBS_MP4_FOURCC('m', 'v', 'e', 'x'), x) <= 0) return HBS_E_ARG;
     bool have_trex = false;
-    for (uint64_t at = xa; at < xe;) {
+    for (uint64_t at = x.pay(); at < x.end();) {
         Mp4Box b;
-        if (!mp4rd_box(seg, at, xe, b)) return HBS_E_ARG;
+        if (!mp4rd_box(seg, at, x.end(), b)) return HBS_E_ARG;
         if (b.type == HBS_MP4_FOURCC('t', 'r', 'e', 'x') && !have_trex) {
             const uint64_t a = at + b.head;
             if (b.size - b.head < 24) return HBS_E_ARG;
@@ -437,6 +362,7 @@ inline int64_t mp4_init_read_host(const uint8_t* seg, uint64_t n, uint32_t track
     if (!have_trex) return HBS_E_ARG;
     t.n_nals = (uint32_t)n_nals;
     *out = t;
+    if (path_out) *path_out = path;
     return n_nals;
 }
 

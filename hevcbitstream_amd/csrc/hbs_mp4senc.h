@@ -3,10 +3,11 @@
  * sample auxiliary information of protected fMP4 fragments back (ISO/IEC 23001-7 senc; 14496-12 saiz as a hint), as host/device
  * inline functions -- mp4senc_find is what one lane does for a fragment (the traf as mp4rd_moof chooses it, its senc, its saiz),
  * mp4senc_header the senc's header, mp4senc_record one sample's record in the serial walk, mp4senc_hint_ok the check of a
- * position that saiz proposes, mp4senc_entry / mp4senc_clear_* / mp4senc_flat_* the entries, mp4senc_numbering_ok the numbering;
- * the kernels of hbs_mp4senc.hip, the host loop below (mp4_senc_samples_host: what tests single-step) and the tests all run them
- * -- the init segment's un-protector (mp4_init_unprotect: plain host code, no GPU), and the host-visible launcher.  Everything
- * above the launcher compiles with plain g++.
+ * position that saiz proposes, mp4senc_entry / mp4senc_clear_* / mp4senc_flat_* the entries (the numbering rule is
+ * mp4prot_numbering_ok of hbs_mp4prot.h); the kernels of hbs_mp4senc.hip, the host loop below (mp4_senc_samples_host: what tests
+ * single-step) and the tests all run them -- the init segment's un-protector (mp4_init_unprotect: plain host code, no GPU; its
+ * walk is hbs_mp4box.h's with mp4senc_entry_ok as the test of a stsd entry, and the reader of hbs_mp4rd.h judges what it
+ * rebuilt), and the host-visible launcher.  Everything above the launcher compiles with plain g++.
  */
 #ifndef HBS_MP4SENC_H
 #define HBS_MP4SENC_H
@@ -37,19 +38,6 @@ struct SencFind {
     uint32_t pad;
 };
 
-/* the big-endian 16-bit value at p + at; on the device no load touches a granule that holds neither byte (rd_be32's way) */
-HBS_HD uint32_t rd_be16(const uint8_t* p, uint64_t at)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(p + (at & ~3ull));
-    const uint32_t sh = (uint32_t)(at & 3u);
-    const uint32_t lo = w[0], hi = sh == 3u ? w[1] : 0u;
-    return __builtin_bswap32(alignbyte(hi, lo, sh)) >> 16;
-#else
-    return ((uint32_t)p[at] << 8) | (uint32_t)p[at + 1];
-#endif
-}
-
 HBS_HD bool mp4_senc_params_ok(const hbs_mp4_senc_params* p)
 {
     if (!p || !mp4prot_iv_size_ok(p->iv_size) || (p->flags & ~HBS_SENC_CLEAR_IF_ABSENT) != 0u) return false;
@@ -58,12 +46,6 @@ HBS_HD bool mp4_senc_params_ok(const hbs_mp4_senc_params* p)
 }
 
 /* ---- the rule ------------------------------------------------------------------------------------------------------------ */
-
-/* the numbering rule is hbs_mp4_protect's */
-HBS_HD bool mp4senc_numbering_ok(uint64_t rel, uint64_t below, uint64_t S, uint64_t n_samples, bool last)
-{
-    return mp4prot_numbering_ok(rel, below, S, n_samples, last);
-}
 
 /* the senc whose payload (behind the box header) is p[pay, pay + len), in a traf of S samples: version 0, flags 0 or 2,
  * sample_count S */
@@ -225,7 +207,7 @@ inline void mp4_senc_samples_host(const uint8_t* in, uint64_t n, const hbs_mp4_f
     uint64_t below = 0, stop = 0;                        /* stop: 1 + the lowest fragment that find or the numbering refuses */
     for (uint64_t r = 0; r < R; ++r) {
         const bool ok = mp4senc_find(in, n, frag[r], prm.track_id, V, size != nullptr, (prm.flags & HBS_SENC_CLEAR_IF_ABSENT) != 0u, find[r]);
-        if ((!ok || !mp4senc_numbering_ok(frag[r].first_au - frag[0].first_au, below, frag[r].samples, N, r + 1 == R)) && !stop) stop = r + 1;
+        if ((!ok || !mp4prot_numbering_ok(frag[r].first_au - frag[0].first_au, below, frag[r].samples, N, r + 1 == R)) && !stop) stop = r + 1;
         first[r] = below;
         below += frag[r].samples;
     }
@@ -292,16 +274,16 @@ struct SencEntry { uint64_t sinf_at, sinf_bytes; uint32_t format; hbs_mp4_tenc t
  * isProtected 1 and an IV rule that hbs_mp4_tenc can state */
 inline bool mp4senc_sinf(const uint8_t* p, uint64_t at, uint64_t end, SencEntry& e)
 {
-    uint64_t a, z;
+    Mp4At b, schi;
     memset(&e.t, 0, sizeof(e.t));
-    if (mp4rd_child(p, at, end, HBS_MP4_FOURCC('f', 'r', 'm', 'a'), a, z) <= 0 || z - a < 4) return false;
-    e.format = rd_be32(p, a);
+    if (mp4_child(p, at, end, HBS_MP4_FOURCC('f', 'r', 'm', 'a'), b) <= 0 || b.size - b.head < 4) return false;
+    e.format = rd_be32(p, b.pay());
     if (e.format != HBS_MP4_FOURCC('h', 'v', 'c', '1') && e.format != HBS_MP4_FOURCC('h', 'e', 'v', '1')) return false;
-    if (mp4rd_child(p, at, end, HBS_MP4_FOURCC('s', 'c', 'h', 'm'), a, z) <= 0 || z - a < 8) return false;
-    e.t.scheme = rd_be32(p, a + 4);
-    uint64_t sa, sz;
-    if (mp4rd_child(p, at, end, HBS_MP4_FOURCC('s', 'c', 'h', 'i'), sa, sz) <= 0) return false;
-    if (mp4rd_child(p, sa, sz, HBS_MP4_FOURCC('t', 'e', 'n', 'c'), a, z) <= 0 || z - a < 24) return false;
+    if (mp4_child(p, at, end, HBS_MP4_FOURCC('s', 'c', 'h', 'm'), b) <= 0 || b.size - b.head < 8) return false;
+    e.t.scheme = rd_be32(p, b.pay() + 4);
+    if (mp4_child(p, at, end, HBS_MP4_FOURCC('s', 'c', 'h', 'i'), schi) <= 0) return false;
+    if (mp4_child(p, schi.pay(), schi.end(), HBS_MP4_FOURCC('t', 'e', 'n', 'c'), b) <= 0 || b.size - b.head < 24) return false;
+    const uint64_t a = b.pay(), z = b.end();
     const uint32_t version = p[a];
     if (version > 1u || p[a + 6] != 1u) return false;
     if (version == 1u) { e.t.crypt_byte_block = p[a + 5] >> 4; e.t.skip_byte_block = p[a + 5] & 15u; }
@@ -316,11 +298,25 @@ inline bool mp4senc_sinf(const uint8_t* p, uint64_t at, uint64_t end, SencEntry&
     return mp4_tenc_ok(&e.t);
 }
 
-/* the first child of type `type` among the boxes of p[at, end) as mp4prot_child finds it, which must have an 8-byte header
- * whose size field is the box's size (not 0, not a 64-bit size): one of the seven boxes whose size is reduced */
-inline bool mp4senc_step(const uint8_t* p, uint64_t at, uint64_t end, uint32_t type, uint64_t& pos, Mp4Box& b)
+/* the test of a stsd entry: a resizable 'encv' that holds an hvcC and a sinf that mp4senc_sinf accepts (se: what it said) */
+inline bool mp4senc_entry_ok(const uint8_t* p, uint32_t type, const Mp4At& e, SencEntry& se)
 {
-    return mp4prot_child(p, at, end, type, 0, pos, b) && b.head == 8u && rd_be32(p, pos) == b.size;
+    if (type != HBS_MP4_FOURCC('e', 'n', 'c', 'v') || !mp4_resizable(p, e) || e.size - e.head < 78) return false;
+    const uint64_t ca = e.pay() + 78u, ce = e.end();
+    Mp4At h, s;
+    if (mp4_child(p, ca, ce, HBS_MP4_FOURCC('h', 'v', 'c', 'C'), h) <= 0 || mp4_child(p, ca, ce, HBS_MP4_FOURCC('s', 'i', 'n', 'f'), s) <= 0) return false;
+    if (!mp4senc_sinf(p, s.pay(), s.end(), se)) return false;
+    se.sinf_at = s.pos; se.sinf_bytes = s.size;
+    return true;
+}
+
+/* k.box[kPathTrak] is a protected video track whose boxes can shrink in place (k: its path); nothing behind them is looked at */
+inline bool mp4senc_track(const uint8_t* p, Mp4TrackPath& k, SencEntry& entry)
+{
+    const auto test = [&](uint32_t type, const Mp4At& e) -> int { return mp4senc_entry_ok(p, type, e, entry) ? 1 : 0; };
+    if (mp4_track_descend(p, k, false, test) <= 0) return false;
+    for (int i = kPathMdia; i <= kPathStsd; ++i) if (!mp4_resizable(p, k.box[i])) return false;
+    return true;
 }
 
 /* hbs_mp4_init_unprotect_host */
@@ -328,97 +324,59 @@ inline int64_t mp4_init_unprotect(const uint8_t* init, uint64_t n, uint32_t trac
                                   uint64_t* pssh_off, uint64_t* pssh_bytes, uint64_t pssh_cap, uint64_t* n_pssh_out, uint8_t* out, uint64_t cap)
 {
     if (!init || !t_out || n > kRdMaxIn || (cap && !out) || (pssh_cap && (!pssh_off || !pssh_bytes))) return HBS_E_ARG;
-    uint64_t pos[7];
-    uint32_t size[7];
-    Mp4Box b;
-    if (!mp4senc_step(init, 0, n, HBS_MP4_FOURCC('m', 'o', 'o', 'v'), pos[0], b)) return HBS_E_ARG;
-    size[0] = (uint32_t)b.size;
-    const uint64_t ma = pos[0] + 8u, me = pos[0] + b.size;
+    /* 1. the moov's children: the pssh boxes leave, and each trak with a 32-bit size is tried until one is found */
+    Mp4TrackPath path, k;
+    if (mp4_child(init, 0, n, HBS_MP4_FOURCC('m', 'o', 'o', 'v'), k.box[kPathMoov]) <= 0 || !mp4_resizable(init, k.box[kPathMoov])) return HBS_E_ARG;
+    const Mp4At moov = k.box[kPathMoov];
     struct Cut { uint64_t at, bytes; };
     std::vector<Cut> cuts;                               /* what leaves the segment, in the order it lies there */
     uint64_t n_pssh = 0, pssh_total = 0;
     bool found = false;
-    SencEntry entry;
     uint32_t found_id = 0;
-    for (uint64_t at = ma; at < me;) {
-        if (!mp4rd_box(init, at, me, b)) return HBS_E_ARG;
+    SencEntry entry;
+    for (uint64_t at = moov.pay(); at < moov.end();) {
+        Mp4Box b;
+        if (!mp4rd_box(init, at, moov.end(), b)) return HBS_E_ARG;
+        k.box[kPathTrak] = Mp4At{at, b.size, b.head};
         if (b.type == HBS_MP4_FOURCC('p', 's', 's', 'h')) {
             cuts.push_back(Cut{at, b.size});
             pssh_total += b.size; n_pssh += 1;
-        } else if (b.type == HBS_MP4_FOURCC('t', 'r', 'a', 'k') && !found && b.head == 8u && rd_be32(init, at) == b.size) {
-            /* tkhd as mp4rd_trak reads it; then mdia, minf, stbl, stsd, each the first of its type */
-            const uint64_t ta = at + 8u, te = at + b.size;
-            uint64_t a, z;
-            if (mp4rd_child(init, ta, te, HBS_MP4_FOURCC('t', 'k', 'h', 'd'), a, z) <= 0 || z - a < 4) return HBS_E_ARG;
-            const uint32_t tv = init[a];
-            if (tv > 1u || z - a < (tv ? 96u : 84u)) return HBS_E_ARG;
-            const uint32_t id = rd_be32(init, a + (tv ? 20u : 12u));
-            if (track_id == 0u || id == track_id) {
-                const uint32_t path[4] = {HBS_MP4_FOURCC('m', 'd', 'i', 'a'), HBS_MP4_FOURCC('m', 'i', 'n', 'f'), HBS_MP4_FOURCC('s', 't', 'b', 'l'),
-                                          HBS_MP4_FOURCC('s', 't', 's', 'd')};
-                uint64_t q[7], lo = ta, hi = te;
-                uint32_t sz[7];
-                q[1] = at; sz[1] = (uint32_t)b.size;
-                bool ok = true;
-                for (int i = 0; i < 4 && ok; ++i) {
-                    Mp4Box k;
-                    ok = mp4senc_step(init, lo, hi, path[i], q[2 + i], k);
-                    if (ok) { sz[2 + i] = (uint32_t)k.size; lo = q[2 + i] + 8u; hi = q[2 + i] + k.size; }
-                }
-                if (ok && hi - lo >= 8) {
-                    const uint32_t entries = rd_be32(init, lo + 4);
-                    uint64_t e = lo + 8u;
-                    for (uint32_t i = 0; i < entries && e < hi && !found; ++i) {
-                        Mp4Box k;
-                        if (!mp4rd_box(init, e, hi, k)) break;
-                        if (k.type == HBS_MP4_FOURCC('e', 'n', 'c', 'v') && k.head == 8u && rd_be32(init, e) == k.size && k.size - 8u >= 78) {
-                            const uint64_t ca = e + 8u + 78u, ce = e + k.size;
-                            uint64_t ha, he;
-                            Mp4Box s;
-                            uint64_t sp;
-                            if (mp4rd_child(init, ca, ce, HBS_MP4_FOURCC('h', 'v', 'c', 'C'), ha, he) > 0 &&
-                                mp4prot_child(init, ca, ce, HBS_MP4_FOURCC('s', 'i', 'n', 'f'), 0, sp, s) &&
-                                mp4senc_sinf(init, sp + s.head, sp + s.size, entry)) {
-                                found = true; found_id = id;
-                                entry.sinf_at = sp; entry.sinf_bytes = s.size;
-                                q[6] = e; sz[6] = (uint32_t)k.size;
-                                for (int j = 1; j < 7; ++j) { pos[j] = q[j]; size[j] = sz[j]; }
-                                cuts.push_back(Cut{sp, s.size});
-                            }
-                        }
-                        e += k.size;
-                    }
-                }
+        } else if (b.type == HBS_MP4_FOURCC('t', 'r', 'a', 'k') && !found && mp4_resizable(init, k.box[kPathTrak])) {
+            Mp4Tkhd h;
+            if (!mp4_tkhd(init, at + b.head, at + b.size, h)) return HBS_E_ARG;
+            if ((track_id == 0u || h.track_id == track_id) && mp4senc_track(init, k, entry)) {
+                found = true; found_id = h.track_id; path = k;
+                cuts.push_back(Cut{entry.sinf_at, entry.sinf_bytes});
             }
         }
         at += b.size;
     }
     if (!found) return HBS_E_ARG;
+    /* 2. the clear segment, made whole: the cuts closed, the seven sizes reduced, the entry named as the frma says */
     const uint64_t need = n - entry.sinf_bytes - pssh_total;
-    /* the clear segment, made whole so that hbs_mp4_init_read_host can be asked whether it accepts it */
     std::vector<uint8_t> seg;
     seg.reserve(need);
     uint64_t from = 0;
     for (const Cut& c : cuts) { seg.insert(seg.end(), init + from, init + c.at); from = c.at + c.bytes; }
     seg.insert(seg.end(), init + from, init + n);
-    for (int i = 0; i < 7; ++i) {
+    for (int i = 0; i < kPathBoxes; ++i) {
         uint64_t shift = 0;                              /* what was cut in front of the box */
-        for (const Cut& c : cuts) if (c.at < pos[i]) shift += c.bytes;
-        const uint32_t v = size[i] - (uint32_t)entry.sinf_bytes - (i == 0 ? (uint32_t)pssh_total : 0u);
-        uint8_t* q = seg.data() + (pos[i] - shift);
-        q[0] = (uint8_t)(v >> 24); q[1] = (uint8_t)(v >> 16); q[2] = (uint8_t)(v >> 8); q[3] = (uint8_t)v;
-        if (i == 6) { q[4] = (uint8_t)(entry.format >> 24); q[5] = (uint8_t)(entry.format >> 16); q[6] = (uint8_t)(entry.format >> 8); q[7] = (uint8_t)entry.format; }
+        for (const Cut& c : cuts) if (c.at < path.box[i].pos) shift += c.bytes;
+        uint8_t* q = seg.data() + (path.box[i].pos - shift);
+        wr_be32(q, (uint32_t)path.box[i].size - (uint32_t)entry.sinf_bytes - (i == kPathMoov ? (uint32_t)pssh_total : 0u));
+        if (i == kPathEntry) wr_be32(q + 4, entry.format);
     }
+    /* 3. the reader's verdict on it */
     hbs_mp4_track trk;
     if (mp4_init_read_host(seg.data(), need, found_id, &trk, nullptr, nullptr, 0) < 0 || trk.entry != entry.format) return HBS_E_ARG;
     *t_out = entry.t;
     if (format_out) *format_out = entry.format;
     if (n_pssh_out) *n_pssh_out = n_pssh;
-    uint64_t k = 0;
+    uint64_t j = 0;
     for (const Cut& c : cuts) {
         if (c.at == entry.sinf_at) continue;
-        if (k < pssh_cap) { pssh_off[k] = c.at; pssh_bytes[k] = c.bytes; }
-        k += 1;
+        if (j < pssh_cap) { pssh_off[j] = c.at; pssh_bytes[j] = c.bytes; }
+        j += 1;
     }
     if (need <= cap) memcpy(out, seg.data(), need);
     return (int64_t)need;

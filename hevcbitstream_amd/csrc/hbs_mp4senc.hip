@@ -47,16 +47,6 @@ static_assert(kSencLanes == kPlanLanes, "the plan's workgroups share block_scan'
  * fragment, the bad sample; the fragments whose senc was read */
 enum : int { kErr = 0, kSkip = 1, kCode = 2, kTotal = 3, kBadFrag = 4, kBadSamp = 5, kSencRead = 6 };
 
-__device__ __forceinline__ uint64_t min_nonzero_of(const unsigned long long* flags, uint64_t blocks)
-{
-    uint64_t m = 0;
-    for (uint64_t i = threadIdx.x; i < blocks; i += kPlanLanes) {
-        const uint64_t x = flags[i];
-        if (x && (!m || x < m)) m = x;
-    }
-    return block_min_nonzero(m);
-}
-
 /* ---- fragments --------------------------------------------------------------------------------------------------------- */
 
 /* MODE 0 find, 1 number */
@@ -95,7 +85,7 @@ __global__ __launch_bounds__(kST) void k_senc_frag(Mp4SencArgs a)
     if (in) {
         const uint64_t below = a.part_f[(uint64_t)blockIdx.x * 8] + ex;
         const bool last = r + 1 == a.n_frags;
-        if (!mp4senc_numbering_ok(f.first_au - a.frag[0].first_au, below, f.samples, a.n_samples, last)) bad = r + 1;
+        if (!mp4prot_numbering_ok(f.first_au - a.frag[0].first_au, below, f.samples, a.n_samples, last)) bad = r + 1;
         a.frag_first[r] = below;
         if (last) a.frag_first[r + 1] = a.n_samples;
     }

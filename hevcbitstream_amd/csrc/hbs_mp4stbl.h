@@ -4,8 +4,8 @@
  * boxes' fixed parts and checks versions and lengths, stbl_stsc_entry / stbl_stss_entry check one entry against its
  * neighbour, stbl_run_samples / stbl_join keep the sums exact where counts of 2^32 - 1 meet, stbl_place checks a sample's
  * offset and times; the kernels of hbs_mp4stbl.hip, the host checks and the tests all run them -- the box finder and the track
- * reader (plain host code, no GPU; their walk is mp4rd_find_track of hbs_mp4rd.h), and the host-visible launcher.  Everything
- * above the launcher compiles with plain g++.
+ * reader (plain host code, no GPU; their walk is mp4rd_find_track of hbs_mp4rd.h, whose Mp4TrackPath names the stbl), and the
+ * host-visible launcher.  Everything above the launcher compiles with plain g++.
  */
 #ifndef HBS_MP4STBL_H
 #define HBS_MP4STBL_H
@@ -134,10 +134,10 @@ inline int64_t mp4_track_read_host(const uint8_t* seg, uint64_t n, uint32_t trac
                                    uint64_t cap)
 {
     if (!seg || !out || n > kRdMaxIn || (cap && (!nal_off || !nal_bytes))) return HBS_E_ARG;
-    uint64_t ma, me, sa = 0, se = 0;
     hbs_mp4_track t;
+    Mp4TrackPath path;
     int64_t n_nals = -1;
-    if (!mp4rd_find_track(seg, n, track_id, t, n_nals, nal_off, nal_bytes, cap, ma, me, sa, se)) return HBS_E_ARG;
+    if (!mp4rd_find_track(seg, n, track_id, t, path, n_nals, nal_off, nal_bytes, cap)) return HBS_E_ARG;
     t.n_nals = (uint32_t)n_nals;
     *out = t;
     return n_nals;
@@ -146,14 +146,14 @@ inline int64_t mp4_track_read_host(const uint8_t* seg, uint64_t n, uint32_t trac
 inline int mp4_stbl_find_host(const uint8_t* seg, uint64_t n, uint64_t base, uint32_t track_id, hbs_mp4_stbl* out)
 {
     if (!seg || !out || n > kRdMaxIn) return HBS_E_ARG;
-    uint64_t ma, me, sa = 0, se = 0;
     hbs_mp4_track t;
+    Mp4TrackPath path;
     int64_t n_nals = -1;
-    if (!mp4rd_find_track(seg, n, track_id, t, n_nals, nullptr, nullptr, 0, ma, me, sa, se)) return HBS_E_ARG;
+    if (!mp4rd_find_track(seg, n, track_id, t, path, n_nals, nullptr, nullptr, 0)) return HBS_E_ARG;
     hbs_mp4_stbl r;
     memset(&r, 0, sizeof(r));
     bool stz2 = false, co64 = false;
-    for (uint64_t at = sa; at < se;) {                         /* (the chain held in mp4rd_trak) */
+    for (uint64_t at = path.box[kPathStbl].pay(), se = path.box[kPathStbl].end(); at < se;) {     /* (the chain held in the walk) */
         Mp4Box b;
         if (!mp4rd_box(seg, at, se, b)) return HBS_E_ARG;
         hbs_mp4_box_ref* ref = nullptr;

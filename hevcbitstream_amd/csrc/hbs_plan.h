@@ -1,7 +1,8 @@
 /* hbs_plan.h -- device-only: the scans of a "count, scan, place" plan (hbs_filter.hip, hbs_lenpref.hip, hbs_ts.hip,
- * hbs_tsmux.hip, hbs_rtp.hip, hbs_rtpun.hip, hbs_rtpord.hip, hbs_auins.hip, hbs_mp4.hip, hbs_mp4rd.hip, hbs_mp4prot.hip): over the lanes of a workgroup the exclusive sums (block_scan), the
- * exclusive maxima (block_excl_max) and the sums that restart at marked lanes (block_seg_excl, seg_scan_parts).  A count kernel leaves 8 words a workgroup -- N sums, then a word that says what was
- * wrong -- and one workgroup of kPlanLanes lanes turns the sums into offsets (scan_parts). */
+ * hbs_tsmux.hip, hbs_rtp.hip, hbs_rtpun.hip, hbs_rtpord.hip, hbs_auins.hip, hbs_autimes.hip, hbs_cenc.hip, hbs_cbcs.hip, hbs_mp4.hip, hbs_mp4rd.hip, hbs_mp4stbl.hip, hbs_mp4stblw.hip,
+ * hbs_mp4prot.hip, hbs_mp4senc.hip): over the lanes of a workgroup the exclusive sums (block_scan), the exclusive maxima (block_excl_max), the lowest error mark (block_min_nonzero, and min_nonzero_of
+ * over the marks that the workgroups left) and the sums that restart at marked lanes (block_seg_excl, seg_scan_parts).  A count kernel leaves 8 words a workgroup -- N sums, then a word that says what
+ * was wrong -- and one workgroup of kPlanLanes lanes turns the sums into offsets (scan_parts). */
 #ifndef HBS_PLAN_H
 #define HBS_PLAN_H
 
@@ -92,6 +93,18 @@ __device__ __forceinline__ uint64_t block_min_nonzero(uint64_t x)
     const uint64_t m = s_min;
     __syncthreads();
     return m == ~0ull ? 0 : m;
+}
+
+/* one workgroup of kPlanLanes: the lowest non-zero of the words flags[STRIDE i], i < blocks (0: all are zero) */
+template <int STRIDE = 1>
+__device__ __forceinline__ uint64_t min_nonzero_of(const unsigned long long* flags, uint64_t blocks)
+{
+    uint64_t m = 0;
+    for (uint64_t i = threadIdx.x; i < blocks; i += kPlanLanes) {
+        const uint64_t x = flags[i * STRIDE];
+        if (x && (!m || x < m)) m = x;
+    }
+    return block_min_nonzero(m);
 }
 
 /* one workgroup of kPlanLanes: the per-workgroup sums part[8 i + 0..N-1] become their exclusive prefix sums, carry their

@@ -629,7 +629,9 @@ int64_t hbs_mp4_init_host(const hbs_mp4_init_params* p, int flags,
  * hbs_mp4_init_read_host (plain C, no GPU): the counterpart of hbs_mp4_init_host.  It walks seg[0, n) by the box rule above:
  * moov; its trak boxes in order -- tkhd (version 0 or 1: track_id, width and height, the integer parts), mdia / mdhd (version
  * 0 or 1: timescale), mdia / minf / stbl / stsd, whose first 'hvc1' or 'hev1' entry that holds an hvcC is the one read --
- * and mvex / trex of that track (its three defaults).  track_id 0: the first trak with such an entry.  From the hvcC:
+ * and mvex / trex of that track (its three defaults).  The stsd's entries are taken one at a time, entry_count of them at
+ * the most, each held to the box rule when it is reached, and nothing behind the entry that is chosen is looked at.
+ * track_id 0: the first trak with such an entry.  From the hvcC:
  * length_size = (byte 21 & 3) + 1, and for every array in order every NAL's offset and size within seg.  Returns the number
  * of those NALs; nal_off / nal_bytes are written for the first `cap` of them (so call with cap 0 first, or with room for
  * out->n_nals).  HBS_E_ARG: a NULL seg or out, anything malformed or missing (a box that breaks the size rule, no moov, no such

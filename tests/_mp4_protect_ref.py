@@ -227,7 +227,10 @@ def init_protect(init, t, pssh=(), track_id=0):
         hvcc = RR.init_read(b, track_id)[0]["hvcc_off"]
         lo, hi, path = 0, len(b), []
         for depth in range(7):              # moov, trak, mdia, minf, stbl, stsd, the entry: the box that holds the hvcC
-            (kind, at, pay, end), = [x for x in RR.boxes(b, lo, hi) if x[1] <= hvcc < x[3]]
+            if depth == 6:                  # (like the reader, the walk looks at nothing behind the stsd entry that it takes)
+                kind, at, pay, end = next(x for x in RR.each_box(b, lo, hi) if x[1] <= hvcc < x[3])
+            else:
+                (kind, at, pay, end), = [x for x in RR.boxes(b, lo, hi) if x[1] <= hvcc < x[3]]
             if pay - at != 8 or u32(b, at) != end - at:
                 return E_ARG
             path.append((kind, at, end))

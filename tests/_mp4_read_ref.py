@@ -1,6 +1,7 @@
 """hbs_mp4_samples / hbs_mp4_init_read_host in plain Python, from ISO/IEC 14496-12 and the call's header comment and
 independent of the C rule functions (hbs_mp4rd.h): a reader that goes box by box with exact integers, a general fragment writer
 that uses every optional field the call honours, and a generator of random valid segments that knows what it wrote."""
+import itertools
 import struct
 
 import numpy as np
@@ -31,9 +32,9 @@ def be(b, at, n, signed=False):
     return int.from_bytes(b[at:at + n], "big", signed=signed)
 
 
-def boxes(b, lo, hi):
-    """the boxes that tile b[lo, hi): [(type, box begin, payload begin, end)]; Malformed when one breaks a size rule"""
-    found = []
+def each_box(b, lo, hi):
+    """the boxes that tile b[lo, hi), one at a time: (type, box begin, payload begin, end); Malformed when the one that is
+    reached breaks a size rule (what lies behind the last one taken is not looked at)"""
     while lo < hi:
         if hi - lo < 8:
             raise Malformed("header leaves the container")
@@ -50,9 +51,19 @@ def boxes(b, lo, hi):
             raise Malformed("size below 8")
         if size > hi - lo:
             raise Malformed("box leaves the container")
-        found.append((kind, lo, lo + head, lo + size))
+        yield kind, lo, lo + head, lo + size
         lo += size
-    return found
+
+
+def boxes(b, lo, hi):
+    """all the boxes that tile b[lo, hi): [(type, box begin, payload begin, end)]; Malformed when one breaks a size rule"""
+    return list(each_box(b, lo, hi))
+
+
+def stsd_entries(b, lo, hi, count):
+    """the sample entries of a stsd whose payload is b[lo, hi), one at a time and entry_count at the most: the caller stops at the
+    entry it chooses, and nothing behind that one is looked at"""
+    return itertools.islice(each_box(b, lo + 8, hi), count)
 
 
 def read_traf(b, p, e):
@@ -517,7 +528,7 @@ def init_read(b, track_id=0):
             if at[1] - at[0] < 8:
                 raise Malformed("stsd")
             count = be(b, at[0] + 4, 4)
-            for k2, _, sp, se in boxes(b, at[0] + 8, at[1])[:count]:
+            for k2, _, sp, se in stsd_entries(b, at[0], at[1], count):
                 if k2 in (b"hvc1", b"hev1"):
                     if se - sp < 78:
                         raise Malformed("sample entry")

@@ -7,7 +7,7 @@ import struct
 import numpy as np
 
 from tests import _mp4_ref as R
-from tests._mp4_read_ref import Malformed, be, boxes
+from tests._mp4_read_ref import Malformed, be, boxes, stsd_entries
 
 STBL = np.dtype([("stsz", "<u8", (2,)), ("stco", "<u8", (2,)), ("stsc", "<u8", (2,)), ("stts", "<u8", (2,)), ("ctts", "<u8", (2,)),
                  ("stss", "<u8", (2,)), ("flags", "<u4"), ("reserved0", "<u4"), ("file_bytes", "<u8"), ("reserved", "<u8", (2,))])
@@ -186,7 +186,7 @@ def walk(b, track_id=0):
             stsd = child(*stbl, b"stsd")
             if stsd is None or stsd[1] - stsd[0] < 8:
                 raise Malformed("stsd")
-            for k2, _, sp, se in boxes(b, stsd[0] + 8, stsd[1])[:be(b, stsd[0] + 4, 4)]:
+            for k2, _, sp, se in stsd_entries(b, stsd[0], stsd[1], be(b, stsd[0] + 4, 4)):
                 if k2 in (b"hvc1", b"hev1"):
                     if se - sp < 78:
                         raise Malformed("sample entry")

@@ -1,9 +1,11 @@
 """The host/device rules of hbs_mp4rd.h (mp4rd_box, mp4rd_moof, mp4rd_sample, mp4rd_place) and the init segment's reader under
 AddressSanitizer and UBSan, in a stand-alone program: a plain host loop over the rule functions -- the chain of top-level
 boxes, every moof, every sample -- on segments and init segments in exactly sized heap blocks: valid ones, their truncations
-at every length, and valid ones with single bytes of the size and flag fields altered.  The program prints what it accepted
-and a digest of every table; the box-by-box reader of tests/_mp4_read_ref.py must say the same of every block.  Nothing is
-loaded into python."""
+at every length, and valid ones with single bytes of the size and flag fields altered; and a two-track init segment, clear
+and protected, at every truncation through the reader, mp4_init_protect and mp4_init_unprotect (hbs_mp4prot.h,
+hbs_mp4senc.h), which share the reader's walk.  The program prints what it accepted and a digest of every table and every
+byte written; the box-by-box readers of tests/_mp4_read_ref.py, _mp4_protect_ref.py and _mp4_senc_ref.py must say the same
+of every block.  Nothing is loaded into python."""
 import os
 import shutil
 import struct
@@ -12,8 +14,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import _mp4_protect_ref as P
 from tests import _mp4_ref as R
 from tests import _mp4_read_ref as Q
+from tests import _mp4_senc_ref as S
+from tests.test_mp4_init_mutations import PSSH, TENC, two_tracks
 from tests.test_mp4_read_ref import NALS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +28,7 @@ PROGRAM = r"""
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "hbs_mp4rd.h"
+#include "hbs_mp4senc.h"
 
 static uint64_t h;
 static void mix(uint64_t v) { h = h * 1099511628211ull + v; }
@@ -109,6 +114,47 @@ static void init(const uint8_t* p, uint64_t n, uint32_t track)
     printf("ok %lld %llu\n", (long long)got, (unsigned long long)h);
 }
 
+static const uint8_t kTenc[64] = {@TENC@};
+static const uint8_t kPssh[] = {@PSSH@};
+
+/* the two rewriters: the size first, then into a heap block of exactly that size */
+static void protect(const uint8_t* p, uint64_t n, uint32_t track)
+{
+    hbs_mp4_tenc t;
+    memcpy(&t, kTenc, sizeof(t));
+    const uint8_t* boxes[1] = {kPssh};
+    const uint64_t sizes[1] = {sizeof(kPssh)};
+    const int64_t need = hbs::mp4_init_protect(p, n, track, &t, boxes, sizes, 1, nullptr, 0);
+    if (need < 0) { printf("refused\n"); return; }
+    uint8_t* out = (uint8_t*)malloc((size_t)need);
+    if (hbs::mp4_init_protect(p, n, track, &t, boxes, sizes, 1, out, (uint64_t)need) != need) { printf("the second call disagrees\n"); free(out); return; }
+    h = 0;
+    for (int64_t i = 0; i < need; ++i) mix(out[i]);
+    free(out);
+    printf("ok %lld %llu\n", (long long)need, (unsigned long long)h);
+}
+
+static void unprotect(const uint8_t* p, uint64_t n, uint32_t track)
+{
+    hbs_mp4_tenc t;
+    uint32_t format = 0;
+    uint64_t n_pssh = 0;
+    const int64_t need = hbs::mp4_init_unprotect(p, n, track, &t, &format, nullptr, nullptr, 0, &n_pssh, nullptr, 0);
+    if (need < 0) { printf("refused\n"); return; }
+    uint8_t* out = (uint8_t*)malloc((size_t)need);
+    uint64_t* off = (uint64_t*)malloc(n_pssh ? n_pssh * 8 : 1);
+    uint64_t* size = (uint64_t*)malloc(n_pssh ? n_pssh * 8 : 1);
+    const int64_t got = hbs::mp4_init_unprotect(p, n, track, &t, &format, off, size, n_pssh, &n_pssh, out, (uint64_t)need);
+    h = 0;
+    mix(format); mix(n_pssh);
+    for (uint64_t i = 0; i < n_pssh; ++i) { mix(off[i]); mix(size[i]); }
+    for (size_t i = 0; i < sizeof(t); ++i) mix(((const uint8_t*)&t)[i]);
+    for (int64_t i = 0; i < need; ++i) mix(out[i]);
+    free(out); free(off); free(size);
+    if (got != need) printf("the second call disagrees\n");
+    else printf("ok %lld %llu\n", (long long)need, (unsigned long long)h);
+}
+
 int main(int argc, char** argv)
 {
     FILE* f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
@@ -124,7 +170,9 @@ int main(int argc, char** argv)
             hbs::Mp4Trex x;
             x.track_id = head[1]; x.dur = head[2]; x.size = head[3]; x.flags = head[4];
             if (p || !n) samples(p, n, x);
-        } else init(p, n, head[1]);
+        } else if (head[0] == 1) init(p, n, head[1]);
+        else if (head[0] == 2) protect(p, n, head[1]);
+        else unprotect(p, n, head[1]);
         free(p);
     }
     fclose(f);
@@ -167,6 +215,19 @@ def want_init(buf, track):
     for o, n in nals:
         vals += [o, n]
     return "ok %d %d" % (len(nals), digest(vals))
+
+
+def want_protect(buf, track):
+    out = P.init_protect(buf, TENC, PSSH, track)
+    return "refused" if out == P.E_ARG else "ok %d %d" % (len(out), digest(out))
+
+
+def want_unprotect(buf, track):
+    got = S.init_unprotect(buf, track)
+    if got == S.E_ARG:
+        return "refused"
+    out, tenc, fmt, pssh = got
+    return "ok %d %d" % (len(out), digest([fmt, len(pssh)] + [v for pair in pssh for v in pair] + list(tenc.tobytes()) + list(out)))
 
 
 def field_bytes(buf):
@@ -215,6 +276,15 @@ def cases():
             for v in (0, 1, seg[at] ^ 1, 0xFF):
                 if v != seg[at]:
                     out.append((1, dict(track_id=0), seg[:at] + bytes([v]) + seg[at + 1:]))
+    # two traks, the one in front with an 'mp4a' entry: through the reader and the two rewriters, at every truncation; its
+    # protected form through the un-protector likewise; and the 'mp4a' entry shrunk to 40 bytes, which ends the stsd's walk
+    seg = two_tracks("mp4a", True)
+    prot = P.init_protect(seg, TENC, PSSH, 5)
+    at = seg.index(b"mp4a") - 4
+    for kind in (1, 2, 3):
+        out += [(kind, dict(track_id=track), seg[:n]) for track in (0, 5) for n in range(len(seg) + 1)]
+        out += [(kind, dict(track_id=track), seg[:at] + struct.pack(">I", 40) + seg[at + 4:]) for track in (0, 5, 9)]
+    out += [(3, dict(track_id=track), prot[:n]) for track in (0, 5) for n in range(len(prot) + 1)]
     return out
 
 
@@ -232,7 +302,7 @@ def test_rules_and_init_reader_under_sanitizers(tmp_path):
         pytest.skip("the compiler has no sanitizer runtime: " + (probed.stderr.strip().splitlines() or ["?"])[-1])
     # ... so that the real program failing to build is a failure, whatever the compiler says
     src = tmp_path / "mp4rd_host_asan.cpp"
-    src.write_text(PROGRAM)
+    src.write_text(PROGRAM.replace("@TENC@", ", ".join(str(x) for x in TENC.tobytes())).replace("@PSSH@", ", ".join(str(x) for x in PSSH[0])))
     exe = tmp_path / "mp4rd_host_asan"
     cmd = [cxx] + flags + ["-I", os.path.join(ROOT, "hevcbitstream_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
                            "-o", str(exe), str(src)]
@@ -250,7 +320,8 @@ def test_rules_and_init_reader_under_sanitizers(tmp_path):
     assert len(lines) == len(todo)
     verdicts = set()
     for i, ((kind, prm, buf), got) in enumerate(zip(todo, lines)):
-        want = want_init(buf, prm["track_id"]) if kind else want_samples(buf, prm)
+        want = (want_samples, want_init, want_protect, want_unprotect)[kind](buf, prm if kind == 0 else prm["track_id"])
         assert got == want, (i, kind, prm, len(buf))
         verdicts.add((kind, got.split()[0]))
-    assert verdicts == {(0, "ok"), (0, "big"), (0, "chain"), (0, "moof"), (0, "sample"), (1, "ok"), (1, "refused")}
+    assert verdicts == {(0, "ok"), (0, "big"), (0, "chain"), (0, "moof"), (0, "sample"), (1, "ok"), (1, "refused"), (2, "ok"), (2, "refused"),
+                        (3, "ok"), (3, "refused")}

@@ -54,7 +54,7 @@ int main()
         CHECK(hbs::mp4senc_clear_entry(65536, 0).clear == 65535 && hbs::mp4senc_clear_entry(65536, 1).clear == 1);
         CHECK(hbs::mp4senc_clear_entry(200000, 3).clear == 200000 - 3 * 65535 && hbs::mp4senc_clear_entry(200000, 3).protect == 0);
         CHECK(hbs::mp4senc_flat_count(0) == 0 && hbs::mp4senc_flat_count(7) == 1);
-        CHECK(hbs::mp4senc_numbering_ok(5, 5, 2, 7, true) && !hbs::mp4senc_numbering_ok(5, 5, 2, 8, true) && !hbs::mp4senc_numbering_ok(4, 5, 2, 7, false));
+        CHECK(hbs::mp4prot_numbering_ok(5, 5, 2, 7, true) && !hbs::mp4prot_numbering_ok(5, 5, 2, 8, true) && !hbs::mp4prot_numbering_ok(4, 5, 2, 7, false));
         /* a record that ends with its box, and with the allocation */
         const uint8_t rec[10] = {9, 9, 0, 1, 0, 5, 0, 0, 0, 20};
         uint8_t* r = exact(rec, 10);
